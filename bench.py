@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — stereo frames/sec through track + BA (BASELINE.json metric) on synthetic stereo + IMU.
 
-    python bench.py --gpus N --steps K --warmup W [--mode raw|dynamic] [--config zed|euroc|kitti] [--every-second-frame] [--shard] [--sequences S]
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR] [--mode raw|dynamic] [--config zed|euroc|kitti] [--every-second-frame] [--shard] [--sequences S]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A step = one stereo frame through the HIP front end (FeatureTracker::TrackImage, or TrackSemanticImage + InstsFeatManager::InstsTrack in
@@ -13,8 +13,11 @@ N > 1, default: every rank runs an independent sequence (replicas: config 4's "b
 data-path collective.  --shard: ONE window solve sharded by landmark over the N ranks with the reduced-system all-reduce —
 a BA-only microbench whose line is reported separately.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP-event timed per launch on its own stream, a second instrumented pass) and
-`cpu_baseline` (the CPU oracle = restated reference path, bounded sample, rank 0, N = 1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times ONE block of K steps (`value`, `ms_per_step`) and prints the line: nothing else runs.
+--full adds what the line carries beyond its headline: a second timed block, `roofline` (dominant kernel, HIP-event timed per launch on its own stream, a
+second instrumented pass), `cpu_baseline` (the CPU oracle = restated reference path, bounded sample, rank 0, N = 1 only) and, on the default workload,
+config.dynamic_line / host_frames_line / multiseq_line.
+--dump-outputs DIR: after the timed steps, what the timed path hands its caller after its last step goes to DIR/<name>.npy (float64, a few kB; see dump_outputs).
 """
 import argparse
 import gc
@@ -103,7 +106,9 @@ def main():
     ap.add_argument("--teams", action="store_true", help="(default since round 5) several host threads per dv_batch group: --runner-threads = a multiple of the group count, default two per group")
     ap.add_argument("--no-teams", action="store_true", help="with --sequences --batched: one host thread per dv_batch group (the default until round 4)")
     ap.add_argument("--sequence-threads", action="store_true", help="with --sequences: one host thread per sequence instead of one interleaving thread")
-    ap.add_argument("--blocks", type=int, default=2, help="consecutive timed blocks of --steps frames (the first is `value`; all are listed in config.block_values)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: second timed block, roofline pass, CPU baseline, dynamic / PCIe-inclusive / 16-sequence lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float64)")
+    ap.add_argument("--blocks", type=int, default=0, help="consecutive timed blocks of --steps frames (the first is `value`; all are listed in config.block_values; default 1, with --full 2 at least)")
     ap.add_argument("--timing-block", type=int, default=1, help="which block the instrumented (per-kernel HIP events) pass times")
     ap.add_argument("--scene", choices=["escort", "room"], default="escort", help="--mode dynamic: escort = boxes travelling with the camera (in view in every frame); room = room-fixed boxes (round-2 scene)")
     ap.add_argument("--erode", type=int, default=5, help="--mode dynamic: mask_morphology_size (viode.yaml: 5; the ZED / KITTI dynamic configs: 20)")
@@ -117,6 +122,9 @@ def main():
     ap.add_argument("--host-frames", action="store_true", help="frames handed over as host buffers: the PCIe-inclusive rate (never the headline value)")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
+    if args.dump_outputs and (args.sequences > 1 or args.shard):
+        ap.error("--dump-outputs covers the single-sequence line (not --sequences / --shard)")
+    args.blocks = max(2, args.blocks) if args.full else max(1, args.blocks)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves as FRESH child processes (one per GPU, RCCL rendezvous on 127.0.0.1) — before
@@ -178,7 +186,7 @@ def main():
 
     # north_star's TARGET configuration (>= 500 frames/s on 1280x720 VIODE-dynamic) rides on the default command: the same workload in dynamic mode, objects in every
     # frame, timed the same way (barriers, max over ranks), reported beside the headline as config.dynamic_line
-    want_dyn = args.mode == "raw" and args.config == "zed" and not args.no_dynamic_line and not args.every_second_frame and not args.host_frames
+    want_dyn = args.full and args.mode == "raw" and args.config == "zed" and not args.no_dynamic_line and not args.every_second_frame and not args.host_frames
     # measured FIRST: whichever dynamic-mode pass comes second in the process runs ~12 % slower in its first block (692 against 777 frames/s, same box, same work; the raw
     # pass does not care about the order: 1000 - 1030 either way).  BENCH_DYN_FIRST=0 restores the old order.
     dyn_first = os.environ.get("BENCH_DYN_FIRST", "1") == "1"
@@ -186,8 +194,8 @@ def main():
     if want_dyn and dyn_first:
         a2 = argparse.Namespace(**vars(args)); a2.mode = "dynamic"
         dyn = measure(a2, cfg, rank, world, local_rank, want_roofline=False)
-    out = measure(args, cfg, rank, world, local_rank)
-    extra_lines = args.mode == "raw" and args.config == "zed" and not args.no_extra_lines and not args.no_dynamic_line and not args.every_second_frame and not args.host_frames and world == 1
+    out = measure(args, cfg, rank, world, local_rank, want_roofline=args.full, dump_dir=args.dump_outputs)
+    extra_lines = args.full and args.mode == "raw" and args.config == "zed" and not args.no_extra_lines and not args.no_dynamic_line and not args.every_second_frame and not args.host_frames and world == 1
     if extra_lines:
         # the PCIe-inclusive rate beside the headline (never `value`): the same sequence handed over as pinned host buffers, upload inside the timed region
         a3 = argparse.Namespace(**vars(args)); a3.host_frames = True; a3.no_cpu_baseline = True
@@ -232,8 +240,21 @@ def main():
     dv_dist.finalize()
 
 
-def measure(args, cfg, rank, world, local_rank, want_roofline=True):
-    """one line of the bench: W warm-up + `blocks` x K timed frames of args.mode, then (rank 0) the instrumented pass and the CPU-oracle leg"""
+def dump_outputs(d, pipe):
+    """--dump-outputs: what the timed path hands its caller after its last step, float64 (a few kB): the estimator's sliding window (11 frames x 16), the summary of
+    the last window solve, and the trajectory so far (one row per nonlinear frame: t, p, q)"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    st = pipe.est.state
+    out = {"window": pipe.est.window().astype(np.float64),
+           "last_solve": np.array([st.frame, st.nonlinear, st.margin_old, st.n_landmarks, st.n_long, st.iterations, st.initial_cost, st.final_cost], np.float64),
+           "trajectory": np.column_stack([np.asarray(pipe.pose_times, np.float64), np.asarray(pipe.poses, np.float64).reshape(-1, 7)])}
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def measure(args, cfg, rank, world, local_rank, want_roofline=True, dump_dir=None):
+    """one line of the bench: W warm-up + `blocks` x K timed frames of args.mode, then (rank 0) the outputs (dump_dir), the instrumented pass and the CPU-oracle leg"""
     import numpy as np
     import torch
     from dynamic_vins_amd import dist as dv_dist
@@ -253,7 +274,7 @@ def measure(args, cfg, rank, world, local_rank, want_roofline=True):
     if args.host_frames and os.environ.get("BENCH_HOST_WARM", "0") == "1":
         warm_extra = 32
     warm_ba += warm_extra
-    n_frames = (warm_ba + max(2, args.blocks) * args.steps) * stride + 2
+    n_frames = (warm_ba + args.blocks * args.steps) * stride + 2
     cam = sim.ZED if (w, h) == (1280, 720) else sim.scaled_cam(sim.ZED, w, h, 1280, 720)
     dev = f"cuda:{local_rank}"
     _pad = torch.empty(args.prealloc_mb << 20, dtype=torch.uint8, device=dev) if args.prealloc_mb > 0 else None
@@ -357,7 +378,7 @@ def measure(args, cfg, rank, world, local_rank, want_roofline=True):
                              "t_since_start_s": round(t0 - T_PROCESS_START, 2)})
         return pipe, times, iters
 
-    pipe, times, iters = run(False, blocks=max(2, args.blocks))
+    pipe, times, iters = run(False, blocks=args.blocks)
     red_dev = dev if os.environ.get("BENCH_BACKEND", "nccl") != "gloo" else "cpu"
     times = [dv_dist.max_over_ranks(t, device=red_dev) for t in times]
     dt = times[0]                            # the contract: EXACTLY K timed steps -> the first block is the reported one
@@ -374,6 +395,8 @@ def measure(args, cfg, rank, world, local_rank, want_roofline=True):
                                           detections_per_frame=round(pipe.stat["object_detections"] / max(pipe.stat["frames"], 1), 2), min_detections_in_a_frame=int(pipe.stat["min_detections"]),
                                           object_features_per_frame=round(pipe.stat["object_features"] / max(pipe.stat["frames"], 1), 1)))
     dev_poses, dev_times = np.array(pipe.poses), list(pipe.pose_times)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, pipe)
     pipe.ctx.close()
 
     # ---- roofline of the dominant kernel: second, instrumented pass over the same timed region ----
@@ -428,7 +451,7 @@ def measure(args, cfg, rank, world, local_rank, want_roofline=True):
 
     # ---- CPU baseline: the oracle (restated reference path) on a bounded sample of the same workload; also gives the oracle trajectory ----
     cpu, ate_vs_oracle = None, None
-    if rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.gpus == 1 and args.full and not args.no_cpu_baseline:
         from tests import oracle_py
         flags = "-O3 -march=native -ffp-contract=off"
         try:           # timing build for THIS host; falls back to the checker's -O2 build
@@ -516,13 +539,15 @@ def measure(args, cfg, rank, world, local_rank, want_roofline=True):
                 "parallelism": f"replicas x{world} (independent sequences, no collective)", "landmarks_in_window": n_lm, "features_per_frame": nfeat,
                 "solver_iterations_per_frame": round(iters / (len(times) * args.steps), 2), "ate_rmse_m_vs_ground_truth": round(ate, 5),
                 "ate_rmse_m_vs_oracle": None if ate_vs_oracle is None else float(f"{ate_vs_oracle:.3e}"),
-                "second_block_ms_per_step": round(times[1] / args.steps * 1e3, 4), "second_block_value": round(dv_dist.whole_job_rate(args.steps, world, times[1]), 2),
                 "block_values": [round(dv_dist.whole_job_rate(args.steps, world, t), 2) for t in times],
                 "block_step_ms": frame_ms[: len(times)],
                 "warmup_requested": args.warmup, "git_head": git_head(), "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
                 "host_loop": ("C++ (dv_runner)" if args.host_loop == "cpp" else "Python (pipeline.py)"),
                 "frames": ("pinned host buffers: every frame (2 x %d bytes) crosses PCIe inside the timed region (%s)" % (w * h, "hipMemcpy2DAsync on the tracking stream" if os.environ.get("BENCH_HOST_ENGINE", "0") == "1" else "DV_MEM_PINNED: read in place by the pyramid kernel, no copy engine")) if args.host_frames else "resident in HBM before the timed region",
                 "warmup_note": "at least 12 untimed BA frames: the sliding window (11 frames) must be full before a step is a steady-state step (track + BA + marginalization)"}
+        if len(times) > 1:
+            conf["second_block_ms_per_step"] = round(times[1] / args.steps * 1e3, 4)
+            conf["second_block_value"] = round(dv_dist.whole_job_rate(args.steps, world, times[1]), 2)
         if dyn_info:
             conf["dynamic"] = dyn_info
         out = {"metric": "stereo frames/sec (track+BA)", "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": warm_ba,

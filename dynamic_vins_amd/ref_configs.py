@@ -1,8 +1,8 @@
-"""The reference's shipped parameter sets (config/**.yaml under /root/reference/dynamic_vins), as the values the hot path reads — so that tests and
+"""The reference's shipped parameter sets (its config/**.yaml), as the values the hot path reads — so that tests and
 bench.py run the front end and the back end at the numbers a user of the reference actually runs, not at round numbers of our own.
 
-Every entry cites the YAML it restates; tests/test_reference_configs.py::test_tables_match_the_shipped_yamls re-reads the files (when /root/reference is
-present) and fails if a value here drifts from them.  What is NOT taken from the YAMLs, and why:
+Every entry cites the YAML it restates; tests/test_reference_configs.py::test_tables_match_the_shipped_yamls checks it against the values of those files kept in
+tests/golden/ref_config.json and fails if a value here drifts from them.  What is NOT taken from the YAMLs, and why:
   * body_T_cam rotations: a calibration of the dataset's IMU frame.  The synthetic rig keeps its own body frame (x forward); what is kept is which kind of
     rig it is (IMU body vs. body = camera 0, `body_is_camera`) and the stereo baseline.
   * KITTI's 0.54 m baseline is shortened to 0.2 m: the synthetic room is 18 m across, not a street; at 0.54 m the near-field disparities (> 130 px) exceed

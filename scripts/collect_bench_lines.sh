@@ -4,9 +4,9 @@ TAG=${1:-r04_c}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out; mkdir -p $OUT; cd $ROOT
 run() { name=$1; shift; python3 bench.py "$@" > $OUT/${TAG}_bench${name}.json 2> $OUT/${TAG}_bench${name}.err || echo "bench${name}: exit $? (no line: see ${TAG}_bench${name}.err)"; }
-run ""                      
-run _steps20                --steps 20 --warmup 5
-run _dynamic                --mode dynamic --no-cpu-baseline
+run "" --full
+run _steps20                --full --steps 20 --warmup 5
+run _dynamic                --full --mode dynamic --no-cpu-baseline
 run _sequences16_batched    --sequences 16 --batched --steps 60
 run _sequences16_groups8    --sequences 16 --batched --group-size 8 --steps 60
 run _sequences16_teams      --sequences 16 --batched --teams --runner-threads 4 --steps 60

@@ -13,9 +13,9 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 BATCHED="--sequences 32 --batched --group-size 16 --steps 30"
 cd $ROOT
-python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
-python3 bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_steps20.json 2>/dev/null
-python3 bench.py --mode dynamic --no-cpu-baseline > $OUT/${TAG}_bench_dynamic.json 2>/dev/null
+python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench_steps20.json 2>/dev/null
+python3 bench.py --full --mode dynamic --no-cpu-baseline > $OUT/${TAG}_bench_dynamic.json 2>/dev/null
 python3 bench.py --sequences 16 --batched --steps 60 > $OUT/${TAG}_bench_sequences16_batched.json 2>$OUT/${TAG}_bench_sequences16_batched.err || true
 python3 bench.py --sequences 16 --batched --teams --runner-threads 4 --steps 60 > $OUT/${TAG}_bench_sequences16_teams.json 2>/dev/null || true
 python3 bench.py --sequences 32 --batched --group-size 8 --steps 40 > $OUT/${TAG}_bench_sequences32_groups8.json 2>/dev/null || true
@@ -25,10 +25,10 @@ python3 bench.py --config kitti --sequences 21 --batched --steps 60 > $OUT/${TAG
 python3 bench.py --config kitti --sequences 21 --batched --group-size 7 --steps 60 > $OUT/${TAG}_bench_kitti21_groups7.json 2>/dev/null || true
 python3 bench.py --sequences 8 --runner-threads 2 --steps 40 > $OUT/${TAG}_bench_sequences8.json 2>/dev/null || true
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -- python3 $ROOT/bench.py --steps 30 --no-cpu-baseline --no-dynamic-line > $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace_dyn -- python3 $ROOT/bench.py --mode dynamic --steps 30 --no-cpu-baseline > $OUT/${TAG}_bench_dynamic_under_rocprof.json 2>/dev/null
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_fetch -- python3 $ROOT/bench.py --steps 30 --no-cpu-baseline --no-dynamic-line > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_write -- python3 $ROOT/bench.py --steps 30 --no-cpu-baseline --no-dynamic-line > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -- python3 $ROOT/bench.py --full --steps 30 --no-cpu-baseline --no-dynamic-line > $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace_dyn -- python3 $ROOT/bench.py --full --mode dynamic --steps 30 --no-cpu-baseline > $OUT/${TAG}_bench_dynamic_under_rocprof.json 2>/dev/null
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_fetch -- python3 $ROOT/bench.py --full --steps 30 --no-cpu-baseline --no-dynamic-line > /dev/null 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_write -- python3 $ROOT/bench.py --full --steps 30 --no-cpu-baseline --no-dynamic-line > /dev/null 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace_bat -- python3 $ROOT/bench.py $BATCHED > $OUT/${TAG}_bench_batched_under_rocprof.json 2>/dev/null
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_fetch_bat -- python3 $ROOT/bench.py $BATCHED > /dev/null 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_write_bat -- python3 $ROOT/bench.py $BATCHED > /dev/null 2>&1

@@ -17,10 +17,10 @@ export GPU_MAX_HW_QUEUES=8          # (under rocprofv3 the runtime is
 BATCHED="--sequences 32 --batched --group-size 16 --steps 30"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/${TAG}_*
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${TAG}_trace -- python3 $ROOT/bench.py --steps 30 --no-cpu-baseline --no-dynamic-line --no-extra-lines > $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${TAG}_trace_dyn -- python3 $ROOT/bench.py --mode dynamic --steps 30 --no-cpu-baseline > $OUT/${TAG}_bench_dynamic_under_rocprof.json 2>/dev/null
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/${TAG}_pmc_fetch -- python3 $ROOT/bench.py --steps 30 --no-cpu-baseline --no-dynamic-line --no-extra-lines > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/${TAG}_pmc_write -- python3 $ROOT/bench.py --steps 30 --no-cpu-baseline --no-dynamic-line --no-extra-lines > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${TAG}_trace -- python3 $ROOT/bench.py --full --steps 30 --no-cpu-baseline --no-dynamic-line --no-extra-lines > $OUT/${TAG}_bench_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${TAG}_trace_dyn -- python3 $ROOT/bench.py --full --mode dynamic --steps 30 --no-cpu-baseline > $OUT/${TAG}_bench_dynamic_under_rocprof.json 2>/dev/null
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/${TAG}_pmc_fetch -- python3 $ROOT/bench.py --full --steps 30 --no-cpu-baseline --no-dynamic-line --no-extra-lines > /dev/null 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/${TAG}_pmc_write -- python3 $ROOT/bench.py --full --steps 30 --no-cpu-baseline --no-dynamic-line --no-extra-lines > /dev/null 2>&1
 export GPU_MAX_HW_QUEUES=12
 export BENCH_BIT_IDENTITY=0
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${TAG}_trace_bat -- python3 $ROOT/bench.py $BATCHED > $OUT/${TAG}_bench_batched_under_rocprof.json 2>/dev/null
@@ -35,16 +35,16 @@ python3 scripts/pmc_summary.py /tmp/${TAG}_pmc_fetch /tmp/${TAG}_pmc_write > $OU
 # the bench reads profiles/pmc_traffic*.json: put the fresh ones there BEFORE the bench lines, so that the lines carry roofline.traffic
 cp $OUT/${TAG}_pmc_traffic.json profiles/pmc_traffic.json; cp $OUT/${TAG}_pmc_traffic_batched.json profiles/pmc_traffic_batched.json
 run() { name=$1; shift; python3 bench.py "$@" > $OUT/${TAG}_bench${name}.json 2> $OUT/${TAG}_bench${name}.err || echo "bench${name}: exit $? (no line: see ${TAG}_bench${name}.err)"; }
-run ""
-run _steps20                --steps 20 --warmup 5
-run _dynamic                --mode dynamic --no-cpu-baseline
+run "" --full
+run _steps20                --full --steps 20 --warmup 5
+run _dynamic                --full --mode dynamic --no-cpu-baseline
 run _sequences16_batched    --sequences 16 --batched --steps 60
 run _sequences16_no_teams   --sequences 16 --batched --no-teams --steps 60
 run _sequences32_batched    --sequences 32 --batched --steps 40
 run _sequences64_batched    --sequences 64 --batched --steps 40
 run _kitti21_batched        --config kitti --sequences 21 --batched --steps 60
 run _sequences8             --sequences 8 --runner-threads 2 --steps 40
-run _steps20_b              --steps 20 --warmup 5
+run _steps20_b              --full --steps 20 --warmup 5
 # worst frame of a dynamic 1280x720 sequence from a cold process (scripts/dyn_cold_frames.py; tests/test_frame_gaps.py), copy kernels vs the copy engines
 for i in 1 2 3; do python3 scripts/dyn_cold_frames.py 60 0 | tail -1 > $OUT/${TAG}_cold_dynamic_frames_$i.json; done
 DVINS_COPY_ENGINE=1 python3 scripts/dyn_cold_frames.py 60 0 | tail -1 > $OUT/${TAG}_cold_dynamic_frames_copy_engine.json

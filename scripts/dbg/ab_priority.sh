@@ -1,6 +1,6 @@
 # stream priorities: back-end streams highest (1) / front-end streams lowest (2) against all default (0); one box, interleaved
 cd /root/repo
-one() { tag="$1"; shift; timeout 400 python bench.py "$@" --no-cpu-baseline 2>/dev/null | python -c "
+one() { tag="$1"; shift; timeout 400 python bench.py "$@" --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 for ln in sys.stdin:
     if ln.startswith('{'):

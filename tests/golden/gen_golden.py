@@ -21,6 +21,9 @@
                      text; the functions are Python-2 era (they .remove() from dict.keys()), so they are run from their source text on dict objects whose
                      keys() returns a list, as it did when the file was written.
 4. aux_kat.npz     — the same for cv::remap with fixed-point maps, the object solve and the line-only solve (oracle outputs; parity unpinned).
+5. ref_config.json, ref_topics.json (`gen_golden.py ref_config ref_topics`, DVINS_REFERENCE = the reference checkout) — the values of the reference's shipped
+                     configuration files that the shim and the tests read (scalars, body_T_cam matrices, camera intrinsics), and the ROS topic table of its
+                     SystemCallBack / publishers (names, message types, queue sizes, callbacks).
 Only data is written: inputs and expected outputs.
 """
 import ctypes as C
@@ -301,9 +304,114 @@ def gen_gftt_cuda(o):
     print("gftt_cuda_kat.npz: corners", len(out["corners_nomask"]), len(out["corners_mask"]), "cpu rule under the same mask", len(out["corners_mask_cpu_rule"]), "naive rows", out["track_n"])
 
 
+# ---- the reference's shipped configuration files and ROS topic table, as data (tests/test_reference_configs.py, tests/test_node.py) ----
+# Only the values the shim and the tests read are kept; the YAML files themselves are not stored.  DVINS_REFERENCE = the reference checkout's root.
+SHIM_KEYS = ("slam_type dataset_type num_of_cam image_width image_height max_cnt min_dist flow_back use_mask_morphology mask_morphology_size max_dynamic_cnt "
+             "min_dynamic_dist undistort_input dst_mode only_frontend imu plane_constraint max_num_iterations max_solver_time keyframe_parallax INIT_DEPTH acc_n gyr_n "
+             "acc_w gyr_w g_norm td use_line line_min_obs use_det3d instance_init_min_num static_inst_threshold static_inst_as_background estimate_extrinsic estimate_td "
+             "kitti_calib_path cam0_calib cam1_calib image0_topic image1_topic image0_segmentation_topic image1_segmentation_topic imu_topic rgb_to_label_file basic_dir "
+             "dynamic_label_id").split()
+CAM_KEYS = ("model_type", "image_width", "image_height", "k1", "k2", "p1", "p2", "fx", "fy", "cx", "cy")
+
+
+def _ref_tree():
+    root = os.environ.get("DVINS_REFERENCE")
+    if not root or not os.path.isdir(os.path.join(root, "dynamic_vins")):
+        raise SystemExit("set DVINS_REFERENCE to the root of the reference checkout")
+    return os.path.join(root, "dynamic_vins")
+
+
+def _yaml_entries(path):
+    """top-level `key: value` (value text as written, comments cut), nested `section.key: value`, and the data lists of !!opencv-matrix nodes"""
+    scal, mats, section, in_data = {}, {}, None, False
+    for ln in open(path, encoding="utf-8", errors="replace"):
+        ln = ln.split("#", 1)[0].rstrip()
+        if not ln.strip() or ln[0] == "%" or ln.strip() == "---":
+            continue
+        if in_data:
+            mats[section] += [float(v) for v in ln.replace("]", "").split(",") if v.strip()]
+            in_data = "]" not in ln
+            continue
+        if ":" not in ln:
+            continue
+        k, v = ln.split(":", 1)
+        k, v = k.strip(), v.strip()
+        if ln[0] not in " \t":
+            section = k
+            if v.startswith("!!opencv-matrix"):
+                mats[k] = []
+            elif v:
+                scal[k] = v
+        elif section in mats and k == "data":
+            mats[section] += [float(x) for x in v.replace("[", "").replace("]", "").split(",") if x.strip()]
+            in_data = "]" not in v
+        elif section is not None and section not in mats:
+            scal[section + "." + k] = v
+    return scal, mats
+
+
+def gen_ref_config():
+    import json
+    ref = _ref_tree()
+    cfg = os.path.join(ref, "config")
+    out = {"configs": {}, "cameras": {}, "label_files": []}
+    for dirpath, _, files in sorted(os.walk(cfg)):
+        for f in sorted(files):
+            path = os.path.join(dirpath, f)
+            if not f.endswith(".yaml"):
+                continue
+            scal, mats = _yaml_entries(path)
+            if "slam_type" not in scal:
+                continue
+            rel = os.path.relpath(path, cfg)
+            out["configs"][rel] = {"scalars": {k: v for k, v in scal.items() if k in SHIM_KEYS},
+                                   "matrices": {k: v for k, v in mats.items() if k in ("body_T_cam0", "body_T_cam1")}}
+            for ck in ("cam0_calib", "cam1_calib"):
+                cam = os.path.join(dirpath, scal.get(ck, "").strip('"'))
+                if ck in scal and os.path.isfile(cam):
+                    cs, _ = _yaml_entries(cam)
+                    out["cameras"][os.path.relpath(cam, cfg)] = {k: v for k, v in cs.items() if k.split(".")[-1] in CAM_KEYS}
+            lab = scal.get("rgb_to_label_file", "").strip('"')
+            if lab and os.path.isfile(os.path.join(ref, lab)) and lab not in out["label_files"]:
+                out["label_files"].append(lab)          # only its presence matters to the tests: they write a header-only stand-in
+    json.dump(out, open(os.path.join(HERE, "ref_config.json"), "w"), indent=1, sort_keys=True)
+    print("ref_config.json:", len(out["configs"]), "configs,", len(out["cameras"]), "camera files")
+
+
+def gen_ref_topics():
+    """SystemCallBack's subscriptions (topic or config key, queue, callback, message type) and every topic the publishers use"""
+    import json
+    src = os.path.join(_ref_tree(), "src")
+    cb = open(os.path.join(src, "utils/io/system_call_back.cpp")).read()
+    hdr = open(os.path.join(src, "utils/io/system_call_back.h")).read()
+    key_of = {"kImage0Topic": "image0_topic", "kImage1Topic": "image1_topic", "kImage0SegTopic": "image0_segmentation_topic", "kImage1SegTopic": "image1_segmentation_topic", "kImuTopic": "imu_topic"}
+    subs = []
+    for _, var, lit, queue, callback in re.findall(r"nh\.subscribe\(\s*(io_para::(\w+)|\"([^\"]+)\")\s*,\s*(\d+)\s*,\s*&SystemCallBack::(\w+)", cb):
+        arg = re.search(r"void\s+%s\(const\s+(\w+)::(\w+)ConstPtr" % callback, hdr)
+        subs.append({"name": key_of[var] if var else lit, "from_config": int(bool(var)), "queue": int(queue), "callback": callback,
+                     "msg_type": f"{arg.group(1)}/{arg.group(2)}" if arg else None})
+    vis = "".join(open(os.path.join(src, f)).read() for f in ("utils/io/visualization.cpp", "system/main.cpp", "estimator/estimator.cpp"))
+    pubs = {}
+    for t, name in re.findall(r"PublisherMap::Pub<\s*([\w:]+)\s*>\([^,]+,\s*\"(\w+)\"", vis): pubs[name] = {"Marker": "visualization_msgs/Marker"}.get(t, t.replace("::", "/"))
+    for t, name in re.findall(r"GetPublisher<\s*([\w:]+)\s*>\(\s*\"(\w+)\"", vis): pubs[name] = {"MarkerArray": "visualization_msgs/MarkerArray"}.get(t, t.replace("::", "/"))
+    for name in re.findall(r"PubMarkers\([^,]+,\s*\"(\w+)\"", vis): pubs[name] = "visualization_msgs/MarkerArray"
+    for name in re.findall(r"PubImage\([^,]+,\s*\"(\w+)\"", vis): pubs[name] = "sensor_msgs/Image"
+    for var, name in re.findall(r"PubPointCloud\(\s*\*?(\w+)\s*,\s*\"(\w+)\"", vis):
+        pubs[name] = "sensor_msgs/PointCloud2" if name in ("instance_point_cloud", "stereo_point_cloud") else "sensor_msgs/PointCloud"      # pcl clouds go out as PointCloud2 (publisher_map.cpp)
+    json.dump({"subscriptions": subs, "publications": pubs}, open(os.path.join(HERE, "ref_topics.json"), "w"), indent=1, sort_keys=True)
+    print("ref_topics.json:", len(subs), "subscriptions,", len(pubs), "publications")
+
+
 if __name__ == "__main__":
-    import oracle_py
     which = sys.argv[1:] or ["ate", "front", "back", "aux", "gftt_cuda"]
+    if "ref_config" in which:
+        gen_ref_config()
+    if "ref_topics" in which:
+        gen_ref_topics()
+    which = [w for w in which if w not in ("ref_config", "ref_topics")]
+    if not which:
+        raise SystemExit(0)
+    import oracle_py
     if "ate" in which:
         gen_ate()
         gen_associate()

@@ -1,6 +1,6 @@
 """The reference's SHIPPED parameter sets (config/**.yaml) through the product.
 
-CPU (`-m "not gpu"`; skipped where /root/reference is absent — the GPU box):
+CPU (`-m "not gpu"`; the shipped files are rebuilt from the values tests/golden/ref_config.json keeps of them — the keys the shim and these tests read):
   * every top-level YAML the reference ships is read by the C++ shim's ReadConfig (dynamic_vins_amd/host/dvins_shim.hpp) and either yields the values an
     independent Python read of the same file gives, or throws exactly where the reference's own Config / VioParameters constructors throw
     (utils/parameters.cpp:134-137, estimator/vio_parameters.cpp:54-61);
@@ -12,6 +12,7 @@ GPU (`-m gpu`): images -> trajectory parity against the oracle AT those paramete
   LinePoint + dynamic with detector segments through UndistortedLineEndPoints), and BASELINE.json config 5 as stated — the ZED set with use_line 1
   (1280x720 LinePoint + dynamic together).  Bars as in tests/test_dynamic_pipeline.py."""
 import glob
+import json
 import os
 import subprocess
 
@@ -21,7 +22,7 @@ import pytest
 from dynamic_vins_amd import ref_configs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_CFG = "/root/reference/dynamic_vins/config"
+REF_DATA = os.path.join(ROOT, "tests", "golden", "ref_config.json")          # tests/golden/gen_golden.py ref_config
 KITTI_CALIB = os.path.join(ROOT, "tests", "golden", "config", "kitti_calib") + "/"
 
 
@@ -36,10 +37,41 @@ def shim_exe(tmp_path_factory):
     return exe
 
 
-def shipped_yamls():
+@pytest.fixture(scope="module")
+def ref_cfg(tmp_path_factory):
+    """the reference's config/ tree rebuilt from tests/golden/ref_config.json: every shipped configuration file with the scalars and body_T_cam matrices the shim
+    reads, the camera files they name, and a header-only stand-in for the label table a VIODE configuration points to (only its presence is read here)"""
+    data = json.load(open(REF_DATA))
+    root = tmp_path_factory.mktemp("ref")
+    for rel, c in data["configs"].items():
+        lines = ["%YAML:1.0", "---"] + ["%s: %s" % kv for kv in c["scalars"].items()]
+        for k, m in c["matrices"].items():
+            lines += ["%s: !!opencv-matrix" % k, "  rows: %d" % (len(m) // 4), "  cols: 4", "  dt: d", "  data: [%s]" % ", ".join(repr(float(x)) for x in m)]
+        _write(root / "config" / rel, lines)
+    for rel, c in data["cameras"].items():
+        lines, sections = ["%YAML:1.0", "---"], {}
+        for k, v in c.items():
+            if "." in k:
+                sections.setdefault(k.split(".", 1)[0], []).append("   %s: %s" % (k.split(".", 1)[1], v))
+            else:
+                lines.append("%s: %s" % (k, v))
+        for sec, body in sections.items():
+            lines += [sec + ":"] + body
+        _write(root / "config" / rel, lines)
+    for rel in data["label_files"]:
+        _write(root / rel, ["label_id,r,g,b"])
+    return str(root / "config")
+
+
+def _write(path, lines):
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text("\n".join(lines) + "\n")
+
+
+def shipped_yamls(ref_cfg):
     """the top-level configuration files (they name a slam_type); camera files and VIODE's own calibration dump are not configs"""
     out = []
-    for f in sorted(glob.glob(os.path.join(REF_CFG, "**", "*.yaml"), recursive=True)):
+    for f in sorted(glob.glob(os.path.join(ref_cfg, "**", "*.yaml"), recursive=True)):
         if "slam_type" in ref_configs.yaml_scalars(f):
             out.append(f)
     return out
@@ -74,9 +106,8 @@ def test_estimate_extrinsic_and_td_keys_reach_the_estimator_config(shim_exe, tmp
             assert c["estimate"] == want and c["use_imu"] == str(imu), (ex, td, imu, c["estimate"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="the reference's config tree is not on this machine")
-def test_every_shipped_yaml_constructs_the_shim_config(shim_exe):
-    files = shipped_yamls()
+def test_every_shipped_yaml_constructs_the_shim_config(shim_exe, ref_cfg):
+    files = shipped_yamls(ref_cfg)
     assert len(files) >= 14, files
     built, thrown = [], []
     for f in files:
@@ -87,9 +118,9 @@ def test_every_shipped_yaml_constructs_the_shim_config(shim_exe):
         if isinstance(c, str):
             # the only legitimate failures: a dynamic config without use_det3d / instance_init_min_num (the reference throws there too), or a camera model off the path
             assert dynamic and ("use_det3d" not in y or "instance_init_min_num" not in y) or "PINHOLE" in c, (f, c)
-            thrown.append(os.path.relpath(f, REF_CFG))
+            thrown.append(os.path.relpath(f, ref_cfg))
             continue
-        built.append(os.path.relpath(f, REF_CFG))
+        built.append(os.path.relpath(f, ref_cfg))
         assert c["dynamic"] == str(int(dynamic)) and c["naive"] == str(int(st == "naive")), f
         for key, ykey in [("width", "image_width"), ("height", "image_height"), ("max_cnt", "max_cnt"), ("min_dist", "min_dist"), ("max_iters", "max_num_iterations"),
                           ("use_imu", "imu"), ("use_line", "use_line"), ("plane_constraint", "plane_constraint")]:
@@ -114,10 +145,9 @@ def test_every_shipped_yaml_constructs_the_shim_config(shim_exe):
         assert need in built, (need, thrown)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="the reference's config tree is not on this machine")
-def test_tables_match_the_shipped_yamls():
+def test_tables_match_the_shipped_yamls(ref_cfg):
     for name, c in ref_configs.CONFIGS.items():
-        path = os.path.join(REF_CFG, c["yaml"])
+        path = os.path.join(ref_cfg, c["yaml"])
         y = ref_configs.yaml_scalars(path)
         assert (c["w"], c["h"]) == (int(y["image_width"]), int(y["image_height"])), name
         assert (c["max_cnt"], c["min_dist"], c["max_iters"]) == (int(y["max_cnt"]), int(y["min_dist"]), int(y["max_num_iterations"])), name
