@@ -34,10 +34,15 @@ def small_rot(v):
 
 def make_window(oracle, seed=1, nframes=11, nlm=120, use_imu=1, max_iters=8, pix_sigma=0.4, with_prior=False, dt_frame=0.1,
                 pose_noise=(0.03, 0.01), depth_noise=0.08, stereo_ratio=0.8, plane_kind=0, outlier_ratio=0.0,
-                feat_vel=False, td_true=0.0, ex_noise=(0.0, 0.0), free_blocks=0, prior_ex_scale=0.01):
+                feat_vel=False, td_true=0.0, ex_noise=(0.0, 0.0), free_blocks=0, prior_ex_scale=0.01, prior_ex_offset=0.0,
+                sb_noise=1.0, prior_scale=30.0, prior_x0_noise=0.01):
     """feat_vel: the factors carry the features' image velocities (what the td Jacobian needs); td_true: the observations were taken td_true seconds late
     (x + v td_true: the factor undoes it with the td being estimated); ex_noise: (metres, radians) perturbation of the extrinsics handed to the solve;
-    free_blocks: dv_ba_problem::free_blocks (bit 0 extrinsics, bit 1 td).  The defaults draw the same random numbers as before these options existed."""
+    free_blocks: dv_ba_problem::free_blocks (bit 0 extrinsics, bit 1 td); prior_ex_offset: spread (metres, radians, seconds) of the prior's linearisation
+    point of the extrinsic and td blocks around the states (0: at the states, so their dx, and their share of the prior's gradient A dx, start at zero);
+    sb_noise: scale of the speed-bias perturbations; prior_scale: scale of the prior's square root (A grows with its square: how firmly the prior pins the
+    gauge directions of a VIO window); prior_x0_noise: spread of the prior's linearisation point of the poses' positions and the
+    speed-biases around the states, and of the point its b pulls towards.  The defaults draw the same random numbers as before these options existed."""
     rng = np.random.default_rng(seed)
     traj = sim.Trajectory()
     t0 = 2.0 + 0.37 * seed
@@ -105,9 +110,9 @@ def make_window(oracle, seed=1, nframes=11, nlm=120, use_imu=1, max_iters=8, pix
         pn = p_wb[k] + (rng.normal(0, pose_noise[0], 3) if (use_imu or k > 0) else 0)
         pose[k, :3] = pn
         pose[k, 3:] = quat_xyzw(Rn)
-        sb[k, :3] = v_wb[k] + rng.normal(0, 0.05, 3)
-        sb[k, 3:6] = rng.normal(0, 0.01, 3)
-        sb[k, 6:9] = rng.normal(0, 0.002, 3)
+        sb[k, :3] = v_wb[k] + rng.normal(0, 0.05 * sb_noise, 3)
+        sb[k, 3:6] = rng.normal(0, 0.01 * sb_noise, 3)
+        sb[k, 6:9] = rng.normal(0, 0.002 * sb_noise, 3)
     ex = np.zeros((2, 7))
     for c in range(2):
         ex[c, :3] = tic[c]
@@ -153,14 +158,21 @@ def make_window(oracle, seed=1, nframes=11, nlm=120, use_imu=1, max_iters=8, pix
             src = pose[idx] if ty == 0 else sb[idx] if ty == 1 else ex[idx] if ty == 2 else np.array([0.0])
             x0 = np.array(src, float).copy()
             if ty == 0:
-                x0[:3] += rng.normal(0, 0.01, 3)
+                x0[:3] += rng.normal(0, prior_x0_noise, 3)
             if ty == 1:
-                x0 += rng.normal(0, 0.01, 9)
+                x0 += rng.normal(0, prior_x0_noise, 9)
+            if ty == 2 and prior_ex_offset:
+                x0[:3] += rng.normal(0, prior_ex_offset, 3)
+                (vx, vy, vz), (x, y, z, w) = rng.normal(0, prior_ex_offset / 2, 3), x0[3:]          # q0 = q [1, v]: x y z w
+                q = np.array([w * vx + x + y * vz - z * vy, w * vy - x * vz + y + z * vx, w * vz + x * vy - y * vx + z, w - x * vx - y * vy - z * vz])
+                x0[3:] = q / np.linalg.norm(q)
+            if ty == 3 and prior_ex_offset:
+                x0 += rng.normal(0, prior_ex_offset)
             for j in range(len(x0)):
                 prior.x0[i][j] = x0[j]
             off += sz
         n = off
-        M = rng.normal(0, 1, (n + 10, n)) * 30.0
+        M = rng.normal(0, 1, (n + 10, n)) * prior_scale
         M[:, -13:] *= prior_ex_scale          # the extrinsic / td columns of the prior (weak by default: the blocks are constants of the solve)
         A = M.T @ M
         # a near-null direction, like the gauge freedom of a real prior
@@ -168,7 +180,7 @@ def make_window(oracle, seed=1, nframes=11, nlm=120, use_imu=1, max_iters=8, pix
         v /= np.linalg.norm(v)
         Pn = np.eye(n) - np.outer(v, v)
         A = Pn @ A @ Pn
-        b = A @ rng.normal(0, 0.01, n)
+        b = A @ rng.normal(0, prior_x0_noise, n)
         prior.valid, prior.n, prior.nblocks = 1, n, len(blocks)
         oracle.lib.dvo_prior_c0.restype = C.c_double
         oracle.lib.dvo_prior_c0.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
