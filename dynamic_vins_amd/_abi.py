@@ -70,6 +70,11 @@ SIGNATURES = {
     "dv_bgr2gray": (C.c_int, [_ctx, _u8p, C.c_int, C.c_int, C.c_int, _u8p, C.c_int]),
     "dv_remap": (C.c_int, [_ctx, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _u8p, C.c_int]),
     "dv_set_undistort_maps": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "dv_optimal_new_camera": (C.c_int, [C.POINTER(dv_cam), C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double)]),
+    "dv_init_undistort_map": (C.c_int, [_ctx, C.POINTER(dv_cam), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "dv_undistort_setup": (C.c_int, [_ctx, C.c_double, C.POINTER(dv_cam), C.POINTER(dv_cam)]),
+    "dv_get_undistort_maps": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "dv_get_cameras": (C.c_int, [_ctx, C.POINTER(dv_cam), C.POINTER(dv_cam)]),
     "dv_pyr_down": (C.c_int, [_ctx, _u8p, C.c_int, C.c_int, C.c_int, _u8p, C.c_int]),
     "dv_circle_mask": (C.c_int, [_ctx, _u8p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, C.c_int, C.c_int]),
     "dv_erode": (C.c_int, [_ctx, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, C.c_int]),

@@ -202,6 +202,7 @@ struct dv_ctx {
     struct UnmaskJob { int x, y, w, h; size_t off; };
     std::vector<UnmaskJob> unmask; void* unmask_pinned = nullptr; size_t unmask_pinned_bytes = 0;
     DevBuf undist_buf[2]; bool undist[2] = { false, false }; int undist_w = 0, undist_h = 0;      // cfg::is_undistort_input: fixed-point maps per camera (map1 | map2)
+    bool cam_switched = false; dv_cam cam_orig[2]{};      // dv_undistort_setup: cfg.cam0 / cam1 hold (newK, 0); the cameras the ctx was created with, restored when the maps are removed
     DevBuf out_buf; dv_feat* out_dev = nullptr; int* nout_dev = nullptr;
     dv_feat* out_pinned = nullptr; int* nout_pinned = nullptr; int* err_pinned = nullptr;
     hipEvent_t done = nullptr; bool pending = false;

@@ -74,6 +74,9 @@ void dv_launch_pyr_down2(const uint8_t* src0, const uint8_t* src1, int sw, int s
 void dv_launch_bgr2gray(const uint8_t* src0, const uint8_t* src1, int w, int h, int spitch, uint8_t* dst0, uint8_t* dst1, int dpitch, hipStream_t s);
 void dv_launch_remap(const uint8_t* src0, const uint8_t* src1, int w, int h, int spitch, int cn, int to_gray, const int16_t* m1_0, const uint16_t* m2_0,
                      const int16_t* m1_1, const uint16_t* m2_1, uint8_t* dst0, uint8_t* dst1, int dpitch, hipStream_t s);
+// cv::initUndistortRectifyMap(..., CV_16SC2) (undistort_map.hip): xcol = w doubles of device scratch (the row walk's _x values), map1 8-byte / map2 4-byte aligned device memory
+#define DV_UMAP_TILE 512       // consecutive pixels (row-major over the whole image) per workgroup: 256 lanes x 2 pixels.  tests/test_undistort_setup.py reads this line (MAP_TILE): its widths sit one below / above the tile
+void dv_launch_undistort_map(const dv_cam& cam, const double* newK4, int w, int h, double* xcol, int16_t* map1_xy, uint16_t* map2, hipStream_t s);
 void dv_launch_viode_mask(const uint8_t* seg, int w, int h, int spitch, const uint32_t* dyn_keys, int nkeys, uint8_t* merge, uint8_t* inv, int mpitch,
                           uint32_t* key_img, int32_t* boxes, hipStream_t s);
 void dv_launch_lk_generic(const DvPyr& A, const DvPyr& B, const float2* pts_a, int n, int max_level, int iters,

@@ -32,6 +32,20 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data)
 
 
+def optimal_new_camera(cam, w, h, alpha=0.0):
+    """cv::getOptimalNewCameraMatrix(K, D, (w, h), alpha, (w, h)) for a pinhole + radtan dv_cam (or its 8-tuple) -> (fx, fy, cx, cy).  Host code: needs no GPU."""
+    lib = _abi.load()
+    c = cam if isinstance(cam, dv_cam) else make_cam(*cam)
+    nk = (C.c_double * 4)()
+    if lib.dv_optimal_new_camera(C.byref(c), int(w), int(h), float(alpha), nk) != 0:
+        raise DvinsError(lib.dv_last_error(None).decode())
+    return tuple(nk)
+
+
+def cam_tuple(c):
+    return (c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2)
+
+
 class Context:
     """Owns a dv_ctx (device memory + stream).  One per thread, like the reference's FeatureTracker."""
 
@@ -267,11 +281,46 @@ class Context:
         """cfg::is_undistort_input: install (or, with map1=None, remove) the fixed-point undistortion maps of camera 0 / 1"""
         if map1 is None:
             self._check(self.lib.dv_set_undistort_maps(self.h, int(cam), None, None, 0, 0))
+            self.cfg.cam0, self.cfg.cam1 = self.cameras()      # the original cameras again, had undistort_setup switched them
             return
         m1, m2 = np.ascontiguousarray(map1, np.int16), np.ascontiguousarray(map2, np.uint16)
         h, w = m2.shape
         assert m1.shape == (h, w, 2)
         self._check(self.lib.dv_set_undistort_maps(self.h, int(cam), m1.ctypes.data, m2.ctypes.data, w, h))
+        self.cfg.cam0, self.cfg.cam1 = self.cameras()      # own maps after undistort_setup: that camera's original intrinsics hold again
+
+    def init_undistort_map(self, cam, new_k, w, h, map1=None, map2=None):
+        """cv::initUndistortRectifyMap(K, D, I, newK, (w, h), CV_16SC2) on the device -> (map1 (h, w, 2) int16, map2 (h, w) uint16) as host arrays, or — map1 / map2 given
+        as device pointers (int) — written there (DV_MEM_DEVICE)"""
+        c = cam if isinstance(cam, dv_cam) else make_cam(*cam)
+        nk = (C.c_double * 4)(*[float(v) for v in new_k])
+        if map1 is not None:
+            self._check(self.lib.dv_init_undistort_map(self.h, C.byref(c), nk, int(w), int(h), _ptr(int(map1)), _ptr(int(map2)), DV_MEM_DEVICE))
+            return None
+        m1, m2 = np.zeros((h, w, 2), np.int16), np.zeros((h, w), np.uint16)
+        self._check(self.lib.dv_init_undistort_map(self.h, C.byref(c), nk, int(w), int(h), m1.ctypes.data, m2.ctypes.data, DV_MEM_HOST))
+        return m1, m2
+
+    def undistort_setup(self, alpha=0.0):
+        """cfg::is_undistort_input as InitOneCamera sets it up (utils/camera_model.cpp:479-504): new camera matrices, both map pairs built and installed on the device, the
+        ctx's cameras switched to (newK, 0).  From then on the tracker takes DISTORTED frames.  -> (new_cam0, new_cam1); set_undistort_maps(0) undoes it."""
+        c0, c1 = dv_cam(), dv_cam()
+        self._check(self.lib.dv_undistort_setup(self.h, float(alpha), C.byref(c0), C.byref(c1)))
+        self.cfg.cam0, self.cfg.cam1 = c0, c1
+        return c0, c1
+
+    def undistort_maps(self, cam):
+        """the installed maps of camera 0 / 1 -> (map1 (h, w, 2) int16, map2 (h, w) uint16)"""
+        w, h = self.cfg.width, self.cfg.height
+        m1, m2 = np.zeros((h, w, 2), np.int16), np.zeros((h, w), np.uint16)
+        self._check(self.lib.dv_get_undistort_maps(self.h, int(cam), m1.ctypes.data, m2.ctypes.data, DV_MEM_HOST))
+        return m1, m2
+
+    def cameras(self):
+        """the cameras the ctx lifts with at the moment"""
+        c0, c1 = dv_cam(), dv_cam()
+        self._check(self.lib.dv_get_cameras(self.h, C.byref(c0), C.byref(c1)))
+        return c0, c1
 
     def pyr_down(self, img):
         h, w = img.shape

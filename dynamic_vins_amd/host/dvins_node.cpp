@@ -152,7 +152,7 @@ std::string stem(const std::string& path) {
 
 int main(int argc, char** argv) {
     try {
-        std::vector<std::string> pos; std::string seq_name, kitti_calib; int max_frames = 1 << 30, device = 0, marg_form = DV_MARG_INFO;
+        std::vector<std::string> pos; std::string seq_name, kitti_calib; int max_frames = 1 << 30, device = 0, marg_form = DV_MARG_INFO, undistort = -1 /* -1: as the file says */;
         if (argc >= 3 && std::string(argv[1]) == "--decode") {      // dvins_node --decode <image>...: size and a checksum of the decoded gray image (CPU; tests/test_node.py)
             for (int i = 2; i < argc; ++i) {
                 const Gray g = read_image(argv[i]);
@@ -168,6 +168,11 @@ int main(int argc, char** argv) {
             else if (a == "--kitti-calib" && i + 1 < argc) kitti_calib = argv[++i];
             else if (a == "--max-frames" && i + 1 < argc) max_frames = std::atoi(argv[++i]);
             else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
+            else if (a == "--undistort") {          // overrides the file's undistort_input (cfg::is_undistort_input, utils/camera_model.cpp:479-504)
+                const std::string v = i + 1 < argc ? argv[++i] : "";
+                if (v != "0" && v != "1") { std::fprintf(stderr, "dvins_node: --undistort takes 0 or 1, not '%s'\n", v.c_str()); return 2; }
+                undistort = v == "1";
+            }
             else if (a == "--marg-form") {          // the form of the marginalization prior (dv_set_marg_form): info = DV_MARG_INFO (default), eigen = the reference's DV_MARG_EIGEN
                 const std::string v = i + 1 < argc ? argv[++i] : "";
                 if (v == "info") marg_form = DV_MARG_INFO;
@@ -176,7 +181,7 @@ int main(int argc, char** argv) {
             }
             else pos.push_back(a);
         }
-        if (pos.size() < 2) { std::fprintf(stderr, "usage: dvins_node <config.yaml> <sequence dir> [output dir] [--seq NAME] [--kitti-calib DIR] [--max-frames N] [--device D] [--marg-form info|eigen]\n"); return 2; }
+        if (pos.size() < 2) { std::fprintf(stderr, "usage: dvins_node <config.yaml> <sequence dir> [output dir] [--seq NAME] [--kitti-calib DIR] [--max-frames N] [--device D] [--marg-form info|eigen] [--undistort 0|1]\n"); return 2; }
         const std::string cfg_path = pos[0], seq_dir = pos[1], out_dir = pos.size() > 2 ? pos[2] : ".";
         if (seq_name.empty()) seq_name = stem(seq_dir);
         Config cfg = ReadConfig(cfg_path, device, seq_name, kitti_calib);
@@ -187,6 +192,10 @@ int main(int argc, char** argv) {
         if (cfg.est.use_line) std::fprintf(stderr, "dvins_node: use_line needs the LSD / LBD detector's segments (upstream of this path): running without lines\n");
         const bool run_dynamic = cfg.dynamic && viode, run_naive = cfg.naive && viode;
         if (viode && cfg.viode_dynamic_keys.size() > 64) throw std::runtime_error("dvins_node: more than 64 dynamic keys (dv_viode_mask takes at most 64)");
+        // undistort_input (file or --undistort): the frames are remapped on the device; masks and key images cut from the DISTORTED segmentation images would no longer
+        // lie on them (the reference remaps the merged mask too, basic/semantic_image.cpp:84-92).  No shipped file combines the two: refused rather than tracked misaligned.
+        const bool undistort_on = undistort < 0 ? cfg.undistort_input != 0 : undistort != 0;
+        if (undistort_on && viode) throw std::runtime_error("dvins_node: undistort_input with VIODE segmentation masks is not supported (the masks and key images would have to be remapped with the frames)");
         cfg.est.dynamic = run_dynamic ? 1 : 0; cfg.est.use_line = 0;
         if (run_dynamic) cfg.est.use_det3d = 0;          // (no 3-D detector output in a VIODE directory; viode.yaml ships use_det3d: 0)
 
@@ -220,6 +229,13 @@ int main(int argc, char** argv) {
         if (!ctx) throw std::runtime_error(std::string("dvins_node: ") + dv_last_error(nullptr));
         if (dv_est_create(ctx, &cfg.est)) throw std::runtime_error(std::string("dvins_node: ") + dv_last_error(ctx));
         if (dv_set_marg_form(ctx, marg_form)) throw std::runtime_error(std::string("dvins_node: ") + dv_last_error(ctx));
+        // undistort_input: 1 (EuRoC, MYNT EYE): new camera matrices, undistortion maps built and installed on the device, the tracker's cameras switched to (newK, 0);
+        // the frames are handed over as they are and remapped on the way into pyramid level 0
+        if (undistort_on) {
+            dv_cam c0, c1;
+            if (dv_undistort_setup(ctx, 0.0, &c0, &c1)) throw std::runtime_error(std::string("dvins_node: ") + dv_last_error(ctx));
+            std::fprintf(stderr, "dvins_node: undistort_input: cam0 -> fx %.6f fy %.6f cx %.6f cy %.6f\n", c0.fx, c0.fy, c0.cx, c0.cy);
+        }
         // Everything the device reads per frame — frames, inverse masks, key images — lives in ONE pinned, device-mapped arena (dv_pinned_alloc) and is handed over as
         // DV_MEM_PINNED: the kernels read it in place over PCIe, no staging copy and no copy engine in the per-frame path.  If the arena cannot be had (a very long sequence),
         // the buffers stay pageable and travel as DV_MEM_HOST (hipMemcpy2DAsync per frame).

@@ -189,6 +189,15 @@ struct Config {
     // rgb_ids.txt line whose label id is one of dynamic_label_id; the first line of a key wins (unordered_map::insert).  Ascending.  Empty unless input_seg.
     std::vector<uint32_t> viode_dynamic_keys; std::string rgb_to_label_file;
     double baseline = 0, max_solver_time = 0;
+    // cfg::is_undistort_input (utils/camera_model.cpp:479-504): the intrinsics everything behind the remap works with — cam_s.K0 / K1 after InitOneCamera: (newK, 0) of
+    // cv::getOptimalNewCameraMatrix(alpha = 0) (dv_optimal_new_camera) when undistort_input is 1, front.cam0 / cam1 (the camera files') otherwise.  k: 0 left, 1 right.
+    dv_cam Camera(int k) const {
+        const dv_cam& src = k == 0 ? front.cam0 : front.cam1;
+        if (!undistort_input || (k == 1 && !front.stereo)) return src;
+        double nk[4];
+        if (dv_optimal_new_camera(&src, front.width, front.height, 0.0, nk)) throw std::runtime_error(std::string("dvins: undistort_input: ") + dv_last_error(nullptr));
+        return dv_cam{ nk[0], nk[1], nk[2], nk[3], 0, 0, 0, 0 };
+    }
     std::map<std::string, std::string> topics;  // image0_topic, image1_topic, image0_segmentation_topic, image1_segmentation_topic, imu_topic
 };
 inline Config ReadConfig(const std::string& config_path, int device = 0, const std::string& seq_name = "", const std::string& kitti_calib_dir = "") {
@@ -381,8 +390,23 @@ inline std::vector<dv_feat> to_rows(const FeatureBackground& fb) {
 class FeatureTracker {
 public:
     using Ptr = std::shared_ptr<FeatureTracker>;
-    explicit FeatureTracker(const std::string& config_path, int device = 0, const std::string& seq_name = "") { init(ReadConfig(config_path, device, seq_name).front); }
+    // undistort_input: 1 in the file: the whole of InitOneCamera's set-up (utils/camera_model.cpp:479-504) runs here — new camera matrices, maps built and installed on
+    // the device, lifting cameras switched (dv_undistort_setup) — and TrackImage* takes the DISTORTED frames; cam0() / cam1() report the new intrinsics (= Config::Camera(0 / 1))
+    explicit FeatureTracker(const std::string& config_path, int device = 0, const std::string& seq_name = "") {
+        const Config c = ReadConfig(config_path, device, seq_name);
+        init(c.front);
+        if (c.undistort_input) UndistortSetup();
+    }
     explicit FeatureTracker(const dv_config& c) { init(c); }
+    void UndistortSetup(double alpha = 0.0) {
+        detail::check(ctx_, dv_undistort_setup(ctx_, alpha, &cams_[0], &cams_[1]), "UndistortSetup");
+        // the merged instance mask goes through camera 0's maps too (SemanticImage::SetMask, basic/semantic_image.cpp:84-92): a host copy for dv_remap
+        mask_map1_.resize((size_t)cfg_.width * cfg_.height * 2); mask_map2_.resize((size_t)cfg_.width * cfg_.height);
+        detail::check(ctx_, dv_get_undistort_maps(ctx_, 0, mask_map1_.data(), mask_map2_.data(), DV_MEM_HOST), "UndistortSetup");
+        remap_mask_ = true;
+    }
+    const dv_cam& cam0() const { return cams_[0]; }      // the cameras the tracker lifts with: the config's, or (newK, 0) after UndistortSetup
+    const dv_cam& cam1() const { return cams_[1]; }
     ~FeatureTracker() { if (ctx_) dv_destroy(ctx_); }
     FeatureTracker(const FeatureTracker&) = delete;
     FeatureTracker& operator=(const FeatureTracker&) = delete;
@@ -401,7 +425,7 @@ public:
             if (segs.empty()) return;
             std::vector<float> px(4 * segs.size()); std::vector<double> un(4 * segs.size());
             for (size_t i = 0; i < segs.size(); ++i) { px[4 * i] = segs[i].x1; px[4 * i + 1] = segs[i].y1; px[4 * i + 2] = segs[i].x2; px[4 * i + 3] = segs[i].y2; }
-            detail::check(ctx_, dv_undistort_lines(ctx_, cam_id == 0 ? &cfg_.cam0 : &cfg_.cam1, px.data(), (int)segs.size(), un.data()), "TrackImageLine");
+            detail::check(ctx_, dv_undistort_lines(ctx_, &cams_[cam_id], px.data(), (int)segs.size(), un.data()), "TrackImageLine");
             for (size_t i = 0; i < segs.size(); ++i) {
                 const Line l{ segs[i].id, un[4 * i], un[4 * i + 1], un[4 * i + 2], un[4 * i + 3] };
                 if (cam_id == 0) fb.lines.insert({ l.id, { { 0, l } } });
@@ -418,7 +442,7 @@ public:
         remember(img);
         cur_time = img.time0;
         detail::check(ctx_, dv_track_stereo_enqueue(ctx_, img.gray0.data, img.gray1.data, img.gray0.width, img.gray0.height, img.gray0.stride, img.time0,
-                                                    img.inv_merge_mask.data, mode, mem_of(img.gray0)), "TrackImage");
+                                                    undistorted_mask(img), mode, mem_of(img.gray0)), "TrackImage");
     }
     FeatureBackground TrackImageCollect() {
         int n = 0;
@@ -456,9 +480,11 @@ public:
     // cfg::is_undistort_input (utils/camera_model.cpp:481-499): hand over cam_s.{left,right}_undist_map1 / _map2 (CV_16SC2 / CV_16UC1, image
     // size); from then on TrackImage* takes the DISTORTED frames — gray, or BGR with ImageView::bgr — and undistorts them on the way into
     // pyramid level 0 (ImageProcessor::Run's cv::remap + SetGrayImageGpu fused).  The config's camera files must then describe the new,
-    // distortion-free intrinsics, as the reference resets them.  map1 == nullptr removes the maps.
+    // distortion-free intrinsics, as the reference resets them.  map1 == nullptr removes the maps (and undoes UndistortSetup's camera switch).
+    // For callers who bring their own maps; a config with undistort_input: 1 needs none of this (the constructor builds them on the device).
     void SetUndistortMaps(int cam, const int16_t* map1_xy, const uint16_t* map2) {
         detail::check(ctx_, dv_set_undistort_maps(ctx_, cam, map1_xy, map2, cfg_.width, cfg_.height), "SetUndistortMaps");
+        if (!map1_xy) { cams_[1] = cfg_.cam1; if (cam == 0) { cams_[0] = cfg_.cam0; remap_mask_ = false; } }      // the library restores the cameras it was created with
     }
 #ifdef DVINS_SHIM_WITH_OPENCV
     void SetUndistortMaps(int cam, const cv::Mat& map1, const cv::Mat& map2) {
@@ -478,6 +504,7 @@ private:
         ctx_ = dv_create(&cfg_);
         if (!ctx_) throw std::runtime_error(std::string("dvins: FeatureTracker: ") + dv_last_error(nullptr));
         rows_.resize(DV_MAX_FEATS);
+        cams_[0] = cfg_.cam0; cams_[1] = cfg_.cam1;
     }
     static int mem_of(const ImageView& v) { return (v.device ? DV_MEM_DEVICE : DV_MEM_HOST) | (v.bgr ? DV_FMT_BGR : 0); }
     void check_image(const SemanticImage& img) const {
@@ -491,17 +518,32 @@ private:
         for (int y = 0; y < cur_img.height; ++y) std::memcpy(&cur_img.data[(size_t)y * cur_img.width], img.gray0.data + (size_t)y * img.gray0.stride, cur_img.width);
     }
     HostImage img_track_;
+    // After UndistortSetup the frames are undistorted on the device, so the mask must be too.  The reference remaps the MERGED mask (255 = object, border 0) with the left
+    // camera's maps and inverts the result (basic/semantic_image.cpp:84-92): inv' = ~remap(~inv).  The tracker reads the mask with the frames' stride (gray) or w (BGR).
+    const uint8_t* undistorted_mask(const SemanticImage& img) {
+        const ImageView& m = img.inv_merge_mask;
+        if (m.empty() || !remap_mask_) return m.data;
+        if (m.device || img.gray0.device) throw std::runtime_error("dvins: undistort_input: the instance mask of a device frame cannot be remapped by the shim (remap it with dv_remap and SetUndistortMaps' own maps)");
+        const int w = cfg_.width, h = cfg_.height, stride = img.gray0.bgr ? w : img.gray0.stride;
+        mask_in_.resize((size_t)w * h); mask_out_.resize((size_t)w * h); mask_pitched_.resize((size_t)stride * h);
+        for (int y = 0; y < h; ++y) for (int x = 0; x < w; ++x) mask_in_[(size_t)y * w + x] = (uint8_t)~m.data[(size_t)y * stride + x];
+        detail::check(ctx_, dv_remap(ctx_, mask_in_.data(), w, h, w, 1, mask_map1_.data(), mask_map2_.data(), mask_out_.data(), DV_MEM_HOST), "TrackImage (mask remap)");
+        for (int y = 0; y < h; ++y) for (int x = 0; x < w; ++x) mask_pitched_[(size_t)y * stride + x] = (uint8_t)~mask_out_[(size_t)y * w + x];
+        return mask_pitched_.data();
+    }
+    bool remap_mask_ = false; std::vector<int16_t> mask_map1_; std::vector<uint16_t> mask_map2_; std::vector<uint8_t> mask_in_, mask_out_, mask_pitched_;
     FeatureBackground track(SemanticImage& img, int mode) {
         check_image(img);
         remember(img);
         cur_time = img.time0;
         int n = 0;
         detail::check(ctx_, dv_track_stereo(ctx_, img.gray0.data, img.gray1.data, img.gray0.width, img.gray0.height, img.gray0.stride, img.time0,
-                                            img.inv_merge_mask.data, mode, mem_of(img.gray0), rows_.data(), &n), "TrackImage");
+                                            undistorted_mask(img), mode, mem_of(img.gray0), rows_.data(), &n), "TrackImage");
         n_rows_ = n;
         return detail::to_points(rows_.data(), n);
     }
     dv_config cfg_{};
+    dv_cam cams_[2]{};
     dv_ctx* ctx_ = nullptr;
     std::vector<dv_feat> rows_;
     int n_rows_ = 0;
@@ -581,7 +623,8 @@ public:
     using Ptr = std::shared_ptr<Estimator>;
     enum SolverFlag { kInitial = 0, kNonLinear = 1 };
     explicit Estimator(const std::string& config_path, int device = 0, const std::string& seq_name = "") {
-        cfg_ = ReadConfig(config_path, device, seq_name).est;
+        const Config c = ReadConfig(config_path, device, seq_name);
+        cfg_ = c.est; config_ = c;
         dv_config fc{};
         fc.width = 64; fc.height = 48; fc.max_cnt = 8; fc.min_dist = 8; fc.flow_back = 1; fc.stereo = 1; fc.device = device;
         fc.cam0 = dv_cam{1, 1, 0, 0, 0, 0, 0, 0}; fc.cam1 = fc.cam0;
@@ -590,6 +633,10 @@ public:
         SetParameter();
     }
     ~Estimator() { if (ctx_) dv_destroy(ctx_); }
+    // cam_s.K0 / K1 as the estimator side of the reference sees them (utils/camera_model.cpp:501-511): Config::Camera(0 / 1) — with undistort_input: 1 the same (newK, 0)
+    // the FeatureTracker built from this file reports
+    dv_cam cam0() const { return config_.Camera(0); }
+    dv_cam cam1() const { return config_.Camera(1); }
     Estimator(const Estimator&) = delete;
     Estimator& operator=(const Estimator&) = delete;
 
@@ -767,7 +814,7 @@ private:
         }
     }
     std::mutex out_pose_mutex_; EgoInfo ego_{};
-    dv_est_config cfg_;
+    dv_est_config cfg_; Config config_;
     dv_est_state state_{};
     dv_ctx* ctx_ = nullptr;
     bool created_ = false;

@@ -31,11 +31,16 @@ class SyntheticSequence:
 
 
 class Pipeline:
-    def __init__(self, seq: SyntheticSequence, max_cnt=250, min_dist=25, max_iters=10, device=0, use_imu=1, host_frames=False, ba_stride=1, est_kw=None):
+    def __init__(self, seq: SyntheticSequence, max_cnt=250, min_dist=25, max_iters=10, device=0, use_imu=1, host_frames=False, ba_stride=1, est_kw=None, undistort_input=False,
+                 undistort_alpha=0.0):
         self.seq = seq
         self.host = [seq.host_frame(k) for k in range(len(seq.frames))] if host_frames else None
         c = make_cam(*sim.cam_tuple(seq.cam))
         self.ctx = Context(width=seq.w, height=seq.h, max_cnt=max_cnt, min_dist=min_dist, cam0=c, cam1=make_cam(*sim.cam_tuple(seq.cam1)), device=device)
+        # undistort_input (cfg::is_undistort_input, utils/camera_model.cpp:479-504): the sequence's frames are the DISTORTED ones; the tracker remaps them on the way into
+        # pyramid level 0 and every camera behind it — the estimator's included — is (newK, 0)
+        self.undistort_input = bool(undistort_input)
+        self.cam0, self.cam1 = self.ctx.undistort_setup(undistort_alpha) if self.undistort_input else self.ctx.cameras()
         self.est_kw = dict(use_imu=use_imu, stereo=1, max_iters=max_iters, ric=seq.rig["est_ric"], tic=seq.rig["est_tic"], **seq.noise)
         self.est_kw.update(est_kw or {})          # keyframe_parallax, g_norm, ... of a shipped YAML (ref_configs.py)
         self.est = Estimator(self.ctx, **self.est_kw)

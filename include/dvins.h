@@ -160,6 +160,32 @@ int dv_remap(dv_ctx* ctx, const uint8_t* src, int w, int h, int stride, int chan
  * dv_config.cam0 / cam1 should then be the NEW intrinsics without distortion, as the reference resets them (camera_model.cpp:486-503).
  * A mask passed to the tracker is used as given (the reference remaps it before inverting it: use dv_remap with channels = 1). */
 int dv_set_undistort_maps(dv_ctx* ctx, int cam, const int16_t* map1_xy, const uint16_t* map2, int w, int h);
+/* cv::getOptimalNewCameraMatrix(K, D, Size(w, h), alpha, Size(w, h)) without principal-point centring (utils/camera_model.cpp:483,493), for the pinhole + radtan
+ * camera of dv_cam (k3 = 0): newK4 = fx, fy, cx, cy.  Host code, no ctx.  Restated from OpenCV 3.4 calib3d (un-vendored: from memory, like SURVEY App. A):
+ * cvGetOptimalNewCameraMatrix -> icvGetRectangles (a 9 x 9 grid over the image, pixel (x w / 8, y h / 8)) -> cvUndistortPoints with R = P = I (5 fixed-point
+ * iterations from the normalised point) -> inner rectangle (largest of the left / top edge points, smallest of the right / bottom ones) and outer rectangle (bounding
+ * box of all 81), each mapped onto [0, w - 1] x [0, h - 1]; the two projections are blended by alpha (0: no black border, 1: every source pixel kept).  All in double
+ * (the library keeps the grid as float points: declared choice U1).  <0: bad argument or a degenerate rectangle. */
+int dv_optimal_new_camera(const dv_cam* cam, int w, int h, double alpha, double newK4[4]);
+/* cv::initUndistortRectifyMap(K, D, Mat(), newK, Size(w, h), CV_16SC2, map1, map2) (utils/camera_model.cpp:484,494; OpenCV 3.4 imgproc undistort.cpp) on the device:
+ * the map pair dv_remap / dv_set_undistort_maps read, map1_xy = w*h (x, y) int16 pairs, map2 = w*h uint16 (fy << 5 | fx).  The library walks a row by _x += 1 / fx',
+ * one rounded addition per pixel: the column values are produced by that same chain once (they are the same in every row for R = I) and the distortion polynomial of
+ * all pixels is evaluated in parallel (undistort_map.hip).  The maps follow `mem` (DV_MEM_HOST / DV_MEM_DEVICE); w, h <= 32767. */
+int dv_init_undistort_map(dv_ctx* ctx, const dv_cam* cam, const double newK4[4], int w, int h, int16_t* map1_xy, uint16_t* map2, int mem);
+/* The whole of cfg::is_undistort_input in InitOneCamera (utils/camera_model.cpp:479-504) for the cameras the ctx was created with: newK of camera 0 (and of camera 1 on
+ * a stereo ctx) by dv_optimal_new_camera(alpha) (the reference: alpha = 0), both map pairs built in HBM and installed as dv_set_undistort_maps would install them (no
+ * host round trip), and the ctx's cameras switched to (newK, 0, 0, 0, 0): the rows of dv_track_stereo* and the object tracker then lift with the undistorted intrinsics,
+ * as the reference's re-parameterised cam0 / cam1 do (:501-511); give them (dv_get_cameras) to dv_lift_projective* / dv_undistort_lines.  new_cam0 / new_cam1 (may be NULL) receive
+ * them (new_cam1 = the unchanged camera 1 on a mono ctx).  Refused, with nothing changed, while a frame is pending.  A second call starts from the original cameras
+ * again; if it fails after that refusal point (allocation, launch), no maps are installed and the original cameras hold.  dv_set_undistort_maps(ctx, 0, NULL, ...)
+ * removes the maps AND restores the original cameras ((ctx, 1, NULL, ...): camera 1's).  Installing the caller's OWN maps for a camera afterwards also restores that camera's
+ * original intrinsics: (newK, 0) belongs to the maps built here. */
+int dv_undistort_setup(dv_ctx* ctx, double alpha, dv_cam* new_cam0, dv_cam* new_cam1);
+/* copies the installed maps of camera `cam` out of HBM (w*h*2 int16, w*h uint16; host or device memory by `mem`), e.g. to dv_remap the merged mask with them as the
+ * reference does (basic/semantic_image.cpp:86-89); <0 if none are installed */
+int dv_get_undistort_maps(dv_ctx* ctx, int cam, int16_t* map1_xy, uint16_t* map2, int mem);
+/* the cameras the ctx lifts with at the moment (dv_config's, or those of dv_undistort_setup); either pointer may be NULL */
+int dv_get_cameras(dv_ctx* ctx, dv_cam* cam0, dv_cam* cam1);
 /* cv::circle(mask, pt, radius, 0, -1) per point (background_tracker.cpp:79-80) */
 int dv_circle_mask(dv_ctx* ctx, uint8_t* mask, int w, int h, int stride, const float* pts_xy, int n,
                    int radius, int mem);
