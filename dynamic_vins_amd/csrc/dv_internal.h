@@ -86,6 +86,13 @@ void dv_launch_lk_generic(const DvPyr& A, const DvPyr& B, const float2* pts_a, i
 struct DvPyrJob { const uint8_t* src0; const uint8_t* src1; uint8_t* dst0; uint8_t* dst1; int sw, sh, spitch, dw, dh, dpitch; uint8_t* cpy0; uint8_t* cpy1; int cpitch, pad_; };      // cpy (optional): the source tile's own pixels also go to a pitched copy (level 0 of the pyramid: frame read once)
 void dv_launch_pyr_down_multi(const DvPyrJob* jobs_dev, int n_jobs, int max_dw, int max_dh, hipStream_t s);
 void dv_launch_pyr_apron_multi(const DvPyr* pyrs_dev, int n_pyr, int max_levels, hipStream_t s);
+// pyramid level 0 of one member of a dv_batch round for dv_launch_level0_multi: remap through the member's own maps (gray or BGR -> gray) or BGR -> gray alone.
+// map0 / map1: the member's map block per camera (w * h short2 of map1, then w * h uint16 of map2), unused by DV_L0_BGR; src1 / dst1 null: single image.  w, h: the group's common geometry
+#define DV_L0_REMAP_GRAY 0
+#define DV_L0_REMAP_BGR  1
+#define DV_L0_BGR        2
+struct DvLevel0Job { const uint8_t* src0; const uint8_t* src1; const uint8_t* map0; const uint8_t* map1; uint8_t* dst0; uint8_t* dst1; int spitch, dpitch, kind, pad_; };
+void dv_launch_level0_multi(const DvLevel0Job* jobs_dev, int n_jobs, int w, int h, hipStream_t s);
 // job-table forms of the tracker's single-workgroup / per-image stages (the front ends of a dv_batch group in shared launches: front_batch.hip)
 struct DvCompactJob { DvTrackState tr; const uint8_t* in_mask; int mask_pitch, sort_by_cnt; int* n_cand; unsigned* max_ord; };
 void dv_launch_compact_multi(const DvCompactJob* jobs_dev, int n_jobs, hipStream_t s);

@@ -454,6 +454,8 @@ int dv_track_stereo(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gray1, int
 // sequence, system/main.cpp:178-330): pyrDown levels 1..3 (level 1 also writes the pitched level-0 copy), aprons, temporal LK, compaction / sort, Shi-Tomasi tile,
 // corner selection, stereo LK, rows = 10 launches per group and frame instead of 10 per sequence.  The kernels are the single-sequence kernels' bodies behind a
 // job table in HBM (blockIdx.z / .y / .x = member), so every member's rows are bit-identical to what its own dv_track_stereo_enqueue produces.
+// Members with undistortion maps (cfg::is_undistort_input) or BGR frames differ in level 0 alone: one more launch (level0_multi_kernel, pyramid.hip) fills it for all
+// of them, each through its own maps, and level 1 then reads it; a round without such a member does not launch it.
 struct DvFrontBatch {
     hipStream_t stream = nullptr; hipEvent_t done = nullptr, ev_copy[2] = { nullptr, nullptr };
     DevBuf tab[2]; void* tab_pinned[2] = { nullptr, nullptr }; size_t tab_bytes = 0; int parity = 0; bool copy_used[2] = { false, false };
@@ -482,7 +484,8 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
         for (int k = 0; k < 2; ++k) DV_CHECK(hipEventCreateWithFlags(&Fp->ev_copy[k], hipEventDisableTiming));
     }
     DvFrontBatch& F = *Fp;
-    // ---- which jobs can share launches: raw mode, gray frames, no mask, no undistortion maps, no object tracker, the group's common geometry ----
+    // ---- which jobs can share launches: raw mode, no mask, no object tracker, the group's common geometry (gray or BGR frames, with or without the member's own
+    //      undistortion maps: those differ in how level 0 is filled and in nothing behind it) ----
     std::vector<int> M;                                         // job indices that are batched
     const dv_config* ref = nullptr;
     for (int i = 0; i < n; ++i) {
@@ -490,7 +493,7 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
         if (j.member < 0 || j.member >= (int)mem.size()) DV_FAIL("dv_batch_track_enqueue: member index out of range");
         dv_ctx* c = mem[j.member];
         for (int q = 0; q < i; ++q) if (jobs[q].member == j.member) DV_FAIL("dv_batch_track_enqueue: a member appears twice");
-        const bool plain = j.mode == DV_MODE_RAW && !j.mask && !(j.mem & DV_FMT_BGR) && !c->undist[0] && !c->inst && !c->timing && j.gray0 && (!c->cfg.stereo || j.gray1);
+        const bool plain = j.mode == DV_MODE_RAW && !j.mask && !c->inst && !c->timing && j.gray0 && (!c->cfg.stereo || j.gray1);
         const bool same = !ref || (c->cfg.width == ref->width && c->cfg.height == ref->height && c->cfg.stereo == ref->stereo && c->cfg.flow_back == ref->flow_back);
         if (plain && same) { if (!ref) ref = &c->cfg; M.push_back(i); }
         else {      // its own launches on its own stream (ordered behind whatever the batch stream still holds for it: dv_track_stereo_enqueue)
@@ -502,7 +505,7 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
     if (S == 0) return 0;
     if (S == 1) {      // nothing to share
         const dv_track_job& j = jobs[M[0]]; dv_ctx* c = mem[j.member];
-        if (dv_track_stereo_enqueue(c, j.gray0, j.gray1, c->cfg.width, c->cfg.height, j.stride > 0 ? j.stride : c->cfg.width, j.t, nullptr, DV_MODE_RAW, j.mem)) { dv_set_error(ctx, c->err); return -1; }
+        if (dv_track_stereo_enqueue(c, j.gray0, j.gray1, c->cfg.width, c->cfg.height, j.stride > 0 ? j.stride : c->cfg.width * ((j.mem & DV_FMT_BGR) ? 3 : 1), j.t, nullptr, DV_MODE_RAW, j.mem)) { dv_set_error(ctx, c->err); return -1; }
         F.members_single++;
         return 0;
     }
@@ -516,6 +519,14 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
     for (int i : M) {
         const dv_track_job& j = jobs[i]; dv_ctx* c = mem[j.member];
         if (c->pending) { dv_set_error(ctx, "dv_batch_track_enqueue: a member's previous frame was not collected"); return -1; }
+        if ((j.mem & 0xff) != DV_MEM_HOST && (j.mem & 0xff) != DV_MEM_DEVICE && (j.mem & 0xff) != DV_MEM_PINNED) {      // dv_track_stereo_enqueue's check, with its text
+            dv_set_error(c, "dv_track_stereo: unknown memory kind"); dv_set_error(ctx, c->err); return -1;
+        }
+        if (c->undist[0]) {      // build_pyramids' checks of the undistort path, with its texts
+            const char* bad = (w != c->undist_w || h != c->undist_h) ? "dv_track_stereo: undistortion maps were installed for another image size"
+                            : (stereo && !c->undist[1]) ? "dv_track_stereo: undistortion maps installed for camera 0 but not for camera 1" : nullptr;
+            if (bad) { dv_set_error(c, bad); dv_set_error(ctx, bad); return -1; }
+        }
         if (ensure_hw(c, c->cfg.min_dist) || ensure_cand(c, w, h)) { dv_set_error(ctx, c->err); return -1; }
         if (c->last_front && c->last_front != s && c->last_done) DV_CHECK(hipStreamWaitEvent(s, c->last_done, 0));      // its previous frame ran on its own stream
         c->cur ^= 1; cur_guard.flipped.push_back(c);
@@ -527,7 +538,7 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
     const size_t o_pyr = 0, o_apr = o_pyr + (size_t)3 * S * sizeof(DvPyrJob), o_lk = (o_apr + (size_t)2 * S * sizeof(DvPyr) + 255) / 256 * 256,
                  o_cmp = (o_lk + (size_t)2 * S * sizeof(DvLkJob) + 255) / 256 * 256, o_gt = (o_cmp + (size_t)S * sizeof(DvCompactJob) + 255) / 256 * 256,
                  o_gs = (o_gt + (size_t)S * sizeof(GfttTileArgs) + 255) / 256 * 256, o_fin = (o_gs + (size_t)S * sizeof(GfttSelectArgs) + 255) / 256 * 256,
-                 total = (o_fin + (size_t)S * sizeof(DvFinalizeJob) + 255) / 256 * 256;
+                 o_l0 = (o_fin + (size_t)S * sizeof(DvFinalizeJob) + 255) / 256 * 256, total = (o_l0 + (size_t)S * sizeof(DvLevel0Job) + 255) / 256 * 256;
     const int par = F.parity; F.parity ^= 1;
     if (F.copy_used[par]) DV_CHECK(hipEventSynchronize(F.ev_copy[par]));      // the upload that last read this pinned block (two rounds ago) has run
     if (F.tab_bytes < total) {
@@ -544,21 +555,37 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
     uint8_t* hp = (uint8_t*)F.tab_pinned[par]; const uint8_t* dp = (const uint8_t*)F.tab[par].p;
     DvPyrJob* h_pyr = (DvPyrJob*)(hp + o_pyr); DvPyr* h_apr = (DvPyr*)(hp + o_apr); DvLkJob* h_lk = (DvLkJob*)(hp + o_lk); DvCompactJob* h_cmp = (DvCompactJob*)(hp + o_cmp);
     GfttTileArgs* h_gt = (GfttTileArgs*)(hp + o_gt); GfttSelectArgs* h_gs = (GfttSelectArgs*)(hp + o_gs); DvFinalizeJob* h_fin = (DvFinalizeJob*)(hp + o_fin);
+    DvLevel0Job* h_l0 = (DvLevel0Job*)(hp + o_l0); int n_l0 = 0;      // only the members whose level 0 is not a copy of the frame: none in an all-plain round, and no launch then
     int levels = 0, lw[DV_MAX_LEVELS] = { 0 }, lh[DV_MAX_LEVELS] = { 0 };
     for (int k = 0; k < S; ++k) {
         const dv_track_job& j = jobs[M[k]]; dv_ctx* c = mem[j.member];
         const dv_config& cf = c->cfg;
         PyrSet& L = c->left[c->cur]; PyrSet& Lp = c->left[c->cur ^ 1];
         const DvPyr& a = L.pyr; const DvPyr* b = stereo ? &c->right.pyr : nullptr;
-        const int stride = j.stride > 0 ? j.stride : w;
-        const bool dev = j.mem == DV_MEM_DEVICE || j.mem == DV_MEM_PINNED;      // (pinned + mapped host memory: read in place by the level-1 kernel, like HBM)
-        if (!dev || a.levels == 1) {      // host frames: the upload IS the level-0 copy
+        const bool bgr = (j.mem & DV_FMT_BGR) != 0, und = c->undist[0], l0 = bgr || und;
+        const int mk = j.mem & 0xff, cn = bgr ? 3 : 1;
+        const int stride = j.stride > 0 ? j.stride : cn * w;
+        const bool dev = mk == DV_MEM_DEVICE || mk == DV_MEM_PINNED;      // (pinned + mapped host memory: read in place by the level-0 / level-1 kernel, like HBM)
+        if (l0) {      // remap and / or BGR -> gray straight into level 0 (build_pyramids); host frames are staged in the member's own buffers first, on this stream
+            DvLevel0Job z{};
+            z.src0 = j.gray0; z.src1 = b ? j.gray1 : nullptr; z.spitch = stride;
+            if (!dev) {
+                const int cp = align_up(cn * w, 16);
+                DV_CHECK(c->s3.ensure((size_t)cp * h)); DV_CHECK(hipMemcpy2DAsync(c->s3.p, cp, j.gray0, stride, (size_t)cn * w, h, hipMemcpyHostToDevice, s));
+                z.src0 = (const uint8_t*)c->s3.p; z.spitch = cp;
+                if (b) { DV_CHECK(c->s4.ensure((size_t)cp * h)); DV_CHECK(hipMemcpy2DAsync(c->s4.p, cp, j.gray1, stride, (size_t)cn * w, h, hipMemcpyHostToDevice, s)); z.src1 = (const uint8_t*)c->s4.p; }
+            }
+            z.map0 = und ? (const uint8_t*)c->undist_buf[0].p : nullptr; z.map1 = (und && b) ? (const uint8_t*)c->undist_buf[1].p : nullptr;
+            z.dst0 = a.L[0].p; z.dst1 = b ? b->L[0].p : nullptr; z.dpitch = a.L[0].pitch;
+            z.kind = und ? (bgr ? DV_L0_REMAP_BGR : DV_L0_REMAP_GRAY) : DV_L0_BGR;
+            h_l0[n_l0++] = z;
+        } else if (!dev || a.levels == 1) {      // host frames: the upload IS the level-0 copy
             DV_CHECK(hipMemcpy2DAsync(a.L[0].p, a.L[0].pitch, j.gray0, stride, w, h, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
             if (b) DV_CHECK(hipMemcpy2DAsync(b->L[0].p, b->L[0].pitch, j.gray1, stride, w, h, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
         }
         levels = a.levels;
         for (int l = 1; l < a.levels; ++l) {
-            const bool fuse = dev && l == 1;
+            const bool fuse = dev && l == 1 && !l0;      // (a member with a level-0 job: level 1 reads L[0], as in build_pyramids)
             DvPyrJob pj{};
             pj.src0 = fuse ? j.gray0 : a.L[l - 1].p; pj.src1 = b ? (fuse ? j.gray1 : b->L[l - 1].p) : nullptr;
             pj.dst0 = a.L[l].p; pj.dst1 = b ? b->L[l].p : nullptr;
@@ -594,6 +621,7 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
     DV_CHECK(dv_copy_async(F.tab[par].p, hp, total, s));
     DV_CHECK(hipEventRecord(F.ev_copy[par], s)); F.copy_used[par] = true;
     // ---- the stages ----
+    if (n_l0) dv_launch_level0_multi((const DvLevel0Job*)(dp + o_l0), n_l0, w, h, s);
     for (int l = 1; l < levels; ++l) dv_launch_pyr_down_multi((const DvPyrJob*)(dp + o_pyr) + (size_t)(l - 1) * S, S, lw[l], lh[l], s);
     dv_launch_pyr_apron_multi((const DvPyr*)(dp + o_apr), 2 * S, levels, s);
     dv_launch_lk_track_multi((const DvLkJob*)(dp + o_lk), S, n_max, ref->flow_back, 0.5f, s);

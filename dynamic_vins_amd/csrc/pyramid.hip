@@ -188,12 +188,8 @@ void dv_launch_pyr_down2(const uint8_t* src0, const uint8_t* src1, int sw, int s
 // fixed-point weights (B 1868, G 9617, R 4899, +8192 >> 14).  Written straight into level 0 of the pyramid, so a
 // colour frame is read once (3P) and never exists as a separate gray image.
 // One thread = 4 pixels: three coalesced dword loads, one dword store.  blockIdx.z selects the image of a stereo pair.
-__global__ __launch_bounds__(256) void bgr2gray_kernel(const uint8_t* __restrict__ src0, const uint8_t* __restrict__ src1, int w, int h, int spitch,
-                                                       uint8_t* __restrict__ dst0, uint8_t* __restrict__ dst1, int dpitch) {
-    const uint8_t* src = blockIdx.z ? src1 : src0;
-    uint8_t* dst = blockIdx.z ? dst1 : dst0;
-    const int y = blockIdx.y, x4 = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (x4 >= w) return;
+// bgr2gray_quad: pixels x4 .. x4 + 3 of row y — the one definition of the arithmetic, shared by bgr2gray_kernel and level0_multi_kernel
+__device__ __forceinline__ void bgr2gray_quad(const uint8_t* __restrict__ src, int w, int spitch, uint8_t* __restrict__ dst, int dpitch, int y, int x4) {
     const uint8_t* row = src + (size_t)y * spitch + (size_t)x4 * 3;
     uint8_t px[12];
     if (x4 + 4 <= w && ((reinterpret_cast<uintptr_t>(row) & 3) == 0)) {
@@ -210,6 +206,12 @@ __global__ __launch_bounds__(256) void bgr2gray_kernel(const uint8_t* __restrict
     uint8_t* o = dst + (size_t)y * dpitch + x4;
     if (x4 + 4 <= w) *reinterpret_cast<uint32_t*>(o) = (uint32_t)g[0] | ((uint32_t)g[1] << 8) | ((uint32_t)g[2] << 16) | ((uint32_t)g[3] << 24);
     else for (int k = 0; k < 4 && x4 + k < w; ++k) o[k] = g[k];
+}
+__global__ __launch_bounds__(256) void bgr2gray_kernel(const uint8_t* __restrict__ src0, const uint8_t* __restrict__ src1, int w, int h, int spitch,
+                                                       uint8_t* __restrict__ dst0, uint8_t* __restrict__ dst1, int dpitch) {
+    const int y = blockIdx.y, x4 = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (x4 >= w) return;
+    bgr2gray_quad(blockIdx.z ? src1 : src0, w, spitch, blockIdx.z ? dst1 : dst0, dpitch, y, x4);
 }
 
 void dv_launch_bgr2gray(const uint8_t* src0, const uint8_t* src1, int w, int h, int spitch, uint8_t* dst0, uint8_t* dst1, int dpitch, hipStream_t s) {
@@ -230,16 +232,10 @@ void dv_launch_bgr2gray(const uint8_t* src0, const uint8_t* src1, int w, int h, 
 // written per pixel instead of remap (6 + 3 + 3) + cvtColor (3 + 1).
 // One thread = 4 destination pixels of a row; blockIdx.z selects the image (and its maps) of a stereo pair.
 typedef uint64_t __attribute__((aligned(1))) u64_unaligned;
+// remap_quad: destination pixels x4 .. x4 + 3 of row y — the one definition of the arithmetic, shared by remap_kernel and level0_multi_kernel
 template <int CN, bool TO_GRAY>
-__global__ __launch_bounds__(256) void remap_kernel(const uint8_t* __restrict__ src0, const uint8_t* __restrict__ src1, int w, int h, int spitch,
-                                                    const short2* __restrict__ m1_0, const uint16_t* __restrict__ m2_0,
-                                                    const short2* __restrict__ m1_1, const uint16_t* __restrict__ m2_1,
-                                                    uint8_t* __restrict__ dst0, uint8_t* __restrict__ dst1, int dpitch) {
-    const uint8_t* src = blockIdx.z ? src1 : src0;
-    const short2* m1 = blockIdx.z ? m1_1 : m1_0; const uint16_t* m2 = blockIdx.z ? m2_1 : m2_0;
-    uint8_t* dst = blockIdx.z ? dst1 : dst0;
-    const int y = blockIdx.y, x4 = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (x4 >= w) return;
+__device__ __forceinline__ void remap_quad(const uint8_t* __restrict__ src, int w, int h, int spitch, const short2* __restrict__ m1, const uint16_t* __restrict__ m2,
+                                           uint8_t* __restrict__ dst, int dpitch, int y, int x4) {
     constexpr int OC = TO_GRAY ? 1 : CN;
     uint8_t o[4 * OC];
 #pragma unroll
@@ -284,6 +280,15 @@ __global__ __launch_bounds__(256) void remap_kernel(const uint8_t* __restrict__ 
     if (OC == 1 && x4 + 4 <= w) *reinterpret_cast<uint32_t*>(out) = (uint32_t)o[0] | ((uint32_t)o[1] << 8) | ((uint32_t)o[2] << 16) | ((uint32_t)o[3] << 24);
     else for (int k = 0; k < 4 * OC && x4 * OC + k < w * OC; ++k) out[k] = o[k];
 }
+template <int CN, bool TO_GRAY>
+__global__ __launch_bounds__(256) void remap_kernel(const uint8_t* __restrict__ src0, const uint8_t* __restrict__ src1, int w, int h, int spitch,
+                                                    const short2* __restrict__ m1_0, const uint16_t* __restrict__ m2_0,
+                                                    const short2* __restrict__ m1_1, const uint16_t* __restrict__ m2_1,
+                                                    uint8_t* __restrict__ dst0, uint8_t* __restrict__ dst1, int dpitch) {
+    const int y = blockIdx.y, x4 = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (x4 >= w) return;
+    remap_quad<CN, TO_GRAY>(blockIdx.z ? src1 : src0, w, h, spitch, blockIdx.z ? m1_1 : m1_0, blockIdx.z ? m2_1 : m2_0, blockIdx.z ? dst1 : dst0, dpitch, y, x4);
+}
 
 // cn: channels of src; to_gray (cn == 3 only): write the gray image.  dpitch in bytes, 4-byte aligned rows when the output has one channel.
 void dv_launch_remap(const uint8_t* src0, const uint8_t* src1, int w, int h, int spitch, int cn, int to_gray, const int16_t* m1_0, const uint16_t* m2_0,
@@ -293,4 +298,29 @@ void dv_launch_remap(const uint8_t* src0, const uint8_t* src1, int w, int h, int
     if (cn == 1) hipLaunchKernelGGL((remap_kernel<1, false>), grid, dim3(256), 0, s, src0, src1, w, h, spitch, a, m2_0, b, m2_1, dst0, dst1, dpitch);
     else if (to_gray) hipLaunchKernelGGL((remap_kernel<3, true>), grid, dim3(256), 0, s, src0, src1, w, h, spitch, a, m2_0, b, m2_1, dst0, dst1, dpitch);
     else hipLaunchKernelGGL((remap_kernel<3, false>), grid, dim3(256), 0, s, src0, src1, w, h, spitch, a, m2_0, b, m2_1, dst0, dst1, dpitch);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Pyramid level 0 of every member of a dv_batch round whose frames do not arrive as plain gray images (dv_batch_track_enqueue): cv::remap through the member's own
+// maps, cv::remap + cvtColor of a colour frame, or cvtColor alone — the per-pixel bodies of the single-member kernels above behind a job table in HBM, both images of
+// a stereo pair, in ONE launch.  Grid (x-block, row, plane z = 2 * job + image) like the single-member kernels: the map reads stream (6 B per pixel, read once), the
+// source reads are gathered around the destination row, so nothing is shared between workgroups that a tile order could keep in one L2.
+__global__ __launch_bounds__(256) void level0_multi_kernel(const DvLevel0Job* __restrict__ jobs, int w, int h) {
+    const DvLevel0Job j = jobs[blockIdx.z >> 1];
+    const int img = blockIdx.z & 1;
+    const uint8_t* src = img ? j.src1 : j.src0;
+    if (!src) return;                                         // (mono member: no second image)
+    const int y = blockIdx.y, x4 = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (x4 >= w) return;
+    uint8_t* dst = img ? j.dst1 : j.dst0;
+    const uint8_t* mb = img ? j.map1 : j.map0;                // map1 (w * h short2) | map2 (w * h uint16)
+    const short2* m1 = reinterpret_cast<const short2*>(mb);
+    const uint16_t* m2 = reinterpret_cast<const uint16_t*>(mb + (size_t)4 * w * h);
+    if (j.kind == DV_L0_REMAP_GRAY) remap_quad<1, false>(src, w, h, j.spitch, m1, m2, dst, j.dpitch, y, x4);
+    else if (j.kind == DV_L0_REMAP_BGR) remap_quad<3, true>(src, w, h, j.spitch, m1, m2, dst, j.dpitch, y, x4);
+    else bgr2gray_quad(src, w, j.spitch, dst, j.dpitch, y, x4);
+}
+void dv_launch_level0_multi(const DvLevel0Job* jobs_dev, int n_jobs, int w, int h, hipStream_t s) {
+    if (n_jobs <= 0) return;
+    hipLaunchKernelGGL(level0_multi_kernel, dim3((w + 1023) / 1024, h, 2 * n_jobs), dim3(256), 0, s, jobs_dev, w, h);
 }

@@ -308,10 +308,17 @@ int dv_batch_info(dv_batch* batch, long long* batched_rounds, long long* single_
 /* The FRONT ENDS of the members in shared launches: dv_track_stereo_enqueue for several members at once — FeatureTracker::TrackImage (front_end/background_tracker.cpp:52-158)
  * of S sequences as one launch per stage (pyramid levels, aprons, temporal LK, compaction, Shi-Tomasi tile, corner selection, stereo LK, rows: 10 launches per group and
  * frame instead of 10 per sequence; the reference runs one process per sequence, system/main.cpp:178-330).  member = index into the array dv_batch_create was given.
- * Jobs that cannot share launches (a mode other than DV_MODE_RAW, a mask, BGR frames, installed undistortion maps, an object tracker on the ctx, another image size
- * than the first job's) run through their member's own dv_track_stereo_enqueue inside this call.  Every member is collected with dv_track_stereo_collect as usual;
- * its rows are bit-identical to the unbatched path's. */
-typedef struct dv_track_job { int32_t member, mem /* DV_MEM_* [| DV_FMT_BGR] */; const uint8_t* gray0; const uint8_t* gray1; int32_t stride /* bytes, 0 = width */, mode; double t; const uint8_t* mask; } dv_track_job;
+ * BGR frames (mem = DV_MEM_* | DV_FMT_BGR) and members with installed undistortion maps (dv_undistort_setup / dv_set_undistort_maps; the maps are per member, so
+ * the members' cameras may differ) share the launches too: one more launch fills pyramid level 0 of all such members of the round (remap, remap + BGR -> gray, or
+ * BGR -> gray), their DV_MEM_HOST frames are staged on the group's stream first, DV_MEM_DEVICE / DV_MEM_PINNED frames are read in place.  A round of gray members
+ * without maps enqueues exactly the ten launches above.
+ * Jobs that cannot share launches (a mode other than DV_MODE_RAW, a mask, an object tracker on the ctx, dv_timing_enable on the ctx, another image size than the
+ * first job's) run through their member's own dv_track_stereo_enqueue inside this call.  Every member is collected with dv_track_stereo_collect as usual;
+ * its rows are bit-identical to the unbatched path's.  A member whose maps do not fit (another size, camera 1 missing on a stereo member) fails the call with
+ * dv_track_stereo's message; no member of the shared part has a frame pending then.
+ * Between this call and a member's dv_track_stereo_collect, call no image operator (dv_remap, dv_bgr2gray, dv_pyr_down_cuda, ...) on that member: its staging buffers
+ * are in use on the group's stream, which the operators' own stream is not ordered against. */
+typedef struct dv_track_job { int32_t member, mem /* DV_MEM_* [| DV_FMT_BGR] */; const uint8_t* gray0; const uint8_t* gray1; int32_t stride /* bytes, 0 = width (3 * width for DV_FMT_BGR) */, mode; double t; const uint8_t* mask; } dv_track_job;
 int dv_batch_track_enqueue(dv_batch* batch, const dv_track_job* jobs, int n);
 int dv_batch_track_info(dv_batch* batch, long long* rounds, long long* members_batched, long long* members_single);
 /* measurement: HIP events on the batch stream around the solve / evaluation / reduce launches of one steady-state iteration slot per round; out3 = average ms per launch so far */
@@ -534,7 +541,7 @@ int dv_est_get_marg_health(dv_ctx* ctx, long long* checked, long long* clamped, 
  * The contexts (each with its estimator: dv_est_create) stay the caller's; frames are referenced, not copied (device or host memory: dv_seq_input::mem).
  * dynamic_vins_amd/host/dvins_node.cpp is the ROS-free node built on it (image directory + IMU csv in, `<seq>_<mode>_Odometry.txt` out). */
 typedef struct dv_seq_input {
-    const uint8_t* const* left; const uint8_t* const* right;      /* [n_frames] gray images of the configured size */
+    const uint8_t* const* left; const uint8_t* const* right;      /* [n_frames] gray images of the configured size (DV_FMT_BGR is not taken here: the default row stride is the width).  Contexts with installed undistortion maps take the distorted frames, in a group's shared launches too */
     const double* times; int32_t n_frames, mem /* DV_MEM_HOST / DV_MEM_DEVICE */, stride /* bytes per row, 0 = width */, ba_stride /* 2: only every 2nd tracked frame goes to the back end (system/main.cpp:300-307); 0 / 1: every frame */;
     const double* imu_t; const double* imu_acc; const double* imu_gyr; int32_t n_imu, reserved2;      /* [n_imu], [n_imu][3], [n_imu][3]; n_imu 0 for vision-only */
 } dv_seq_input;
