@@ -716,7 +716,7 @@ struct dv_batch {
     hipStream_t solve_stream = nullptr; std::vector<hipEvent_t> ev_x;      // DVINS_SOLVE_CUS: the solve launches of a round on a stream of their own (reserved CUs), chained to `stream` by events
     DevBuf tab; void* tab_pinned = nullptr; size_t tab_bytes = 0;      // [S] BeEvalArgs | [S] BeSolveArgs | [S] BeGaugeArgs | [S] BeRejectArgs | [S] BeMargArgs
     long long batched_rounds = 0, single_rounds = 0;
-    DvFrontBatch* front = nullptr;                // the members' front ends in shared launches (dv_batch_track_enqueue, dvins_api.hip)
+    DvFrontBatch* front = nullptr;                // the members' front ends in shared launches (dv_batch_track_enqueue, front_track.hip)
     hipEvent_t ev_state = nullptr;                // behind the shared accept + gauge + reject launches of a round: what the members' dv_est_process_end wait for
     std::mutex mu; std::condition_variable cv; int arrived = 0; long long generation = 0; int last_rc = 0;      // dv_batch_arrive
     bool aborted = false;                         // dv_batch_abort: every waiting and every later dv_batch_arrive returns -1

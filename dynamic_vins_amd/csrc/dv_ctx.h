@@ -141,7 +141,7 @@ struct BeFused {
 };
 int be_solve_fused(dv_ctx* ctx, dv_ba_problem* P, dv_ba_summary* summary, BeFused* fused);
 void be_batch_detach(dv_ctx* ctx);          // dv_destroy: leave the dv_batch this ctx is a member of
-struct DvFrontBatch;                        // the front-end half of a dv_batch (dvins_api.hip): stream, event, job tables of the shared tracking launches
+struct DvFrontBatch;                        // the front-end half of a dv_batch (front_track.hip): stream, event, job tables of the shared tracking launches
 DvFrontBatch*& be_batch_front(struct dv_batch* B);
 int be_batch_index(struct dv_batch* B);
 const std::vector<dv_ctx*>& be_batch_members(struct dv_batch* B);
@@ -269,3 +269,11 @@ struct HostScope {
     ~HostScope() { if (t) { const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); std::lock_guard<std::mutex> lk(c->timer_mu); t->total_ms += ms; t->count++; } }
 };
 void dv_harvest_timers(dv_ctx* ctx, hipStream_t synced);      // harvests the timers recorded on `synced` (must be idle)
+// ---- host helpers of dvins_api.hip that the tracker entries (front_track.hip) share with the operator-level entries ----
+int dv_ensure_hw(dv_ctx* ctx, int radius);         // the disc half widths of `radius` in hw_buf
+int dv_ensure_cand(dv_ctx* ctx, int w, int h);     // the candidate buffer of a w x h image
+// One frame's way into a pyramid (an image or a pair) in the job types of the table kernels: filled by dv_plan_pyramids, launched by value (dv_launch_pyramids) or scattered into a dv_batch round's tables
+struct PyrPlan { bool has_l0, pair; int levels; DvLevel0Job l0; DvPyrJob down[DV_MAX_LEVELS - 1]; DvPyr apron[2]; };
+int dv_plan_pyramids(dv_ctx* ctx, const DvPyr& a, const DvPyr* b, const uint8_t* img0, const uint8_t* img1, int stride, int mem, bool undistort, hipStream_t s, PyrPlan& P);
+void dv_launch_pyramids(const PyrPlan& P, hipStream_t s);
+int dv_build_cuda_pyramids(dv_ctx* ctx, PyrSet& C0, PyrSet* C1, const DvPyr& a0, const DvPyr* b0, int w, int h, int max_level);

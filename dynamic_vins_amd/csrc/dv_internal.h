@@ -93,7 +93,7 @@ void dv_launch_pyr_apron_multi(const DvPyr* pyrs_dev, int n_pyr, int max_levels,
 #define DV_L0_BGR        2
 struct DvLevel0Job { const uint8_t* src0; const uint8_t* src1; const uint8_t* map0; const uint8_t* map1; uint8_t* dst0; uint8_t* dst1; int spitch, dpitch, kind, pad_; };
 void dv_launch_level0_multi(const DvLevel0Job* jobs_dev, int n_jobs, int w, int h, hipStream_t s);
-// job-table forms of the tracker's single-workgroup / per-image stages (the front ends of a dv_batch group in shared launches: front_batch.hip)
+// job-table forms of the tracker's single-workgroup / per-image stages (the front ends of a dv_batch group in shared launches: front_track.hip)
 struct DvCompactJob { DvTrackState tr; const uint8_t* in_mask; int mask_pitch, sort_by_cnt; int* n_cand; unsigned* max_ord; };
 void dv_launch_compact_multi(const DvCompactJob* jobs_dev, int n_jobs, hipStream_t s);
 struct DvFinalizeJob { DvTrackState tr; dv_cam cam0, cam1; int stereo, use_off; double dt; dv_feat* out; int* n_out; const int* err_in; int* err_out; float off_x, off_y; };      // use_off: the points are ROI-local, (off_x, off_y) = the box corner

@@ -1,12 +1,11 @@
-// dvins_api.hip — C ABI (include/dvins.h) of libdvins_hip.so: context, HBM layout and per-frame
-// orchestration of the front end.  Everything a frame needs lives in HBM inside the ctx:
+// dvins_api.hip — C ABI (include/dvins.h) of libdvins_hip.so: context lifetime, HBM layout, timing and the operator-level entries.
+// Everything a frame needs lives in HBM inside the ctx:
 //   * three image pyramids (left current, left previous, right), each level pitched to 16 B,
 //     level 0 is a pitched copy of the input written by the first pyrDown launch;
 //   * the tracker state as a struct of arrays (DvTrackState) with its counters in device memory,
 //     so the whole of FeatureTracker::TrackImage is enqueued without a host round trip;
 //   * Shi-Tomasi candidate records + the pinned host staging buffer for the frame's output.
-// One frame = pyrDown x3 (stereo pair per launch) -> LK temporal -> compact/sort -> Shi-Tomasi tile
-// -> select/append -> LK stereo -> finalize -> one D2H copy of <= max_cnt 128-byte rows.
+// The per-frame orchestration of the tracker (one sequence, or a dv_batch group in shared launches) is front_track.hip.
 #include "dv_ctx.h"
 
 static std::string g_last_error;
@@ -31,7 +30,7 @@ static void circle_half_widths(int radius, std::vector<uint8_t>& hw) {
     }
 }
 
-static int ensure_hw(dv_ctx* ctx, int radius) {
+int dv_ensure_hw(dv_ctx* ctx, int radius) {
     if (radius < 0 || radius > DV_MAX_RADIUS) DV_FAIL("disc radius (min_dist) out of range [0,128]");
     if (ctx->hw_radius == radius) return 0;
     std::vector<uint8_t> hw; circle_half_widths(radius, hw);
@@ -42,7 +41,7 @@ static int ensure_hw(dv_ctx* ctx, int radius) {
     return 0;
 }
 
-static int ensure_cand(dv_ctx* ctx, int w, int h) {
+int dv_ensure_cand(dv_ctx* ctx, int w, int h) {
     int cap = std::max(4096, (w * h) / 4);
     if (cap <= ctx->cand_cap) return 0;
     DV_CHECK(ctx->cand_buf.ensure((size_t)cap * sizeof(DvCand)));
@@ -70,61 +69,73 @@ void dv_harvest_timers(dv_ctx* ctx, hipStream_t synced) {
     }
 }
 
-// Builds the pyramids of one image (img1 == nullptr) or of a stereo pair with shared launches.
-static int build_pyramids(dv_ctx* ctx, PyrSet& P0, PyrSet* P1, const uint8_t* img0, const uint8_t* img1, int w, int h, int stride,
-                          int mem, int max_level, bool undistort = false) {
-    DV_CHECK(P0.alloc(w, h, max_level));
-    if (P1) DV_CHECK(P1->alloc(w, h, max_level));
-    const DvPyr& a = P0.pyr;
-    const DvPyr* b = P1 ? &P1->pyr : nullptr;
-    hipStream_t s = ctx->stream;
-    const bool bgr = (mem & DV_FMT_BGR) != 0;
-    mem &= ~DV_FMT_BGR;
-    const bool dev = (mem == DV_MEM_DEVICE);
-    if (undistort) {    // cfg::is_undistort_input: cv::remap (+ cvtColor for colour frames) straight into level 0; host frames are staged in HBM first
-        if (w != ctx->undist_w || h != ctx->undist_h) DV_FAIL("dv_track_stereo: undistortion maps were installed for another image size");
-        if (b && !ctx->undist[1]) DV_FAIL("dv_track_stereo: undistortion maps installed for camera 0 but not for camera 1");
+// How a frame becomes pyramid level 0, decided here and nowhere else.  Maps and / or BGR frames: a level-0 job (cv::remap, with cvtColor for colour frames, or
+// cvtColor alone, straight into level 0; host frames are staged in s3 / s4 first, in rows of align_up(channels * w, 16) bytes).  Gray host frames, and pyramids of
+// one level: a pitched copy.  Gray device frames: the level-1 step reads the frame itself and writes the pitched level-0 copy beside level 1 (frame read once).
+// The copies are enqueued on s, the launches left to dv_launch_pyramids or a dv_batch round's tables.  undistort: the caller has checked the maps.
+int dv_plan_pyramids(dv_ctx* ctx, const DvPyr& a, const DvPyr* b, const uint8_t* img0, const uint8_t* img1, int stride, int mem, bool undistort, hipStream_t s, PyrPlan& P) {
+    const int w = a.L[0].w, h = a.L[0].h;
+    const bool bgr = (mem & DV_FMT_BGR) != 0, dev = (mem & ~DV_FMT_BGR) == DV_MEM_DEVICE;
+    if (!b) img1 = nullptr;
+    P.has_l0 = undistort || bgr; P.pair = b != nullptr; P.levels = a.levels;
+    if (P.has_l0) {
         const int cn = bgr ? 3 : 1;
-        const uint8_t* c0 = img0; const uint8_t* c1 = img1; int cp = stride;
+        DvLevel0Job& z = P.l0; z = DvLevel0Job{};
+        z.src0 = img0; z.src1 = img1; z.spitch = stride;
         if (!dev) {
-            cp = align_up(cn * w, 16);
+            const int cp = align_up(cn * w, 16);
             DV_CHECK(ctx->s3.ensure((size_t)cp * h)); DV_CHECK(hipMemcpy2DAsync(ctx->s3.p, cp, img0, stride, (size_t)cn * w, h, hipMemcpyHostToDevice, s));
-            c0 = (const uint8_t*)ctx->s3.p;
-            if (b) { DV_CHECK(ctx->s4.ensure((size_t)cp * h)); DV_CHECK(hipMemcpy2DAsync(ctx->s4.p, cp, img1, stride, (size_t)cn * w, h, hipMemcpyHostToDevice, s)); c1 = (const uint8_t*)ctx->s4.p; }
+            z.src0 = (const uint8_t*)ctx->s3.p; z.spitch = cp;
+            if (b) { DV_CHECK(ctx->s4.ensure((size_t)cp * h)); DV_CHECK(hipMemcpy2DAsync(ctx->s4.p, cp, img1, stride, (size_t)cn * w, h, hipMemcpyHostToDevice, s)); z.src1 = (const uint8_t*)ctx->s4.p; }
         }
-        const size_t m2off = (size_t)4 * w * h;
-        const uint8_t* mb0 = (const uint8_t*)ctx->undist_buf[0].p; const uint8_t* mb1 = (const uint8_t*)ctx->undist_buf[1].p;
-        dv_launch_remap(c0, b ? c1 : nullptr, w, h, cp, cn, bgr ? 1 : 0, (const int16_t*)mb0, (const uint16_t*)(mb0 + m2off),
-                        b ? (const int16_t*)mb1 : nullptr, b ? (const uint16_t*)(mb1 + m2off) : nullptr, a.L[0].p, b ? b->L[0].p : nullptr, a.L[0].pitch, s);
-    } else if (bgr) {   // colour input: BGR -> gray straight into level 0 (row N2); host frames are staged in HBM first
-        const uint8_t* c0 = img0; const uint8_t* c1 = img1; int cp = stride;
-        if (!dev) {
-            cp = align_up(3 * w, 16);
-            DV_CHECK(ctx->s3.ensure((size_t)cp * h)); DV_CHECK(hipMemcpy2DAsync(ctx->s3.p, cp, img0, stride, (size_t)3 * w, h, hipMemcpyHostToDevice, s));
-            c0 = (const uint8_t*)ctx->s3.p;
-            if (b) { DV_CHECK(ctx->s4.ensure((size_t)cp * h)); DV_CHECK(hipMemcpy2DAsync(ctx->s4.p, cp, img1, stride, (size_t)3 * w, h, hipMemcpyHostToDevice, s)); c1 = (const uint8_t*)ctx->s4.p; }
-        }
-        dv_launch_bgr2gray(c0, b ? c1 : nullptr, w, h, cp, a.L[0].p, b ? b->L[0].p : nullptr, a.L[0].pitch, s);
+        z.map0 = undistort ? (const uint8_t*)ctx->undist_buf[0].p : nullptr; z.map1 = (undistort && b) ? (const uint8_t*)ctx->undist_buf[1].p : nullptr;
+        z.dst0 = a.L[0].p; z.dst1 = b ? b->L[0].p : nullptr; z.dpitch = a.L[0].pitch;
+        z.kind = undistort ? (bgr ? DV_L0_REMAP_BGR : DV_L0_REMAP_GRAY) : DV_L0_BGR;
     } else if (!dev || a.levels == 1) {
-        hipMemcpyKind k = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        const hipMemcpyKind k = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
         DV_CHECK(hipMemcpy2DAsync(a.L[0].p, a.L[0].pitch, img0, stride, w, h, k, s));
         if (b) DV_CHECK(hipMemcpy2DAsync(b->L[0].p, b->L[0].pitch, img1, stride, w, h, k, s));
     }
     for (int l = 1; l < a.levels; ++l) {
-        const bool fuse_copy = dev && l == 1 && !bgr && !undistort;
-        const uint8_t* s0 = fuse_copy ? img0 : a.L[l - 1].p;
-        const uint8_t* s1 = b ? (fuse_copy ? img1 : b->L[l - 1].p) : nullptr;
-        const int sp = fuse_copy ? stride : a.L[l - 1].pitch;
-        dv_launch_pyr_down2(s0, s1, a.L[l - 1].w, a.L[l - 1].h, sp, a.L[l].p, b ? b->L[l].p : nullptr, a.L[l].pitch,
-                            fuse_copy ? a.L[0].p : nullptr, (fuse_copy && b) ? b->L[0].p : nullptr, a.L[0].pitch, s);
+        const bool fuse = dev && l == 1 && !P.has_l0;
+        DvPyrJob& pj = P.down[l - 1]; pj = DvPyrJob{};
+        pj.src0 = fuse ? img0 : a.L[l - 1].p; pj.src1 = b ? (fuse ? img1 : b->L[l - 1].p) : nullptr;
+        pj.dst0 = a.L[l].p; pj.dst1 = b ? b->L[l].p : nullptr;
+        pj.sw = a.L[l - 1].w; pj.sh = a.L[l - 1].h; pj.spitch = fuse ? stride : a.L[l - 1].pitch; pj.dw = a.L[l].w; pj.dh = a.L[l].h; pj.dpitch = a.L[l].pitch;
+        pj.cpy0 = fuse ? a.L[0].p : nullptr; pj.cpy1 = (fuse && b) ? b->L[0].p : nullptr; pj.cpitch = a.L[0].pitch;
     }
-    dv_launch_pyr_apron(a, b, s);
+    P.apron[0] = a; P.apron[1] = b ? *b : a;      // (one image: the second entry repeats the first — idempotent in a table, not launched by value)
+    return 0;
+}
+
+// the plan's launches with the single-sequence kernels, every argument by value
+void dv_launch_pyramids(const PyrPlan& P, hipStream_t s) {
+    const DvLevel0Job& z = P.l0;
+    const int w = P.apron[0].L[0].w, h = P.apron[0].L[0].h;
+    if (P.has_l0 && z.kind == DV_L0_BGR) dv_launch_bgr2gray(z.src0, z.src1, w, h, z.spitch, z.dst0, z.dst1, z.dpitch, s);
+    else if (P.has_l0) {
+        const size_t m2off = (size_t)4 * w * h;      // a camera's map block: w * h short2 of map1, then map2
+        const int bgr = z.kind == DV_L0_REMAP_BGR;
+        dv_launch_remap(z.src0, z.src1, w, h, z.spitch, bgr ? 3 : 1, bgr, (const int16_t*)z.map0, (const uint16_t*)(z.map0 + m2off),
+                        (const int16_t*)z.map1, z.map1 ? (const uint16_t*)(z.map1 + m2off) : nullptr, z.dst0, z.dst1, z.dpitch, s);
+    }
+    for (int l = 1; l < P.levels; ++l) { const DvPyrJob& j = P.down[l - 1]; dv_launch_pyr_down2(j.src0, j.src1, j.sw, j.sh, j.spitch, j.dst0, j.dst1, j.dpitch, j.cpy0, j.cpy1, j.cpitch, s); }
+    dv_launch_pyr_apron(P.apron[0], P.pair ? &P.apron[1] : nullptr, s);
+}
+
+// Builds the pyramids of one image (img1 == nullptr) or of a pair with shared launches: the operator-level entries' form (no maps)
+static int build_pyramids(dv_ctx* ctx, PyrSet& P0, PyrSet* P1, const uint8_t* img0, const uint8_t* img1, int w, int h, int stride, int mem, int max_level) {
+    DV_CHECK(P0.alloc(w, h, max_level));
+    if (P1) DV_CHECK(P1->alloc(w, h, max_level));
+    PyrPlan P;
+    if (dv_plan_pyramids(ctx, P0.pyr, P1 ? &P1->pyr : nullptr, img0, img1, stride, mem, false, ctx->stream, P)) return -1;
+    dv_launch_pyramids(P, ctx->stream);
     DV_CHECK(hipGetLastError());
     return 0;
 }
 
 // the pyramid cv::cuda::SparsePyrLKOpticalFlow builds (cuda::pyrDown: round half to even) on top of an existing level 0 (a0 / b0: level 0 of the regular pyramids)
-static int build_cuda_pyramids(dv_ctx* ctx, PyrSet& C0, PyrSet* C1, const DvPyr& a0, const DvPyr* b0, int w, int h, int max_level) {
+int dv_build_cuda_pyramids(dv_ctx* ctx, PyrSet& C0, PyrSet* C1, const DvPyr& a0, const DvPyr* b0, int w, int h, int max_level) {
     DV_CHECK(C0.alloc(w, h, max_level, true));
     if (C1) DV_CHECK(C1->alloc(w, h, max_level, true));
     C0.pyr.L[0] = a0.L[0];
@@ -263,395 +274,6 @@ int dv_timing_get(dv_ctx* ctx, const char* name, double* total_ms, long long* co
     return 0;
 }
 
-int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gray1, int w, int h, int stride, double t,
-                            const uint8_t* mask_or_null, int mode, int mem) {
-    if (!ctx) return -1;
-    HostScope hs(ctx, "h_front_enqueue");
-    if (!gray0) DV_FAIL("dv_track_stereo: gray0 is null");
-    if (w != ctx->cfg.width || h != ctx->cfg.height) DV_FAIL("dv_track_stereo: image size differs from config (reference: std::terminate, main.cpp:95-99)");
-    if (ctx->pending) DV_FAIL("dv_track_stereo_enqueue: previous frame not collected");
-    if (mode != DV_MODE_RAW && mode != DV_MODE_NAIVE && mode != DV_MODE_SEMANTIC) DV_FAIL("dv_track_stereo: unknown mode");
-    if ((mem & 0xff) == DV_MEM_PINNED) mem = (mem & ~0xff) | DV_MEM_DEVICE;      // pinned + mapped host memory is device-addressable: the kernels read it in place
-    if ((mem & 0xff) != DV_MEM_HOST && (mem & 0xff) != DV_MEM_DEVICE) DV_FAIL("dv_track_stereo: unknown memory kind");
-    DV_CHECK(hipSetDevice(ctx->cfg.device));
-    const dv_config& c = ctx->cfg;
-    const bool stereo = c.stereo && gray1;
-    hipStream_t s = ctx->stream;
-    if (ensure_hw(ctx, c.min_dist)) return -1;
-    if (ensure_cand(ctx, w, h)) return -1;
-    if (dv_inst_wait_before_next_frame(ctx)) DV_FAIL("dv_track_stereo: hipStreamWaitEvent");
-    if (ctx->last_front && ctx->last_front != s && ctx->last_done) DV_CHECK(hipStreamWaitEvent(s, ctx->last_done, 0));      // the previous frame ran on a dv_batch's front-end stream
-    StageScope frame(ctx, "frame");
-    ctx->cur ^= 1;
-    PyrSet& L = ctx->left[ctx->cur];
-    PyrSet& Lp = ctx->left[ctx->cur ^ 1];
-    {
-        StageScope sc(ctx, "pyr");
-        if (build_pyramids(ctx, L, stereo ? &ctx->right : nullptr, gray0, stereo ? gray1 : nullptr, w, h, stride, mem, 3, ctx->undist[0])) return -1;
-    }
-    if (ctx->inst) DV_CHECK(hipEventRecord(ctx->ev_pyr, s));
-    // FeatureTrackByLKGpu's own pyramids where the reference runs that tracker (naive: TrackLeftGPU + TrackRightGPU; semantic: TrackRightGPU)
-    ctx->leftc_valid[ctx->cur] = false;
-    if (mode != DV_MODE_RAW) {
-        StageScope sc(ctx, "pyr_cuda");
-        if (build_cuda_pyramids(ctx, ctx->leftc[ctx->cur], stereo ? &ctx->rightc : nullptr, L.pyr, stereo ? &ctx->right.pyr : nullptr, w, h, 3)) return -1;
-        ctx->leftc_valid[ctx->cur] = true;
-        if (mode == DV_MODE_NAIVE && ctx->have_prev && !ctx->leftc_valid[ctx->cur ^ 1]) {      // the previous frame was tracked in another mode: its pyramid of this flavour does not exist yet
-            if (build_cuda_pyramids(ctx, ctx->leftc[ctx->cur ^ 1], nullptr, Lp.pyr, nullptr, w, h, 3)) return -1;
-            ctx->leftc_valid[ctx->cur ^ 1] = true;
-        }
-    }
-    const uint8_t* mask_dev = nullptr; int mask_pitch = 0;
-    if (mask_or_null) {
-        const bool bgr_in = (mem & DV_FMT_BGR) != 0;
-        if ((mem & ~DV_FMT_BGR) == DV_MEM_DEVICE) { mask_dev = mask_or_null; mask_pitch = bgr_in ? w : stride; }
-        else {
-            mask_pitch = align_up(w, 16);
-            DV_CHECK(ctx->mask_buf.ensure((size_t)mask_pitch * h));
-            DV_CHECK(hipMemcpy2DAsync(ctx->mask_buf.p, mask_pitch, mask_or_null, bgr_in ? w : stride, w, h, hipMemcpyHostToDevice, s));
-            mask_dev = (const uint8_t*)ctx->mask_buf.p;
-        }
-    }
-    if (!ctx->unmask.empty()) {          // system/main.cpp:217-245: the static instances' pixels leave the merged mask (inv_merge_mask = 255 there) before anything reads it
-        if (!mask_dev) { ctx->unmask.clear(); DV_FAIL("dv_track_unmask_static: the frame carries no mask"); }
-        if (mask_dev != (const uint8_t*)ctx->mask_buf.p) {          // the caller's device buffer is not written to: work on a copy
-            const int mp = align_up(w, 16);
-            DV_CHECK(ctx->mask_buf.ensure((size_t)mp * h));
-            DV_CHECK(hipMemcpy2DAsync(ctx->mask_buf.p, mp, mask_dev, mask_pitch, w, h, hipMemcpyDeviceToDevice, s));
-            mask_dev = (const uint8_t*)ctx->mask_buf.p; mask_pitch = mp;
-        }
-        for (const dv_ctx::UnmaskJob& j : ctx->unmask)
-            dv_launch_unmask((uint8_t*)ctx->mask_buf.p, mask_pitch, w, h, j.x, j.y, j.w, j.h, (const uint8_t*)ctx->unmask_pinned + j.off, s);
-        ctx->unmask.clear();
-    }
-    const bool naive = (mode != DV_MODE_RAW);            // naive and semantic share the InstFeat code path (mask test, no sort, >= 10 new)
-    if (naive && mask_dev && c.mask_morphology_size > 0) {       // ErodeMask (background_tracker.cpp:408-416,764-768)
-        const int ep = align_up(w, 16);
-        DV_CHECK(ctx->s3.ensure((size_t)ep * h)); DV_CHECK(ctx->s4.ensure((size_t)ep * h));
-        dv_launch_erode(mask_dev, w, h, mask_pitch, c.mask_morphology_size, (uint8_t*)ctx->s3.p, ep, (uint8_t*)ctx->s4.p, ep, s);
-        mask_dev = (const uint8_t*)ctx->s4.p; mask_pitch = ep;
-    }
-    // forward/backward consistency: FeatureTrackByLK keeps <= 0.5 px (feature_utils.cpp:56), FeatureTrackByLKGpu <= 1.0 px (:126) (Q12) — and the two are different
-    // trackers (lk.hip / lk_cuda.hip), each used where the reference uses it
-    const float dist_temporal = (mode == DV_MODE_NAIVE) ? 1.0f : 0.5f;       // TrackLeftGPU (naive) vs TrackLeft (raw, semantic)
-    const float dist_stereo = (mode == DV_MODE_RAW) ? 0.5f : 1.0f;           // TrackRightGPU in naive and semantic
-    if (ctx->have_prev) {
-        StageScope sc(ctx, "lk_temporal");
-        if (mode == DV_MODE_NAIVE)      // TrackLeftGPU -> FeatureTrackByLKGpu (instance_feature.cpp:191-216): the GPU tracker's rule
-            dv_launch_lk_cuda_track(ctx->leftc[ctx->cur ^ 1].pyr, ctx->leftc[ctx->cur].pyr, ctx->tr.last_pts, ctx->tr.n_feat, c.max_cnt, c.flow_back, dist_temporal, ctx->tr.lk_pts, ctx->tr.lk_status, s);
-        else
-            dv_launch_lk_track(Lp.pyr, L.pyr, ctx->tr.last_pts, ctx->tr.n_feat, c.max_cnt, c.flow_back, dist_temporal, ctx->tr.lk_pts,
-                               ctx->tr.lk_status, s, ctx->tr.lk_order);
-    }
-    {
-        StageScope sc(ctx, "compact");
-        dv_launch_compact(ctx->tr, naive ? mask_dev : nullptr, mask_pitch, naive ? 0 : 1, ctx->n_cand, ctx->max_ord, s);
-    }
-    const int min_new = naive ? 10 : 1;                   // Q23: instance_feature.cpp:353-356 vs background_tracker.cpp:82-90
-    // DetectNewFeature(img, use_gpu, ...): TrackImageNaive passes true (background_tracker.cpp:445) -> DetectShiTomasiCornersGpu (feature_utils.cpp:339-348),
-    // TrackSemanticImage passes false (:789) and TrackImage calls cv::goodFeaturesToTrack itself (:85)
-    const int gftt_rule = (mode == DV_MODE_NAIVE) ? DV_GFTT_RULE_CUDA : DV_GFTT_RULE_CPU;
-    {
-        StageScope sc(ctx, "gftt_eig");
-        GfttTileArgs a{};
-        a.img = L.pyr.L[0].p; a.w = w; a.h = h; a.pitch = L.pyr.L[0].pitch;
-        a.in_mask = mask_dev; a.mask_pitch = mask_pitch;
-        a.disc_pts = ctx->tr.curr_pts; a.n_disc = ctx->tr.n_tracked; a.radius = c.min_dist; a.hw = (const uint8_t*)ctx->hw_buf.p;
-        a.n_feat = ctx->tr.n_feat; a.max_cnt = c.max_cnt; a.min_new = min_new;
-        a.eig_out = nullptr; a.eig_pitch = 0;
-        a.cand = (DvCand*)ctx->cand_buf.p; a.cand_cap = ctx->cand_cap; a.n_cand = ctx->n_cand; a.max_ord = ctx->max_ord;
-        a.rule = gftt_rule;
-        dv_launch_gftt_tile(a, s);
-    }
-    {
-        StageScope sc(ctx, "gftt_select");
-        GfttSelectArgs a{};
-        a.cand = (const DvCand*)ctx->cand_buf.p; a.n_cand = ctx->n_cand; a.cand_cap = ctx->cand_cap; a.max_ord = ctx->max_ord;
-        a.w = w; a.h = h; a.quality = 0.01; a.min_dist = (double)c.min_dist;
-        a.max_n_host = 0; a.n_feat = ctx->tr.n_feat; a.max_cnt = c.max_cnt; a.min_new = min_new;
-        a.out_xy = nullptr; a.n_out = nullptr; a.tr = ctx->tr; a.has_tr = 1; a.err_flag = ctx->err_flag; a.rule = gftt_rule;
-        if (dv_launch_gftt_select(a, s)) DV_FAIL("gftt_select: cannot set dynamic LDS size");
-    }
-    if (ctx->inst) DV_CHECK(hipEventRecord(ctx->ev_bg_select, s));
-    if (stereo) {
-        StageScope sc(ctx, "lk_stereo");
-        if (mode != DV_MODE_RAW)        // TrackRightGPU -> FeatureTrackByLKGpu (instance_feature.cpp:278-310) in naive and semantic mode
-            dv_launch_lk_cuda_track(ctx->leftc[ctx->cur].pyr, ctx->rightc.pyr, ctx->tr.curr_pts, ctx->tr.n_feat, c.max_cnt, c.flow_back, dist_stereo, ctx->tr.right_pts, ctx->tr.right_status, s);
-        else
-            dv_launch_lk_track(L.pyr, ctx->right.pyr, ctx->tr.curr_pts, ctx->tr.n_feat, c.max_cnt, c.flow_back, dist_stereo,
-                               ctx->tr.right_pts, ctx->tr.right_status, s, ctx->tr.lk_order);
-    }
-    {
-        StageScope sc(ctx, "finalize");
-        // the rows, their count and the device error flags go straight into the pinned buffer (three copy dispatches behind the kernel before: ~20 us of the
-        // tracker's latency per frame)
-        dv_launch_finalize(ctx->tr, c.cam0, c.cam1, stereo ? 1 : 0, t - ctx->prev_time, c.max_cnt, ctx->out_pinned, ctx->nout_pinned, s, ctx->err_flag, ctx->err_pinned);
-    }
-    DV_CHECK(hipGetLastError());
-    DV_CHECK(hipEventRecord(ctx->done, s));
-    ctx->last_done = ctx->done; ctx->last_front = s;
-    ctx->prev_time = t; ctx->have_prev = true; ctx->pending = true;
-    return 0;
-}
-
-int dv_track_unmask_static(dv_ctx* ctx, const dv_inst_det* dets, int n_dets, const uint32_t* static_ids, int n_static) {
-    if (!ctx) return -1;
-    ctx->unmask.clear();
-    if (n_static <= 0 || n_dets <= 0) return 0;
-    if (!dets || !static_ids) DV_FAIL("dv_track_unmask_static: null argument");
-    if (ctx->pending) DV_FAIL("dv_track_unmask_static: call it before dv_track_stereo_enqueue of the frame it belongs to");
-    size_t need = 0;
-    for (int i = 0; i < n_dets; ++i) if (std::find(static_ids, static_ids + n_static, dets[i].track_id) != static_ids + n_static) need += ((size_t)dets[i].w * dets[i].h + 15) / 16 * 16;
-    if (!need) return 0;
-    if (ctx->unmask_pinned_bytes < need) {
-        DV_CHECK(hipStreamSynchronize(ctx->stream));          // (a previous frame's kernels may still read the old staging area)
-        if (ctx->unmask_pinned) (void)hipHostFree(ctx->unmask_pinned);
-        ctx->unmask_pinned = nullptr; ctx->unmask_pinned_bytes = 0;
-        const size_t want = std::max<size_t>(2 * need, (size_t)ctx->cfg.width * ctx->cfg.height);      // (a frame's worth from the start: the rectangles grow as objects come closer)
-        DV_CHECK(hipHostMalloc(&ctx->unmask_pinned, want, hipHostMallocDefault));
-        ctx->unmask_pinned_bytes = want;
-    } else if (ctx->last_done && ctx->last_done == ctx->done) DV_CHECK(hipEventSynchronize(ctx->done));      // the previous frame's unmask kernels have read the staging area (a no-op wait in the usual case: that frame was collected)
-    size_t off = 0;
-    for (int i = 0; i < n_dets; ++i) {
-        const dv_inst_det& d = dets[i];
-        if (std::find(static_ids, static_ids + n_static, d.track_id) == static_ids + n_static) continue;
-        if (!d.mask || d.w <= 0 || d.h <= 0 || d.x < 0 || d.y < 0 || d.x + d.w > ctx->cfg.width || d.y + d.h > ctx->cfg.height) { ctx->unmask.clear(); DV_FAIL("dv_track_unmask_static: bad detection rectangle / mask"); }
-        std::memcpy((uint8_t*)ctx->unmask_pinned + off, d.mask, (size_t)d.w * d.h);
-        ctx->unmask.push_back({ d.x, d.y, d.w, d.h, off });
-        off += ((size_t)d.w * d.h + 15) / 16 * 16;
-    }
-    return 0;
-}
-
-int dv_track_stereo_collect(dv_ctx* ctx, dv_feat* out, int* n_out) {
-    if (!ctx) return -1;
-    if (!ctx->pending) DV_FAIL("dv_track_stereo_collect: nothing enqueued");
-    { HostScope hs(ctx, "h_front_wait"); DV_CHECK(hipEventSynchronize(ctx->last_done ? ctx->last_done : ctx->done)); }
-    ctx->pending = false;
-    if (ctx->timing) dv_harvest_timers(ctx, ctx->stream);
-    if (*ctx->err_pinned) {
-        int f = *ctx->err_pinned;
-        DV_CHECK(hipMemsetAsync(ctx->err_flag, 0, 4, ctx->stream));
-        DV_FAIL(std::string("front end device error flags=") + std::to_string(f) +
-                " (1: candidate buffer overflow, 2: min-distance grid too large, 4: value bin overflow)");
-    }
-    const int n = *ctx->nout_pinned;
-    if (n_out) *n_out = n;
-    if (out && n > 0) std::memcpy(out, ctx->out_pinned, (size_t)n * sizeof(dv_feat));
-    return 0;
-}
-
-int dv_track_stereo(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gray1, int w, int h, int stride, double t,
-                    const uint8_t* mask_or_null, int mode, int mem, dv_feat* out, int* n_out) {
-    if (dv_track_stereo_enqueue(ctx, gray0, gray1, w, h, stride, t, mask_or_null, mode, mem)) return -1;
-    return dv_track_stereo_collect(ctx, out, n_out);
-}
-
-}  // extern "C"
-
-// ------------------------------- the front ends of a dv_batch group in shared launches -------------------------------
-// FeatureTracker::TrackImage (background_tracker.cpp:52-158) of S independent sequences, one launch per STAGE for all of them (the reference runs one process per
-// sequence, system/main.cpp:178-330): pyrDown levels 1..3 (level 1 also writes the pitched level-0 copy), aprons, temporal LK, compaction / sort, Shi-Tomasi tile,
-// corner selection, stereo LK, rows = 10 launches per group and frame instead of 10 per sequence.  The kernels are the single-sequence kernels' bodies behind a
-// job table in HBM (blockIdx.z / .y / .x = member), so every member's rows are bit-identical to what its own dv_track_stereo_enqueue produces.
-// Members with undistortion maps (cfg::is_undistort_input) or BGR frames differ in level 0 alone: one more launch (level0_multi_kernel, pyramid.hip) fills it for all
-// of them, each through its own maps, and level 1 then reads it; a round without such a member does not launch it.
-struct DvFrontBatch {
-    hipStream_t stream = nullptr; hipEvent_t done = nullptr, ev_copy[2] = { nullptr, nullptr };
-    DevBuf tab[2]; void* tab_pinned[2] = { nullptr, nullptr }; size_t tab_bytes = 0; int parity = 0; bool copy_used[2] = { false, false };
-    long long rounds = 0, members_batched = 0, members_single = 0;
-};
-void dv_front_batch_sync(DvFrontBatch* F) { if (F && F->stream) (void)hipStreamSynchronize(F->stream); }      // be_batch_detach: a member leaves while one of its frames may be in flight on the group's front-end stream
-void dv_front_batch_release(DvFrontBatch* F) {
-    if (!F) return;
-    if (F->stream) { (void)hipStreamSynchronize(F->stream); (void)hipStreamDestroy(F->stream); }
-    if (F->done) (void)hipEventDestroy(F->done);
-    for (int k = 0; k < 2; ++k) { if (F->ev_copy[k]) (void)hipEventDestroy(F->ev_copy[k]); F->tab[k].release(); if (F->tab_pinned[k]) (void)hipHostFree(F->tab_pinned[k]); }
-    delete F;
-}
-
-extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int n) {
-    if (!B || (n > 0 && !jobs) || n < 0) { dv_set_error(nullptr, "dv_batch_track_enqueue: bad arguments"); return -1; }
-    const std::vector<dv_ctx*>& mem = be_batch_members(B);
-    if (n == 0 || mem.empty()) return 0;
-    dv_ctx* ctx = mem[0];                                       // errors of the shared part are reported on the first member (and the global slot)
-    DV_CHECK(hipSetDevice(ctx->cfg.device));
-    DvFrontBatch*& Fp = be_batch_front(B);
-    if (!Fp) {
-        Fp = new DvFrontBatch();
-        DV_CHECK((std::getenv("DVINS_CU_PARTITION_FRONT") || std::getenv("DVINS_SOLVE_CUS")) ? dv_group_stream_create(&Fp->stream, be_batch_index(B)) : hipStreamCreateWithFlags(&Fp->stream, hipStreamNonBlocking));
-        DV_CHECK(hipEventCreateWithFlags(&Fp->done, hipEventDisableTiming));
-        for (int k = 0; k < 2; ++k) DV_CHECK(hipEventCreateWithFlags(&Fp->ev_copy[k], hipEventDisableTiming));
-    }
-    DvFrontBatch& F = *Fp;
-    // ---- which jobs can share launches: raw mode, no mask, no object tracker, the group's common geometry (gray or BGR frames, with or without the member's own
-    //      undistortion maps: those differ in how level 0 is filled and in nothing behind it) ----
-    std::vector<int> M;                                         // job indices that are batched
-    const dv_config* ref = nullptr;
-    for (int i = 0; i < n; ++i) {
-        const dv_track_job& j = jobs[i];
-        if (j.member < 0 || j.member >= (int)mem.size()) DV_FAIL("dv_batch_track_enqueue: member index out of range");
-        dv_ctx* c = mem[j.member];
-        for (int q = 0; q < i; ++q) if (jobs[q].member == j.member) DV_FAIL("dv_batch_track_enqueue: a member appears twice");
-        const bool plain = j.mode == DV_MODE_RAW && !j.mask && !c->inst && !c->timing && j.gray0 && (!c->cfg.stereo || j.gray1);
-        const bool same = !ref || (c->cfg.width == ref->width && c->cfg.height == ref->height && c->cfg.stereo == ref->stereo && c->cfg.flow_back == ref->flow_back);
-        if (plain && same) { if (!ref) ref = &c->cfg; M.push_back(i); }
-        else {      // its own launches on its own stream (ordered behind whatever the batch stream still holds for it: dv_track_stereo_enqueue)
-            if (dv_track_stereo_enqueue(c, j.gray0, j.gray1, c->cfg.width, c->cfg.height, j.stride > 0 ? j.stride : c->cfg.width * ((j.mem & DV_FMT_BGR) ? 3 : 1), j.t, j.mask, j.mode, j.mem)) { dv_set_error(ctx, c->err); return -1; }
-            F.members_single++;
-        }
-    }
-    const int S = (int)M.size();
-    if (S == 0) return 0;
-    if (S == 1) {      // nothing to share
-        const dv_track_job& j = jobs[M[0]]; dv_ctx* c = mem[j.member];
-        if (dv_track_stereo_enqueue(c, j.gray0, j.gray1, c->cfg.width, c->cfg.height, j.stride > 0 ? j.stride : c->cfg.width * ((j.mem & DV_FMT_BGR) ? 3 : 1), j.t, nullptr, DV_MODE_RAW, j.mem)) { dv_set_error(ctx, c->err); return -1; }
-        F.members_single++;
-        return 0;
-    }
-    const int w = ref->width, h = ref->height; const bool stereo = ref->stereo != 0;
-    hipStream_t s = F.stream;
-    // ---- per member: the checks and the lazily created resources of dv_track_stereo_enqueue ----
-    // (a member's `cur` flips here because everything below addresses its pyramids through it; a failure further down — table growth, the upload, an LDS attribute — flips it
-    //  back, so that no member is left with the wrong current pyramid and no pending frame: ADVICE r4)
-    struct CurGuard { std::vector<dv_ctx*> flipped; bool committed = false; ~CurGuard() { if (!committed) for (dv_ctx* c : flipped) c->cur ^= 1; } } cur_guard;
-    int n_max = 0;
-    for (int i : M) {
-        const dv_track_job& j = jobs[i]; dv_ctx* c = mem[j.member];
-        if (c->pending) { dv_set_error(ctx, "dv_batch_track_enqueue: a member's previous frame was not collected"); return -1; }
-        if ((j.mem & 0xff) != DV_MEM_HOST && (j.mem & 0xff) != DV_MEM_DEVICE && (j.mem & 0xff) != DV_MEM_PINNED) {      // dv_track_stereo_enqueue's check, with its text
-            dv_set_error(c, "dv_track_stereo: unknown memory kind"); dv_set_error(ctx, c->err); return -1;
-        }
-        if (c->undist[0]) {      // build_pyramids' checks of the undistort path, with its texts
-            const char* bad = (w != c->undist_w || h != c->undist_h) ? "dv_track_stereo: undistortion maps were installed for another image size"
-                            : (stereo && !c->undist[1]) ? "dv_track_stereo: undistortion maps installed for camera 0 but not for camera 1" : nullptr;
-            if (bad) { dv_set_error(c, bad); dv_set_error(ctx, bad); return -1; }
-        }
-        if (ensure_hw(c, c->cfg.min_dist) || ensure_cand(c, w, h)) { dv_set_error(ctx, c->err); return -1; }
-        if (c->last_front && c->last_front != s && c->last_done) DV_CHECK(hipStreamWaitEvent(s, c->last_done, 0));      // its previous frame ran on its own stream
-        c->cur ^= 1; cur_guard.flipped.push_back(c);
-        DV_CHECK(c->left[c->cur].alloc(w, h, 3));
-        if (stereo) DV_CHECK(c->right.alloc(w, h, 3));
-        n_max = std::max(n_max, c->cfg.max_cnt);
-    }
-    // ---- the job tables of the round: one pinned block, one upload ----
-    const size_t o_pyr = 0, o_apr = o_pyr + (size_t)3 * S * sizeof(DvPyrJob), o_lk = (o_apr + (size_t)2 * S * sizeof(DvPyr) + 255) / 256 * 256,
-                 o_cmp = (o_lk + (size_t)2 * S * sizeof(DvLkJob) + 255) / 256 * 256, o_gt = (o_cmp + (size_t)S * sizeof(DvCompactJob) + 255) / 256 * 256,
-                 o_gs = (o_gt + (size_t)S * sizeof(GfttTileArgs) + 255) / 256 * 256, o_fin = (o_gs + (size_t)S * sizeof(GfttSelectArgs) + 255) / 256 * 256,
-                 o_l0 = (o_fin + (size_t)S * sizeof(DvFinalizeJob) + 255) / 256 * 256, total = (o_l0 + (size_t)S * sizeof(DvLevel0Job) + 255) / 256 * 256;
-    const int par = F.parity; F.parity ^= 1;
-    if (F.copy_used[par]) DV_CHECK(hipEventSynchronize(F.ev_copy[par]));      // the upload that last read this pinned block (two rounds ago) has run
-    if (F.tab_bytes < total) {
-        DV_CHECK(hipStreamSynchronize(s));
-        const size_t cap = total * 2;
-        for (int k = 0; k < 2; ++k) {
-            DV_CHECK(F.tab[k].ensure(cap));
-            if (F.tab_pinned[k]) (void)hipHostFree(F.tab_pinned[k]);
-            F.tab_pinned[k] = nullptr;
-            DV_CHECK(hipHostMalloc(&F.tab_pinned[k], cap, hipHostMallocDefault));
-        }
-        F.tab_bytes = cap;
-    }
-    uint8_t* hp = (uint8_t*)F.tab_pinned[par]; const uint8_t* dp = (const uint8_t*)F.tab[par].p;
-    DvPyrJob* h_pyr = (DvPyrJob*)(hp + o_pyr); DvPyr* h_apr = (DvPyr*)(hp + o_apr); DvLkJob* h_lk = (DvLkJob*)(hp + o_lk); DvCompactJob* h_cmp = (DvCompactJob*)(hp + o_cmp);
-    GfttTileArgs* h_gt = (GfttTileArgs*)(hp + o_gt); GfttSelectArgs* h_gs = (GfttSelectArgs*)(hp + o_gs); DvFinalizeJob* h_fin = (DvFinalizeJob*)(hp + o_fin);
-    DvLevel0Job* h_l0 = (DvLevel0Job*)(hp + o_l0); int n_l0 = 0;      // only the members whose level 0 is not a copy of the frame: none in an all-plain round, and no launch then
-    int levels = 0, lw[DV_MAX_LEVELS] = { 0 }, lh[DV_MAX_LEVELS] = { 0 };
-    for (int k = 0; k < S; ++k) {
-        const dv_track_job& j = jobs[M[k]]; dv_ctx* c = mem[j.member];
-        const dv_config& cf = c->cfg;
-        PyrSet& L = c->left[c->cur]; PyrSet& Lp = c->left[c->cur ^ 1];
-        const DvPyr& a = L.pyr; const DvPyr* b = stereo ? &c->right.pyr : nullptr;
-        const bool bgr = (j.mem & DV_FMT_BGR) != 0, und = c->undist[0], l0 = bgr || und;
-        const int mk = j.mem & 0xff, cn = bgr ? 3 : 1;
-        const int stride = j.stride > 0 ? j.stride : cn * w;
-        const bool dev = mk == DV_MEM_DEVICE || mk == DV_MEM_PINNED;      // (pinned + mapped host memory: read in place by the level-0 / level-1 kernel, like HBM)
-        if (l0) {      // remap and / or BGR -> gray straight into level 0 (build_pyramids); host frames are staged in the member's own buffers first, on this stream
-            DvLevel0Job z{};
-            z.src0 = j.gray0; z.src1 = b ? j.gray1 : nullptr; z.spitch = stride;
-            if (!dev) {
-                const int cp = align_up(cn * w, 16);
-                DV_CHECK(c->s3.ensure((size_t)cp * h)); DV_CHECK(hipMemcpy2DAsync(c->s3.p, cp, j.gray0, stride, (size_t)cn * w, h, hipMemcpyHostToDevice, s));
-                z.src0 = (const uint8_t*)c->s3.p; z.spitch = cp;
-                if (b) { DV_CHECK(c->s4.ensure((size_t)cp * h)); DV_CHECK(hipMemcpy2DAsync(c->s4.p, cp, j.gray1, stride, (size_t)cn * w, h, hipMemcpyHostToDevice, s)); z.src1 = (const uint8_t*)c->s4.p; }
-            }
-            z.map0 = und ? (const uint8_t*)c->undist_buf[0].p : nullptr; z.map1 = (und && b) ? (const uint8_t*)c->undist_buf[1].p : nullptr;
-            z.dst0 = a.L[0].p; z.dst1 = b ? b->L[0].p : nullptr; z.dpitch = a.L[0].pitch;
-            z.kind = und ? (bgr ? DV_L0_REMAP_BGR : DV_L0_REMAP_GRAY) : DV_L0_BGR;
-            h_l0[n_l0++] = z;
-        } else if (!dev || a.levels == 1) {      // host frames: the upload IS the level-0 copy
-            DV_CHECK(hipMemcpy2DAsync(a.L[0].p, a.L[0].pitch, j.gray0, stride, w, h, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-            if (b) DV_CHECK(hipMemcpy2DAsync(b->L[0].p, b->L[0].pitch, j.gray1, stride, w, h, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-        }
-        levels = a.levels;
-        for (int l = 1; l < a.levels; ++l) {
-            const bool fuse = dev && l == 1 && !l0;      // (a member with a level-0 job: level 1 reads L[0], as in build_pyramids)
-            DvPyrJob pj{};
-            pj.src0 = fuse ? j.gray0 : a.L[l - 1].p; pj.src1 = b ? (fuse ? j.gray1 : b->L[l - 1].p) : nullptr;
-            pj.dst0 = a.L[l].p; pj.dst1 = b ? b->L[l].p : nullptr;
-            pj.sw = a.L[l - 1].w; pj.sh = a.L[l - 1].h; pj.spitch = fuse ? stride : a.L[l - 1].pitch; pj.dw = a.L[l].w; pj.dh = a.L[l].h; pj.dpitch = a.L[l].pitch;
-            pj.cpy0 = fuse ? a.L[0].p : nullptr; pj.cpy1 = (fuse && b) ? b->L[0].p : nullptr; pj.cpitch = a.L[0].pitch;
-            h_pyr[(size_t)(l - 1) * S + k] = pj;
-            lw[l] = a.L[l].w; lh[l] = a.L[l].h;
-        }
-        h_apr[2 * k] = a; h_apr[2 * k + 1] = b ? *b : a;      // (mono: the second entry repeats the first — idempotent)
-        // temporal LK (skipped by its own n_feat == 0 on a sequence's first frame), stereo LK
-        DvLkJob t{}; t.A = Lp.pyr; t.B = a; t.pts_a = c->tr.last_pts; t.n_dev = c->tr.n_feat; t.pts_b = c->tr.lk_pts; t.status = c->tr.lk_status;
-        if (!c->have_prev) t.A = a;                           // (no previous pyramid yet: n_feat is 0, nothing is read)
-        h_lk[k] = t;
-        DvLkJob r{}; r.A = a; r.B = b ? *b : a; r.pts_a = c->tr.curr_pts; r.n_dev = c->tr.n_feat; r.pts_b = c->tr.right_pts; r.status = c->tr.right_status;
-        h_lk[S + k] = r;
-        h_cmp[k] = DvCompactJob{ c->tr, nullptr, 0, 1, c->n_cand, c->max_ord };
-        GfttTileArgs g{};
-        g.img = a.L[0].p; g.w = w; g.h = h; g.pitch = a.L[0].pitch; g.in_mask = nullptr; g.mask_pitch = 0;
-        g.disc_pts = c->tr.curr_pts; g.n_disc = c->tr.n_tracked; g.radius = cf.min_dist; g.hw = (const uint8_t*)c->hw_buf.p;
-        g.n_feat = c->tr.n_feat; g.max_cnt = cf.max_cnt; g.min_new = 1; g.eig_out = nullptr; g.eig_pitch = 0;
-        g.cand = (DvCand*)c->cand_buf.p; g.cand_cap = c->cand_cap; g.n_cand = c->n_cand; g.max_ord = c->max_ord;
-        h_gt[k] = g;
-        GfttSelectArgs q{};
-        q.cand = (const DvCand*)c->cand_buf.p; q.n_cand = c->n_cand; q.cand_cap = c->cand_cap; q.max_ord = c->max_ord;
-        q.w = w; q.h = h; q.quality = 0.01; q.min_dist = (double)cf.min_dist; q.max_n_host = 0; q.n_feat = c->tr.n_feat; q.max_cnt = cf.max_cnt; q.min_new = 1;
-        q.out_xy = nullptr; q.n_out = nullptr; q.tr = c->tr; q.has_tr = 1; q.err_flag = c->err_flag;
-        h_gs[k] = q;
-        DvFinalizeJob f{};
-        f.tr = c->tr; f.cam0 = cf.cam0; f.cam1 = cf.cam1; f.stereo = stereo ? 1 : 0; f.dt = j.t - c->prev_time; f.out = c->out_pinned; f.n_out = c->nout_pinned;
-        f.err_in = c->err_flag; f.err_out = c->err_pinned;
-        h_fin[k] = f;
-    }
-    DV_CHECK(dv_copy_async(F.tab[par].p, hp, total, s));
-    DV_CHECK(hipEventRecord(F.ev_copy[par], s)); F.copy_used[par] = true;
-    // ---- the stages ----
-    if (n_l0) dv_launch_level0_multi((const DvLevel0Job*)(dp + o_l0), n_l0, w, h, s);
-    for (int l = 1; l < levels; ++l) dv_launch_pyr_down_multi((const DvPyrJob*)(dp + o_pyr) + (size_t)(l - 1) * S, S, lw[l], lh[l], s);
-    dv_launch_pyr_apron_multi((const DvPyr*)(dp + o_apr), 2 * S, levels, s);
-    dv_launch_lk_track_multi((const DvLkJob*)(dp + o_lk), S, n_max, ref->flow_back, 0.5f, s);
-    dv_launch_compact_multi((const DvCompactJob*)(dp + o_cmp), S, s);
-    dv_launch_gftt_tile_multi((const GfttTileArgs*)(dp + o_gt), S, w, h, s);
-    if (dv_launch_gftt_select_multi((const GfttSelectArgs*)(dp + o_gs), S, s)) DV_FAIL("gftt_select: cannot set dynamic LDS size");
-    if (stereo) dv_launch_lk_track_multi((const DvLkJob*)(dp + o_lk) + S, S, n_max, ref->flow_back, 0.5f, s);
-    dv_launch_finalize_multi((const DvFinalizeJob*)(dp + o_fin), S, n_max, s);
-    DV_CHECK(hipGetLastError());
-    DV_CHECK(hipEventRecord(F.done, s));
-    for (int i : M) {
-        const dv_track_job& j = jobs[i]; dv_ctx* c = mem[j.member];
-        c->last_done = F.done; c->last_front = s;
-        c->prev_time = j.t; c->have_prev = true; c->pending = true;
-    }
-    cur_guard.committed = true;
-    F.rounds++; F.members_batched += S;
-    return 0;
-}
-extern "C" int dv_batch_track_info(dv_batch* B, long long* rounds, long long* members_batched, long long* members_single) {
-    if (!B) return -1;
-    DvFrontBatch* F = be_batch_front(B);
-    if (rounds) *rounds = F ? F->rounds : 0;
-    if (members_batched) *members_batched = F ? F->members_batched : 0;
-    if (members_single) *members_single = F ? F->members_single : 0;
-    return 0;
-}
-
-extern "C" {
-
 // ------------------------------- operator-level entries -------------------------------
 
 // copies `bytes` from user memory (host or device) into a ctx scratch buffer on the device
@@ -711,7 +333,7 @@ int dv_track_by_lk(dv_ctx* ctx, const uint8_t* img1, const uint8_t* img2, int w,
 // cv::cuda::SparsePyrLKOpticalFlow::calc (use_initial: pts_b holds the initial flow) and FeatureTrackByLKGpu, operator forms for the parity tests
 static int lk_cuda_prepare(dv_ctx* ctx, const uint8_t* img_a, const uint8_t* img_b, int w, int h, int stride, int mem, int max_level) {
     if (build_pyramids(ctx, ctx->opA, &ctx->opB, img_a, img_b, w, h, stride, mem, 0)) return -1;          // level 0 only (pitched copies)
-    return build_cuda_pyramids(ctx, ctx->leftc[0], &ctx->leftc[1], ctx->opA.pyr, &ctx->opB.pyr, w, h, max_level);
+    return dv_build_cuda_pyramids(ctx, ctx->leftc[0], &ctx->leftc[1], ctx->opA.pyr, &ctx->opB.pyr, w, h, max_level);
 }
 int dv_lk_cuda(dv_ctx* ctx, const uint8_t* img_a, const uint8_t* img_b, int w, int h, int stride, const float* pts_a, int n, int max_level, int iters, int use_initial,
                float* pts_b, uint8_t* status, int mem) {
@@ -779,7 +401,7 @@ static int min_eigen_rule(dv_ctx* ctx, const uint8_t* img, int w, int h, int str
     DV_CHECK(hipSetDevice(ctx->cfg.device));
     const uint8_t* d_img; int pitch;
     if (stage_image(ctx, ctx->s0, img, w, h, stride, mem, &d_img, &pitch)) return -1;
-    if (ensure_cand(ctx, w, h)) return -1;
+    if (dv_ensure_cand(ctx, w, h)) return -1;
     float* d_eig = eig;
     if (mem != DV_MEM_DEVICE) { DV_CHECK(ctx->s1.ensure((size_t)w * h * 4)); d_eig = (float*)ctx->s1.p; }
     DV_CHECK(hipMemsetAsync(ctx->n_cand, 0, 8, ctx->stream));     // n_cand + max_ord
@@ -806,7 +428,7 @@ static int gftt_rule_op(dv_ctx* ctx, const uint8_t* img, const uint8_t* mask_or_
     const uint8_t *d_img, *d_mask = nullptr; int pitch, mpitch = 0;
     if (stage_image(ctx, ctx->s0, img, w, h, stride, mem, &d_img, &pitch)) return -1;
     if (mask_or_null && stage_image(ctx, ctx->s3, mask_or_null, w, h, stride, mem, &d_mask, &mpitch)) return -1;
-    if (ensure_cand(ctx, w, h)) return -1;
+    if (dv_ensure_cand(ctx, w, h)) return -1;
     DV_CHECK(ctx->s1.ensure((size_t)DV_MAX_FEATS * 8 + 16));
     float2* d_out = (float2*)ctx->s1.p; int* d_n = (int*)((uint8_t*)ctx->s1.p + (size_t)DV_MAX_FEATS * 8);
     DV_CHECK(hipMemsetAsync(ctx->n_cand, 0, 12, ctx->stream));    // n_cand, max_ord, err_flag
@@ -964,7 +586,7 @@ int dv_circle_mask(dv_ctx* ctx, uint8_t* mask, int w, int h, int stride, const f
     if (!ctx) return -1;
     if (!mask || (n > 0 && !pts_xy)) DV_FAIL("dv_circle_mask: null argument");
     DV_CHECK(hipSetDevice(ctx->cfg.device));
-    if (ensure_hw(ctx, radius)) return -1;
+    if (dv_ensure_hw(ctx, radius)) return -1;
     uint8_t* d_mask = mask; int pitch = stride;
     if (mem != DV_MEM_DEVICE) {
         pitch = align_up(w, 16);

@@ -1,0 +1,369 @@
+// front_track.hip — the tracker's per-frame entries of the C ABI: dv_track_stereo_enqueue / _collect for one sequence, dv_batch_track_enqueue for a dv_batch group.
+// One frame = pyrDown x3 (stereo pair per launch) -> LK temporal -> compact/sort -> Shi-Tomasi tile -> select/append -> LK stereo -> finalize (<= max_cnt 128-byte
+// rows, written into pinned memory by the kernel).  Both entries take what the stages are given from ONE description of the frame (front_plan): the single entry
+// launches it by value with the single-sequence kernels, the group entry scatters it into the job tables of the _multi kernels.
+#include "dv_ctx.h"
+
+// What the stages of one raw-mode frame of one context are given, in the job types of the table kernels
+struct FrontPlan {
+    bool dev;                                  // the frames are device-addressable (DV_MEM_DEVICE, or pinned + mapped host memory)
+    PyrPlan pyr;                               // level 0, the level steps, the two pyramids of the apron stage, the number of levels
+    DvLkJob lk_temporal, lk_stereo;
+    DvCompactJob compact; GfttTileArgs tile; GfttSelectArgs select; DvFinalizeJob fin;
+};
+
+static int job_stride(const dv_track_job& j, int w) { return j.stride > 0 ? j.stride : w * ((j.mem & DV_FMT_BGR) ? 3 : 1); }
+
+// Everything a frame needs before its first launch: the member-level checks, the lazily created resources, the frames' way into level 0 (copies on s) and the
+// stages' arguments.  The frame is built in the pyramid the ctx is NOT looking at (cur ^ 1) and the ctx is not changed: front_commit does that, once the whole
+// enqueue has succeeded, so that a refused or failed enqueue of either kind leaves no flipped `cur` and no pending frame behind.
+static int front_plan(dv_ctx* ctx, const dv_track_job& j, hipStream_t s, FrontPlan& P) {
+    const dv_config& c = ctx->cfg;
+    const int w = c.width, h = c.height;
+    const bool stereo = c.stereo && j.gray1;
+    int mem = j.mem;
+    if ((mem & 0xff) == DV_MEM_PINNED) mem = (mem & ~0xff) | DV_MEM_DEVICE;      // pinned + mapped host memory is device-addressable: the kernels read it in place
+    if ((mem & 0xff) != DV_MEM_HOST && (mem & 0xff) != DV_MEM_DEVICE) DV_FAIL("dv_track_stereo: unknown memory kind");
+    if (ctx->undist[0]) {      // cfg::is_undistort_input.  (The size check cannot fire today — dv_set_undistort_maps / dv_undistort_setup take the config's size only — and is kept, once, because include/dvins.h promises it)
+        if (w != ctx->undist_w || h != ctx->undist_h) DV_FAIL("dv_track_stereo: undistortion maps were installed for another image size");
+        if (stereo && !ctx->undist[1]) DV_FAIL("dv_track_stereo: undistortion maps installed for camera 0 but not for camera 1");
+    }
+    P.dev = (mem & ~DV_FMT_BGR) == DV_MEM_DEVICE;
+    if (dv_ensure_hw(ctx, c.min_dist) || dv_ensure_cand(ctx, w, h)) return -1;
+    if (ctx->last_front && ctx->last_front != s && ctx->last_done) DV_CHECK(hipStreamWaitEvent(s, ctx->last_done, 0));      // the previous frame ran on the other front-end stream (its own / a dv_batch's)
+    PyrSet& L = ctx->left[ctx->cur ^ 1]; PyrSet& Lp = ctx->left[ctx->cur];
+    DV_CHECK(L.alloc(w, h, 3));
+    if (stereo) DV_CHECK(ctx->right.alloc(w, h, 3));
+    const DvPyr& a = L.pyr; const DvPyr& b = stereo ? ctx->right.pyr : a;
+    if (dv_plan_pyramids(ctx, a, stereo ? &b : nullptr, j.gray0, j.gray1, job_stride(j, w), mem, ctx->undist[0], s, P.pyr)) return -1;
+    const DvTrackState& tr = ctx->tr;
+    // temporal LK (a sequence's first frame has no previous pyramid: n_feat is 0, nothing is read), stereo LK
+    DvLkJob& t = P.lk_temporal; t = DvLkJob{}; t.A = ctx->have_prev ? Lp.pyr : a; t.B = a; t.pts_a = tr.last_pts; t.n_dev = tr.n_feat; t.pts_b = tr.lk_pts; t.status = tr.lk_status;
+    DvLkJob& r = P.lk_stereo; r = DvLkJob{}; r.A = a; r.B = b; r.pts_a = tr.curr_pts; r.n_dev = tr.n_feat; r.pts_b = tr.right_pts; r.status = tr.right_status;
+    P.compact = DvCompactJob{ tr, nullptr, 0, 1, ctx->n_cand, ctx->max_ord };
+    GfttTileArgs& g = P.tile; g = GfttTileArgs{};
+    g.img = a.L[0].p; g.w = w; g.h = h; g.pitch = a.L[0].pitch; g.in_mask = nullptr; g.mask_pitch = 0;
+    g.disc_pts = tr.curr_pts; g.n_disc = tr.n_tracked; g.radius = c.min_dist; g.hw = (const uint8_t*)ctx->hw_buf.p;
+    g.n_feat = tr.n_feat; g.max_cnt = c.max_cnt; g.min_new = 1; g.eig_out = nullptr; g.eig_pitch = 0;
+    g.cand = (DvCand*)ctx->cand_buf.p; g.cand_cap = ctx->cand_cap; g.n_cand = ctx->n_cand; g.max_ord = ctx->max_ord; g.rule = DV_GFTT_RULE_CPU;
+    GfttSelectArgs& q = P.select; q = GfttSelectArgs{};
+    q.cand = (const DvCand*)ctx->cand_buf.p; q.n_cand = ctx->n_cand; q.cand_cap = ctx->cand_cap; q.max_ord = ctx->max_ord;
+    q.w = w; q.h = h; q.quality = 0.01; q.min_dist = (double)c.min_dist; q.max_n_host = 0; q.n_feat = tr.n_feat; q.max_cnt = c.max_cnt; q.min_new = 1;
+    q.out_xy = nullptr; q.n_out = nullptr; q.tr = tr; q.has_tr = 1; q.err_flag = ctx->err_flag; q.rule = DV_GFTT_RULE_CPU;
+    // the rows, their count and the device error flags go straight into the pinned buffer (three copy dispatches behind the kernel before: ~20 us of the
+    // tracker's latency per frame)
+    DvFinalizeJob& f = P.fin; f = DvFinalizeJob{};
+    f.tr = tr; f.cam0 = c.cam0; f.cam1 = c.cam1; f.stereo = stereo ? 1 : 0; f.dt = j.t - ctx->prev_time; f.out = ctx->out_pinned; f.n_out = ctx->nout_pinned;
+    f.err_in = ctx->err_flag; f.err_out = ctx->err_pinned;
+    return 0;
+}
+
+// the planned frame is enqueued behind `done` on s: the ctx turns to the pyramid it was built in
+static void front_commit(dv_ctx* ctx, double t, hipEvent_t done, hipStream_t s) {
+    ctx->cur ^= 1; ctx->last_done = done; ctx->last_front = s;
+    ctx->prev_time = t; ctx->have_prev = true; ctx->pending = true;
+}
+
+extern "C" {
+
+int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gray1, int w, int h, int stride, double t,
+                            const uint8_t* mask_or_null, int mode, int mem) {
+    if (!ctx) return -1;
+    HostScope hs(ctx, "h_front_enqueue");
+    if (!gray0) DV_FAIL("dv_track_stereo: gray0 is null");
+    if (w != ctx->cfg.width || h != ctx->cfg.height) DV_FAIL("dv_track_stereo: image size differs from config (reference: std::terminate, main.cpp:95-99)");
+    if (ctx->pending) DV_FAIL("dv_track_stereo_enqueue: previous frame not collected");
+    if (mode != DV_MODE_RAW && mode != DV_MODE_NAIVE && mode != DV_MODE_SEMANTIC) DV_FAIL("dv_track_stereo: unknown mode");
+    DV_CHECK(hipSetDevice(ctx->cfg.device));
+    const dv_config& c = ctx->cfg;
+    const bool stereo = c.stereo && gray1;
+    hipStream_t s = ctx->stream;
+    const int cur = ctx->cur ^ 1;          // the pyramid slot of this frame: the ctx turns to it in front_commit
+    if (dv_inst_wait_before_next_frame(ctx)) DV_FAIL("dv_track_stereo: hipStreamWaitEvent");
+    StageScope frame(ctx, "frame");
+    FrontPlan P;
+    {
+        StageScope sc(ctx, "pyr");
+        const dv_track_job job{ 0, mem, gray0, gray1, stride, mode, t, mask_or_null };
+        if (front_plan(ctx, job, s, P)) return -1;
+        dv_launch_pyramids(P.pyr, s);
+        DV_CHECK(hipGetLastError());
+    }
+    // ---- what the plan of a raw-mode frame does not know: the object tracker's events, the mask, and the GPU tracker's / detector's rules of naive and semantic mode ----
+    const DvPyr& L = P.pyr.apron[0];
+    if (ctx->inst) DV_CHECK(hipEventRecord(ctx->ev_pyr, s));
+    // FeatureTrackByLKGpu's own pyramids where the reference runs that tracker (naive: TrackLeftGPU + TrackRightGPU; semantic: TrackRightGPU)
+    ctx->leftc_valid[cur] = false;
+    if (mode != DV_MODE_RAW) {
+        StageScope sc(ctx, "pyr_cuda");
+        if (dv_build_cuda_pyramids(ctx, ctx->leftc[cur], stereo ? &ctx->rightc : nullptr, L, stereo ? &ctx->right.pyr : nullptr, w, h, 3)) return -1;
+        ctx->leftc_valid[cur] = true;
+        if (mode == DV_MODE_NAIVE && ctx->have_prev && !ctx->leftc_valid[cur ^ 1]) {      // the previous frame was tracked in another mode: its pyramid of this flavour does not exist yet
+            if (dv_build_cuda_pyramids(ctx, ctx->leftc[cur ^ 1], nullptr, ctx->left[cur ^ 1].pyr, nullptr, w, h, 3)) return -1;
+            ctx->leftc_valid[cur ^ 1] = true;
+        }
+    }
+    const uint8_t* mask_dev = nullptr; int mask_pitch = 0;
+    if (mask_or_null) {
+        const bool bgr_in = (mem & DV_FMT_BGR) != 0;
+        if (P.dev) { mask_dev = mask_or_null; mask_pitch = bgr_in ? w : stride; }
+        else {
+            mask_pitch = align_up(w, 16);
+            DV_CHECK(ctx->mask_buf.ensure((size_t)mask_pitch * h));
+            DV_CHECK(hipMemcpy2DAsync(ctx->mask_buf.p, mask_pitch, mask_or_null, bgr_in ? w : stride, w, h, hipMemcpyHostToDevice, s));
+            mask_dev = (const uint8_t*)ctx->mask_buf.p;
+        }
+    }
+    if (!ctx->unmask.empty()) {          // system/main.cpp:217-245: the static instances' pixels leave the merged mask (inv_merge_mask = 255 there) before anything reads it
+        if (!mask_dev) { ctx->unmask.clear(); DV_FAIL("dv_track_unmask_static: the frame carries no mask"); }
+        if (mask_dev != (const uint8_t*)ctx->mask_buf.p) {          // the caller's device buffer is not written to: work on a copy
+            const int mp = align_up(w, 16);
+            DV_CHECK(ctx->mask_buf.ensure((size_t)mp * h));
+            DV_CHECK(hipMemcpy2DAsync(ctx->mask_buf.p, mp, mask_dev, mask_pitch, w, h, hipMemcpyDeviceToDevice, s));
+            mask_dev = (const uint8_t*)ctx->mask_buf.p; mask_pitch = mp;
+        }
+        for (const dv_ctx::UnmaskJob& j : ctx->unmask)
+            dv_launch_unmask((uint8_t*)ctx->mask_buf.p, mask_pitch, w, h, j.x, j.y, j.w, j.h, (const uint8_t*)ctx->unmask_pinned + j.off, s);
+        ctx->unmask.clear();
+    }
+    const bool naive = (mode != DV_MODE_RAW);            // naive and semantic share the InstFeat code path (mask test, no sort, >= 10 new)
+    if (naive && mask_dev && c.mask_morphology_size > 0) {       // ErodeMask (background_tracker.cpp:408-416,764-768)
+        const int ep = align_up(w, 16);
+        DV_CHECK(ctx->s3.ensure((size_t)ep * h)); DV_CHECK(ctx->s4.ensure((size_t)ep * h));
+        dv_launch_erode(mask_dev, w, h, mask_pitch, c.mask_morphology_size, (uint8_t*)ctx->s3.p, ep, (uint8_t*)ctx->s4.p, ep, s);
+        mask_dev = (const uint8_t*)ctx->s4.p; mask_pitch = ep;
+    }
+    // forward/backward consistency: FeatureTrackByLK keeps <= 0.5 px (feature_utils.cpp:56), FeatureTrackByLKGpu <= 1.0 px (:126) (Q12) — and the two are different
+    // trackers (lk.hip / lk_cuda.hip), each used where the reference uses it
+    const float dist_temporal = (mode == DV_MODE_NAIVE) ? 1.0f : 0.5f;       // TrackLeftGPU (naive) vs TrackLeft (raw, semantic)
+    const float dist_stereo = (mode == DV_MODE_RAW) ? 0.5f : 1.0f;           // TrackRightGPU in naive and semantic
+    if (ctx->have_prev) {
+        StageScope sc(ctx, "lk_temporal");
+        const DvLkJob& k = P.lk_temporal;
+        if (mode == DV_MODE_NAIVE)      // TrackLeftGPU -> FeatureTrackByLKGpu (instance_feature.cpp:191-216): the GPU tracker's rule
+            dv_launch_lk_cuda_track(ctx->leftc[cur ^ 1].pyr, ctx->leftc[cur].pyr, k.pts_a, k.n_dev, c.max_cnt, c.flow_back, dist_temporal, k.pts_b, k.status, s);
+        else
+            dv_launch_lk_track(k.A, k.B, k.pts_a, k.n_dev, c.max_cnt, c.flow_back, dist_temporal, k.pts_b, k.status, s, ctx->tr.lk_order);
+    }
+    {
+        StageScope sc(ctx, "compact");
+        DvCompactJob& k = P.compact;
+        k.mask_pitch = mask_pitch;
+        if (naive) { k.in_mask = mask_dev; k.sort_by_cnt = 0; }
+        dv_launch_compact(k.tr, k.in_mask, k.mask_pitch, k.sort_by_cnt, k.n_cand, k.max_ord, s);
+    }
+    const int min_new = naive ? 10 : 1;                   // Q23: instance_feature.cpp:353-356 vs background_tracker.cpp:82-90
+    // DetectNewFeature(img, use_gpu, ...): TrackImageNaive passes true (background_tracker.cpp:445) -> DetectShiTomasiCornersGpu (feature_utils.cpp:339-348),
+    // TrackSemanticImage passes false (:789) and TrackImage calls cv::goodFeaturesToTrack itself (:85)
+    const int gftt_rule = (mode == DV_MODE_NAIVE) ? DV_GFTT_RULE_CUDA : DV_GFTT_RULE_CPU;
+    {
+        StageScope sc(ctx, "gftt_eig");
+        P.tile.in_mask = mask_dev; P.tile.mask_pitch = mask_pitch; P.tile.min_new = min_new; P.tile.rule = gftt_rule;
+        dv_launch_gftt_tile(P.tile, s);
+    }
+    {
+        StageScope sc(ctx, "gftt_select");
+        P.select.min_new = min_new; P.select.rule = gftt_rule;
+        if (dv_launch_gftt_select(P.select, s)) DV_FAIL("gftt_select: cannot set dynamic LDS size");
+    }
+    if (ctx->inst) DV_CHECK(hipEventRecord(ctx->ev_bg_select, s));
+    if (stereo) {
+        StageScope sc(ctx, "lk_stereo");
+        const DvLkJob& k = P.lk_stereo;
+        if (mode != DV_MODE_RAW)        // TrackRightGPU -> FeatureTrackByLKGpu (instance_feature.cpp:278-310) in naive and semantic mode
+            dv_launch_lk_cuda_track(ctx->leftc[cur].pyr, ctx->rightc.pyr, k.pts_a, k.n_dev, c.max_cnt, c.flow_back, dist_stereo, k.pts_b, k.status, s);
+        else
+            dv_launch_lk_track(k.A, k.B, k.pts_a, k.n_dev, c.max_cnt, c.flow_back, dist_stereo, k.pts_b, k.status, s, ctx->tr.lk_order);
+    }
+    {
+        StageScope sc(ctx, "finalize");
+        const DvFinalizeJob& k = P.fin;
+        dv_launch_finalize(k.tr, k.cam0, k.cam1, k.stereo, k.dt, c.max_cnt, k.out, k.n_out, s, k.err_in, k.err_out);
+    }
+    DV_CHECK(hipGetLastError());
+    DV_CHECK(hipEventRecord(ctx->done, s));
+    front_commit(ctx, t, ctx->done, s);
+    return 0;
+}
+
+int dv_track_unmask_static(dv_ctx* ctx, const dv_inst_det* dets, int n_dets, const uint32_t* static_ids, int n_static) {
+    if (!ctx) return -1;
+    ctx->unmask.clear();
+    if (n_static <= 0 || n_dets <= 0) return 0;
+    if (!dets || !static_ids) DV_FAIL("dv_track_unmask_static: null argument");
+    if (ctx->pending) DV_FAIL("dv_track_unmask_static: call it before dv_track_stereo_enqueue of the frame it belongs to");
+    size_t need = 0;
+    for (int i = 0; i < n_dets; ++i) if (std::find(static_ids, static_ids + n_static, dets[i].track_id) != static_ids + n_static) need += ((size_t)dets[i].w * dets[i].h + 15) / 16 * 16;
+    if (!need) return 0;
+    if (ctx->unmask_pinned_bytes < need) {
+        DV_CHECK(hipStreamSynchronize(ctx->stream));          // (a previous frame's kernels may still read the old staging area)
+        if (ctx->unmask_pinned) (void)hipHostFree(ctx->unmask_pinned);
+        ctx->unmask_pinned = nullptr; ctx->unmask_pinned_bytes = 0;
+        const size_t want = std::max<size_t>(2 * need, (size_t)ctx->cfg.width * ctx->cfg.height);      // (a frame's worth from the start: the rectangles grow as objects come closer)
+        DV_CHECK(hipHostMalloc(&ctx->unmask_pinned, want, hipHostMallocDefault));
+        ctx->unmask_pinned_bytes = want;
+    } else if (ctx->last_done && ctx->last_done == ctx->done) DV_CHECK(hipEventSynchronize(ctx->done));      // the previous frame's unmask kernels have read the staging area (a no-op wait in the usual case: that frame was collected)
+    size_t off = 0;
+    for (int i = 0; i < n_dets; ++i) {
+        const dv_inst_det& d = dets[i];
+        if (std::find(static_ids, static_ids + n_static, d.track_id) == static_ids + n_static) continue;
+        if (!d.mask || d.w <= 0 || d.h <= 0 || d.x < 0 || d.y < 0 || d.x + d.w > ctx->cfg.width || d.y + d.h > ctx->cfg.height) { ctx->unmask.clear(); DV_FAIL("dv_track_unmask_static: bad detection rectangle / mask"); }
+        std::memcpy((uint8_t*)ctx->unmask_pinned + off, d.mask, (size_t)d.w * d.h);
+        ctx->unmask.push_back({ d.x, d.y, d.w, d.h, off });
+        off += ((size_t)d.w * d.h + 15) / 16 * 16;
+    }
+    return 0;
+}
+
+int dv_track_stereo_collect(dv_ctx* ctx, dv_feat* out, int* n_out) {
+    if (!ctx) return -1;
+    if (!ctx->pending) DV_FAIL("dv_track_stereo_collect: nothing enqueued");
+    { HostScope hs(ctx, "h_front_wait"); DV_CHECK(hipEventSynchronize(ctx->last_done ? ctx->last_done : ctx->done)); }
+    ctx->pending = false;
+    if (ctx->timing) dv_harvest_timers(ctx, ctx->stream);
+    if (*ctx->err_pinned) {
+        int f = *ctx->err_pinned;
+        DV_CHECK(hipMemsetAsync(ctx->err_flag, 0, 4, ctx->stream));
+        DV_FAIL(std::string("front end device error flags=") + std::to_string(f) +
+                " (1: candidate buffer overflow, 2: min-distance grid too large, 4: value bin overflow)");
+    }
+    const int n = *ctx->nout_pinned;
+    if (n_out) *n_out = n;
+    if (out && n > 0) std::memcpy(out, ctx->out_pinned, (size_t)n * sizeof(dv_feat));
+    return 0;
+}
+
+int dv_track_stereo(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gray1, int w, int h, int stride, double t,
+                    const uint8_t* mask_or_null, int mode, int mem, dv_feat* out, int* n_out) {
+    if (dv_track_stereo_enqueue(ctx, gray0, gray1, w, h, stride, t, mask_or_null, mode, mem)) return -1;
+    return dv_track_stereo_collect(ctx, out, n_out);
+}
+
+}  // extern "C"
+
+// ------------------------------- the front ends of a dv_batch group in shared launches -------------------------------
+// FeatureTracker::TrackImage (background_tracker.cpp:52-158) of S independent sequences, one launch per STAGE for all of them (the reference runs one process per
+// sequence, system/main.cpp:178-330): pyrDown levels 1..3 (level 1 also writes the pitched level-0 copy), aprons, temporal LK, compaction / sort, Shi-Tomasi tile,
+// corner selection, stereo LK, rows = 10 launches per group and frame instead of 10 per sequence.  The kernels are the single-sequence kernels' bodies behind a
+// job table in HBM (blockIdx.z / .y / .x = member), so every member's rows are bit-identical to what its own dv_track_stereo_enqueue produces.
+// Members with undistortion maps (cfg::is_undistort_input) or BGR frames differ in level 0 alone: one more launch (level0_multi_kernel, pyramid.hip) fills it for all
+// of them, each through its own maps, and level 1 then reads it; a round without such a member does not launch it.
+struct DvFrontBatch {
+    hipStream_t stream = nullptr; hipEvent_t done = nullptr, ev_copy[2] = { nullptr, nullptr };
+    DevBuf tab[2]; void* tab_pinned[2] = { nullptr, nullptr }; size_t tab_bytes = 0; int parity = 0; bool copy_used[2] = { false, false };
+    long long rounds = 0, members_batched = 0, members_single = 0;
+};
+void dv_front_batch_sync(DvFrontBatch* F) { if (F && F->stream) (void)hipStreamSynchronize(F->stream); }      // be_batch_detach: a member leaves while one of its frames may be in flight on the group's front-end stream
+void dv_front_batch_release(DvFrontBatch* F) {
+    if (!F) return;
+    if (F->stream) { (void)hipStreamSynchronize(F->stream); (void)hipStreamDestroy(F->stream); }
+    if (F->done) (void)hipEventDestroy(F->done);
+    for (int k = 0; k < 2; ++k) { if (F->ev_copy[k]) (void)hipEventDestroy(F->ev_copy[k]); F->tab[k].release(); if (F->tab_pinned[k]) (void)hipHostFree(F->tab_pinned[k]); }
+    delete F;
+}
+
+extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int n) {
+    if (!B || (n > 0 && !jobs) || n < 0) { dv_set_error(nullptr, "dv_batch_track_enqueue: bad arguments"); return -1; }
+    const std::vector<dv_ctx*>& mem = be_batch_members(B);
+    if (n == 0 || mem.empty()) return 0;
+    dv_ctx* ctx = mem[0];                                       // errors of the shared part are reported on the first member (and the global slot)
+    DV_CHECK(hipSetDevice(ctx->cfg.device));
+    DvFrontBatch*& Fp = be_batch_front(B);
+    if (!Fp) {
+        Fp = new DvFrontBatch();
+        DV_CHECK((std::getenv("DVINS_CU_PARTITION_FRONT") || std::getenv("DVINS_SOLVE_CUS")) ? dv_group_stream_create(&Fp->stream, be_batch_index(B)) : hipStreamCreateWithFlags(&Fp->stream, hipStreamNonBlocking));
+        DV_CHECK(hipEventCreateWithFlags(&Fp->done, hipEventDisableTiming));
+        for (int k = 0; k < 2; ++k) DV_CHECK(hipEventCreateWithFlags(&Fp->ev_copy[k], hipEventDisableTiming));
+    }
+    DvFrontBatch& F = *Fp;
+    // ---- which jobs can share launches: raw mode, no mask, no object tracker, the group's common geometry (gray or BGR frames, with or without the member's own
+    //      undistortion maps: those differ in how level 0 is filled and in nothing behind it) ----
+    std::vector<int> M;                                         // job indices that are batched
+    const dv_config* ref = nullptr;
+    for (int i = 0; i < n; ++i) {
+        const dv_track_job& j = jobs[i];
+        if (j.member < 0 || j.member >= (int)mem.size()) DV_FAIL("dv_batch_track_enqueue: member index out of range");
+        dv_ctx* c = mem[j.member];
+        for (int q = 0; q < i; ++q) if (jobs[q].member == j.member) DV_FAIL("dv_batch_track_enqueue: a member appears twice");
+        const bool plain = j.mode == DV_MODE_RAW && !j.mask && !c->inst && !c->timing && j.gray0 && (!c->cfg.stereo || j.gray1);
+        const bool same = !ref || (c->cfg.width == ref->width && c->cfg.height == ref->height && c->cfg.stereo == ref->stereo && c->cfg.flow_back == ref->flow_back);
+        if (plain && same) { if (!ref) ref = &c->cfg; M.push_back(i); }
+        else {      // its own launches on its own stream (ordered behind whatever the batch stream still holds for it: dv_track_stereo_enqueue)
+            if (dv_track_stereo_enqueue(c, j.gray0, j.gray1, c->cfg.width, c->cfg.height, job_stride(j, c->cfg.width), j.t, j.mask, j.mode, j.mem)) { dv_set_error(ctx, c->err); return -1; }
+            F.members_single++;
+        }
+    }
+    const int S = (int)M.size();
+    if (S == 0) return 0;
+    if (S == 1) {      // nothing to share
+        const dv_track_job& j = jobs[M[0]]; dv_ctx* c = mem[j.member];
+        if (dv_track_stereo_enqueue(c, j.gray0, j.gray1, c->cfg.width, c->cfg.height, job_stride(j, c->cfg.width), j.t, nullptr, DV_MODE_RAW, j.mem)) { dv_set_error(ctx, c->err); return -1; }
+        F.members_single++;
+        return 0;
+    }
+    const int w = ref->width, h = ref->height; const bool stereo = ref->stereo != 0;
+    hipStream_t s = F.stream;
+    // ---- the job tables of the round: one pinned block, one upload ----
+    const size_t o_pyr = 0, o_apr = o_pyr + (size_t)3 * S * sizeof(DvPyrJob), o_lk = (o_apr + (size_t)2 * S * sizeof(DvPyr) + 255) / 256 * 256,
+                 o_cmp = (o_lk + (size_t)2 * S * sizeof(DvLkJob) + 255) / 256 * 256, o_gt = (o_cmp + (size_t)S * sizeof(DvCompactJob) + 255) / 256 * 256,
+                 o_gs = (o_gt + (size_t)S * sizeof(GfttTileArgs) + 255) / 256 * 256, o_fin = (o_gs + (size_t)S * sizeof(GfttSelectArgs) + 255) / 256 * 256,
+                 o_l0 = (o_fin + (size_t)S * sizeof(DvFinalizeJob) + 255) / 256 * 256, total = (o_l0 + (size_t)S * sizeof(DvLevel0Job) + 255) / 256 * 256;
+    const int par = F.parity; F.parity ^= 1;
+    if (F.copy_used[par]) DV_CHECK(hipEventSynchronize(F.ev_copy[par]));      // the upload that last read this pinned block (two rounds ago) has run
+    if (F.tab_bytes < total) {
+        DV_CHECK(hipStreamSynchronize(s));
+        const size_t cap = total * 2;
+        for (int k = 0; k < 2; ++k) {
+            DV_CHECK(F.tab[k].ensure(cap));
+            if (F.tab_pinned[k]) (void)hipHostFree(F.tab_pinned[k]);
+            F.tab_pinned[k] = nullptr;
+            DV_CHECK(hipHostMalloc(&F.tab_pinned[k], cap, hipHostMallocDefault));
+        }
+        F.tab_bytes = cap;
+    }
+    uint8_t* hp = (uint8_t*)F.tab_pinned[par]; const uint8_t* dp = (const uint8_t*)F.tab[par].p;
+    DvPyrJob* h_pyr = (DvPyrJob*)(hp + o_pyr); DvPyr* h_apr = (DvPyr*)(hp + o_apr); DvLkJob* h_lk = (DvLkJob*)(hp + o_lk); DvCompactJob* h_cmp = (DvCompactJob*)(hp + o_cmp);
+    GfttTileArgs* h_gt = (GfttTileArgs*)(hp + o_gt); GfttSelectArgs* h_gs = (GfttSelectArgs*)(hp + o_gs); DvFinalizeJob* h_fin = (DvFinalizeJob*)(hp + o_fin);
+    DvLevel0Job* h_l0 = (DvLevel0Job*)(hp + o_l0); int n_l0 = 0;      // only the members whose level 0 is not a copy of the frame: none in an all-plain round, and no launch then
+    // ---- per member: its plan of the frame, scattered into the tables.  (No ctx changes before the commit below: a member's refusal, a failed upload or LDS
+    //      attribute leave no member with a flipped current pyramid or a pending frame) ----
+    int n_max = 0, levels = 0, lw[DV_MAX_LEVELS] = { 0 }, lh[DV_MAX_LEVELS] = { 0 };
+    FrontPlan P;
+    for (int k = 0; k < S; ++k) {
+        const dv_track_job& j = jobs[M[k]]; dv_ctx* c = mem[j.member];
+        if (c->pending) { dv_set_error(ctx, "dv_batch_track_enqueue: a member's previous frame was not collected"); return -1; }
+        if (front_plan(c, j, s, P)) { dv_set_error(ctx, c->err); return -1; }      // (with dv_track_stereo's text, on the member and on the first one)
+        if (P.pyr.has_l0) h_l0[n_l0++] = P.pyr.l0;
+        levels = P.pyr.levels;
+        for (int l = 1; l < levels; ++l) { h_pyr[(size_t)(l - 1) * S + k] = P.pyr.down[l - 1]; lw[l] = P.pyr.down[l - 1].dw; lh[l] = P.pyr.down[l - 1].dh; }
+        h_apr[2 * k] = P.pyr.apron[0]; h_apr[2 * k + 1] = P.pyr.apron[1];
+        h_lk[k] = P.lk_temporal; h_lk[S + k] = P.lk_stereo;
+        h_cmp[k] = P.compact; h_gt[k] = P.tile; h_gs[k] = P.select; h_fin[k] = P.fin;
+        n_max = std::max(n_max, c->cfg.max_cnt);
+    }
+    DV_CHECK(dv_copy_async(F.tab[par].p, hp, total, s));
+    DV_CHECK(hipEventRecord(F.ev_copy[par], s)); F.copy_used[par] = true;
+    // ---- the stages ----
+    if (n_l0) dv_launch_level0_multi((const DvLevel0Job*)(dp + o_l0), n_l0, w, h, s);
+    for (int l = 1; l < levels; ++l) dv_launch_pyr_down_multi((const DvPyrJob*)(dp + o_pyr) + (size_t)(l - 1) * S, S, lw[l], lh[l], s);
+    dv_launch_pyr_apron_multi((const DvPyr*)(dp + o_apr), 2 * S, levels, s);
+    dv_launch_lk_track_multi((const DvLkJob*)(dp + o_lk), S, n_max, ref->flow_back, 0.5f, s);
+    dv_launch_compact_multi((const DvCompactJob*)(dp + o_cmp), S, s);
+    dv_launch_gftt_tile_multi((const GfttTileArgs*)(dp + o_gt), S, w, h, s);
+    if (dv_launch_gftt_select_multi((const GfttSelectArgs*)(dp + o_gs), S, s)) DV_FAIL("gftt_select: cannot set dynamic LDS size");
+    if (stereo) dv_launch_lk_track_multi((const DvLkJob*)(dp + o_lk) + S, S, n_max, ref->flow_back, 0.5f, s);
+    dv_launch_finalize_multi((const DvFinalizeJob*)(dp + o_fin), S, n_max, s);
+    DV_CHECK(hipGetLastError());
+    DV_CHECK(hipEventRecord(F.done, s));
+    for (int i : M) front_commit(mem[jobs[i].member], jobs[i].t, F.done, s);
+    F.rounds++; F.members_batched += S;
+    return 0;
+}
+extern "C" int dv_batch_track_info(dv_batch* B, long long* rounds, long long* members_batched, long long* members_single) {
+    if (!B) return -1;
+    DvFrontBatch* F = be_batch_front(B);
+    if (rounds) *rounds = F ? F->rounds : 0;
+    if (members_batched) *members_batched = F ? F->members_batched : 0;
+    if (members_single) *members_single = F ? F->members_single : 0;
+    return 0;
+}

@@ -230,6 +230,87 @@ def test_failed_round_leaves_no_wreckage(gpu_ctx_factory):
     batch.close()
 
 
+def test_unknown_memory_kind_fails_the_round_and_leaves_no_wreckage(gpu_ctx_factory):
+    """160 x 120 stereo, two members: a job with memory kind 7 makes the round fail with exactly the text a lone context gives for track_stereo(..., mem=7); nothing
+    is pending on either member, and the following rounds give the rows of twins that never saw the bad round"""
+    import torch
+    from dynamic_vins_amd.backend import Batch
+    from dynamic_vins_amd.frontend import DvinsError
+    w, h = 160, 120
+    kw = dict(max_cnt=40, min_dist=10)
+    members = [Member(gpu_ctx_factory, w, h, 51, **kw), Member(gpu_ctx_factory, w, h, 52, **kw)]
+    lone = gpu_ctx_factory(width=w, height=h, cam0=_cam(EUROC0, w, h), cam1=_cam(EUROC1, w, h), **kw)
+    l, r = members[1].seq.frame(0)
+    with pytest.raises(DvinsError) as single_err:
+        lone.track_stereo(l, r, 0.0, mem=7)
+    assert "memory kind" in str(single_err.value)
+    batch = Batch([m.batched for m in members])
+
+    def good_round(f):
+        want, jobs = {}, []
+        for i, m in enumerate(members):
+            want[i], job = m.step(i, f, 0.05 * f)
+            jobs.append(job)
+        torch.cuda.synchronize()
+        batch.track_enqueue(jobs)
+        for i in want:
+            got = members[i].batched.track_stereo_collect()
+            assert len(got) > 20 and got.tobytes() == want[i].tobytes(), f"frame {f}, member {i}"
+
+    good_round(0)
+    good_round(1)
+    # the bad round: frame 2 for both, member 1's job with a memory kind that does not exist.  The twins do not see it.
+    jobs, keep = [], []
+    for i, m in enumerate(members):
+        fl, fr = m.frame(2)
+        dl, dr = torch.from_numpy(fl).cuda(), torch.from_numpy(fr).cuda()
+        keep += [dl, dr]
+        jobs.append(dict(member=i, gray0=dl.data_ptr(), gray1=dr.data_ptr(), t=0.1, mem=7 if i == 1 else m.mem_job))
+    torch.cuda.synchronize()
+    with pytest.raises(DvinsError) as batch_err:
+        batch.track_enqueue(jobs)
+    assert str(batch_err.value) == str(single_err.value)
+    for m in members:      # nothing is pending on either member
+        with pytest.raises(DvinsError):
+            m.batched.track_stereo_collect()
+    for f in (2, 3):
+        good_round(f)
+    info = batch.track_info()
+    assert info["members_batched"] == 8 and info["members_single"] == 0, info
+    batch.close()
+
+
+def test_refused_single_enqueue_leaves_the_context_as_it_was(gpu_ctx_factory):
+    """160 x 120 stereo, one context and its twin, both with the same maps for both cameras.  After two frames the context loses its camera 1 maps and has
+    track_stereo refused; with the maps back, its next frames' rows equal the twin's, which never saw the refused call: the refusal did not turn the context to the
+    other pyramid (the temporal LK of the next frame would start from the frame before last)"""
+    from dynamic_vins_amd.frontend import DvinsError
+    w, h = 160, 120
+    m = Member(gpu_ctx_factory, w, h, 61, maps=0.0, max_cnt=40, min_dist=10)
+    ctx, twin = m.batched, m.twin
+    maps0, maps1 = ctx.undistort_maps(0), ctx.undistort_maps(1)
+    for c in (ctx, twin):      # own maps (same values) on both: the cameras the rows are lifted with stay alike when camera 1's maps go and come back
+        c.set_undistort_maps(0, *maps0); c.set_undistort_maps(1, *maps1)
+
+    def good_frame(f):
+        l, r = m.frame(f)
+        got, want = ctx.track_stereo(l, r, 0.05 * f), twin.track_stereo(l, r, 0.05 * f)
+        assert len(got) > 20 and got.tobytes() == want.tobytes(), f"frame {f}"
+
+    good_frame(0)
+    good_frame(1)
+    ctx.set_undistort_maps(1)
+    l, r = m.frame(2)
+    with pytest.raises(DvinsError) as err:
+        ctx.track_stereo(l, r, 0.1)
+    assert "camera 1" in str(err.value)
+    with pytest.raises(DvinsError):      # nothing is pending
+        ctx.track_stereo_collect()
+    ctx.set_undistort_maps(1, *maps1)
+    good_frame(2)
+    good_frame(3)
+
+
 def test_runner_group_of_undistorted_members_shares_the_front_end():
     """Runner over three Pipeline(undistort_input=True) members in one group: the shared front end (default) against `batch_front` 0 — states, trajectories and row
     counts bit for bit, and the members are counted as batched"""
