@@ -97,7 +97,7 @@ struct BeMargArgs {
     double* outA; double* outb; double* out_scalars;     // n x n, n, {c0, min pivot, failure flag, rank}
     double* W; double* part; double* psum;                // be_marg_lm -> be_marg_sum: w_l | g_l | 1 / h_l per landmark [nlm][be_marg_wstride(D)]; structured block sums per landmark chunk [chunks][be_marg_part()]; their sum over chunks
     int pose_dim[BE_NF], ex_dim[2], td_dim;               // first dim of each block in the system, -1 = absent (what dim_slot / dim_comp tabulate)
-    int c0_mode;                                           // be_marg_finish: 0 everything; 1 all but c0 (A', b', pivot health); 2 c0 only, from A', b' in outA / outb (the side-stream launch)
+    int c0_mode;                                           // be_marg_finish: 0 everything; 1 all but c0 (A', b', pivot health: DV_MARG_EIGEN, whose c0 comes from be_marg_eig)
     double* sum; double* lm_h; int anchor;                // A_lm | b_lm dense (D*D + D); per-landmark h; the frame the landmarks are anchored in (= the dropped one)
     double* imu_w;                // [465] whitened Jacobian (15 x 30) and residual (15) of the IMU factor (0,1): written by the extra block of be_marg_lm, read by be_marg_finish
     double* c0_out;               // optional second home of c0 (the device-resident prior of the estimator)
@@ -212,7 +212,7 @@ __device__ __forceinline__ void be_accept_body(const BeSolveArgs& a) {
 
 #endif
 
-// Iteration schedule (be_api.hip): the classic slot is  eval(x) -> reduce -> solve -> eval-cost(cand) -> accept.  The speculative slot
+// Iteration schedule (be_host.h: be_run_slots): the classic slot is  eval(x) -> reduce -> solve -> eval-cost(cand) -> accept.  The speculative slot
 // linearises AT THE CANDIDATE instead (full evaluation + reduce into the other set, with the mu an accepted step would leave) and lets the
 // next solve kernel take the accept / reject decision in its prologue: 3 launches per iteration instead of 5, and an accepted step
 // (the common case) finds its reduced system ready.  A rejected step costs one wasted reduce.
@@ -223,7 +223,6 @@ void be_launch_eval(const BeEvalArgs& a, int mode, hipStream_t s);
 int  be_launch_marg(const BeMargArgs& a, hipStream_t s);
 int  dv_warm_stream(hipStream_t s);      // copy.hip: one dispatch with ~150 B of scratch per lane (the queue's scratch memory is allocated at create time, not at the first window solve)
 int  be_eval_prepare(); int be_solve_prepare(); int be_marg_prepare(); int dv_copy_prepare();      // load the code objects / set the LDS attributes at create time (be_prepare)
-int  be_launch_marg_c0(const BeMargArgs& a, hipStream_t s);      // the c0 = b'^T A'^+ b' part alone (BeMargArgs::c0_mode is set to 2)
 // DV_MARG_EIGEN (be_marg_eig.hip): A', b' of be_marg_finish (run with c0_mode = 1) eigen-decomposed in place into the reference's clamped form, c0 and the rank of J0
 struct BeMargEigArgs {
     double* A; double* b;         // n x n, n: in = A', b' of be_marg_finish, out = the eigen-clamped A'_c, b'_c
@@ -245,11 +244,10 @@ int  be_launch_solve(const BeSolveArgs& a, int spec, hipStream_t s);        // s
 void be_launch_accept(const BeSolveArgs& a, hipStream_t s);
 void be_launch_eval_ext(const BeEvalArgs& a, const BeExt& xt, int mode, hipStream_t s);      // behind be_launch_eval (full modes only)
 void be_launch_reduce_ext(const BeSolveArgs& a, int spec, hipStream_t s);                    // behind be_launch_reduce
-// batched forms: n_win independent windows per launch (argument tables in HBM, window index in the grid); be_api.hip enqueues them for a dv_batch
+// batched forms: n_win independent windows per launch (argument tables in HBM, window index in the grid); be_batch.hip enqueues them for a dv_batch
 void be_launch_eval_batch(const BeEvalArgs* tab_dev, int n_win, int max_grid, int mode, hipStream_t s);
 void be_launch_reduce_batch(const BeSolveArgs* tab_dev, int n_win, int max_n, int spec, hipStream_t s);
 int  be_launch_solve_batch(const BeSolveArgs* tab_dev, int n_win, int max_n, int spec, hipStream_t s);      // every window on the MF16 form
-void be_launch_accept_batch(const BeSolveArgs* tab_dev, int n_win, hipStream_t s);
 int be_eval_batch_blocks(int nlm, int nimu);      // workgroups of one window in the batched evaluation launch
 void be_launch_accept_gauge_batch(const BeSolveArgs* stab, const BeGaugeArgs* gtab, int n, hipStream_t s);
 void be_launch_reject_batch(const BeRejectArgs* tab, int n, int max_nlm, hipStream_t s);

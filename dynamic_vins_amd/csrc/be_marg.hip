@@ -369,11 +369,7 @@ __device__ __forceinline__ void be_marg_finish_body(const BeMargArgs& a) {
     double* imu_ws = misc + 16;                           // 960: raw / whitened Jacobian and residual of the IMU factor (its own region: prepared beside the phases below)
     const BeState* st = a.x;
     MTS(8);
-    if (a.c0_mode == 2) {                               // side-stream launch: A', b' come back from global memory, then straight to the c0 factorisation
-        for (int e = tid; e < n * n; e += MG_THREADS) W2[e] = a.outA[e];
-        for (int i = tid; i < n; i += MG_THREADS) yv[i] = a.outb[i];
-        __syncthreads();
-    } else {
+    {
     // The last wave takes no share of the assembly below: it fetches the whitened IMU factor (0,1) that the extra block of be_marg_lm has prepared (the raw
     // evaluation on ONE lane and the whitening used to be a 9 us phase of this kernel, behind the prior).
     const int MGW = MG_THREADS - 64;                      // worker threads of the assembly
@@ -630,7 +626,7 @@ __device__ __forceinline__ void be_marg_finish_body(const BeMargArgs& a) {
     MTS(14);
     for (int e = tid; e < n * n; e += MG_THREADS) a.outA[e] = W2[e];
     for (int i = tid; i < n; i += MG_THREADS) a.outb[i] = yv[i];
-    if (a.c0_mode == 1) {                               // c0 follows on a side stream (be_launch_marg_c0): the new prior's A', b' are what the BA stream waits for
+    if (a.c0_mode == 1) {                               // c0 comes from be_marg_eig behind this kernel (DV_MARG_EIGEN): A', b' and the pivot health are all it leaves
         if (tid == 0) { a.out_scalars[1] = misc[0]; a.out_scalars[2] = misc[1]; }
         return;
     }
@@ -696,7 +692,7 @@ __device__ __forceinline__ void be_marg_finish_body(const BeMargArgs& a) {
     MTS(16);
     if (tid == 0) {
         a.out_scalars[0] = c0; a.out_scalars[3] = (double)rank; if (a.c0_out) a.c0_out[0] = c0;
-        if (a.c0_mode != 2) { a.out_scalars[1] = misc[0]; a.out_scalars[2] = misc[1]; }
+        a.out_scalars[1] = misc[0]; a.out_scalars[2] = misc[1];
     }
 }
 __global__ __launch_bounds__(MG_THREADS) void be_marg_finish_kernel(BeMargArgs a) { be_marg_finish_body(a); }
@@ -827,11 +823,6 @@ int be_marg_chunks(int nlm) { return (nlm + MG_CH - 1) / MG_CH; }
 int be_marg_part() { return MG_PART; }
 int be_marg_wstride(int D) { return mg_wstride(D); }
 
-int be_launch_marg_c0(const BeMargArgs& a0, hipStream_t s) {
-    BeMargArgs a = a0; a.c0_mode = 2;
-    hipLaunchKernelGGL(be_marg_finish_kernel, dim3(1), dim3(MG_THREADS), finish_smem(a.D, a.D - a.m), s, a);
-    return 0;
-}
 // the frame tails of a dv_batch group: accept + gauge + download, outlier test, (caller records its event), then the three marginalization stages
 void be_launch_accept_gauge_batch(const BeSolveArgs* stab, const BeGaugeArgs* gtab, int n, hipStream_t s) { hipLaunchKernelGGL(be_accept_gauge_batch_kernel, dim3(n), dim3(256), 0, s, stab, gtab); }
 void be_launch_reject_batch(const BeRejectArgs* tab, int n, int max_nlm, hipStream_t s) { if (max_nlm > 0) hipLaunchKernelGGL(be_reject_batch_kernel, dim3((max_nlm + REJ_LM - 1) / REJ_LM, n), dim3(256), 0, s, tab); }

@@ -14,7 +14,7 @@
 //   phase B  every off-diagonal 2 x 2 block (pair i, pair j), i < j, becomes R_i^T B R_j (mirrored: A stays bitwise symmetric), V becomes V J.
 // A sweep is N - 1 steps; before each sweep off = sum_{i<j} a_ij^2 and diag = sum a_ii^2 are reduced in a fixed order and the oracle's test
 // off <= 1e-30 (diag + 1e-300) ends the iteration.  30 sweeps without convergence is a failure: out_scalars[3] (the rank) becomes -1 and the
-// host refuses the result (be_api.hip).  Schedule and reductions are fixed, so the result is bitwise reproducible.
+// host refuses the result (be_marg_host.hip).  Schedule and reductions are fixed, so the result is bitwise reproducible.
 //
 // Out of scope: the reference's pseudo-inverse of a rank-deficient A_mm (a dense eigen-decomposition of 15 + L columns does not fit one
 // workgroup).  be_marg_finish keeps eliminating A_mm with its LDL^T and reports the smallest pivot and the clamp flag (out_scalars[1], [2];

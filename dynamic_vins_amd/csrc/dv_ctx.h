@@ -107,7 +107,6 @@ struct BeWork {
     double* priorA_buf[2] = { nullptr, nullptr }; double* priorb_buf[2] = { nullptr, nullptr }; int prior_cur = 0;      // double-buffered prior (A', b')
     bool prior_resident = false;      // true: buffer prior_cur holds the estimator's current prior (written by the fused marginalization)
     hipEvent_t ev_state = nullptr;    // recorded behind the download of the solved states (the marginalization runs on past it)
-    hipStream_t c0_stream = nullptr; hipEvent_t ev_margA = nullptr, ev_c0 = nullptr; bool c0_side = false, c0_pending = false;     // dv_debug_set "c0_side": the prior's constant c0 on a side stream (be_api.hip marg_enqueue); measured SLOWER (969-977 against 1008 frames/s: the two cross-stream event waits cost more than the 33 us they hide), so off
     double* prior_c0 = nullptr;       // [2] the prior's constant c0 per buffer, device resident
     int marg_form = 0;                // DV_MARG_INFO / DV_MARG_EIGEN (dv_set_marg_form): the form of the prior every marginalization of this ctx leaves
     DevBuf eig_spec; bool eig_ran = false;      // DV_MARG_EIGEN: eigenvalues | sweeps | n | converged of the last be_marg_eig (dv_marg_last_spectrum); whether one has been enqueued
@@ -143,7 +142,6 @@ int be_solve_fused(dv_ctx* ctx, dv_ba_problem* P, dv_ba_summary* summary, BeFuse
 void be_batch_detach(dv_ctx* ctx);          // dv_destroy: leave the dv_batch this ctx is a member of
 struct DvFrontBatch;                        // the front-end half of a dv_batch (front_track.hip): stream, event, job tables of the shared tracking launches
 DvFrontBatch*& be_batch_front(struct dv_batch* B);
-int be_batch_index(struct dv_batch* B);
 const std::vector<dv_ctx*>& be_batch_members(struct dv_batch* B);
 void dv_front_batch_release(DvFrontBatch* F);
 void dv_front_batch_sync(DvFrontBatch* F);
@@ -222,16 +220,14 @@ struct dv_ctx {
     ObjPending obj_pend, obj_op_pend;            // estimator's object solve / operator-level dv_obj_solve
     hipStream_t obj_stream = nullptr; DevBuf obj_buf;      // dynamic mode: the object solve runs beside the window solve
     DvDist dist;
-    struct dv_batch* batch = nullptr;             // member of a batch of independent windows solved by shared launches (be_api.hip)
+    struct dv_batch* batch = nullptr;             // member of a batch of independent windows solved by shared launches (be_batch.hip)
     dv_estimator* est = nullptr;
     struct dv_inst_tracker* inst = nullptr; hipEvent_t ev_pyr = nullptr, ev_bg_select = nullptr;      // dynamic mode: the per-object tracker (inst_track.hip)
 };
 
 void dv_set_error(dv_ctx* ctx, const std::string& msg);
-// Stream of a dv_batch group.  DVINS_CU_PARTITIONS=P (experiment, off by default): group g's streams get the CU mask of partition g mod P — bits [256 g / P, 256 (g + 1) / P) of
-// the 256-bit mask, i.e. (mask bit i = CU i / 8 of XCD i mod 8: scripts/dbg/cumask_probe.hip) the same 32 / P CUs of EVERY XCD — so that the groups' kernels do not
-// compete for CUs with each other: a be_solve_batch workgroup needs a whole CU (157 KB of LDS, 16 waves of 128 VGPRs) and has to wait for one to drain completely.
-hipError_t dv_group_stream_create(hipStream_t* s, int group_index);
+// (The CU-mask experiments — a partition of the CUs per dv_batch group, CUs reserved for the window solves — and the side stream of the prior's constant c0 were all
+// measured slower and have left the code: every stream of the library is a plain non-blocking stream.  Their measurements: DESIGN_HISTORY.md.)
 
 #define DV_CHECK(expr)                                                                   \
     do {                                                                                 \

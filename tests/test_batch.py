@@ -16,8 +16,9 @@ def make_inputs(seed, phase, use_imu):
     return traj, fs, T0
 
 
-@pytest.mark.parametrize("use_imu,S,frames", [(1, 3, 32), (0, 3, 32), (1, 16, 22)])
-def test_batched_estimators_equal_single_estimators(gpu_ctx_factory, use_imu, S, frames):
+def run_group_against_singles(gpu_ctx_factory, use_imu, S, frames, setup=None, sits_out=1):
+    """S estimators in a Batch beside S estimators alone, the same measurements to both: every frame's summary and window must be EQUAL.  setup(single, batched) may
+    set debug switches before the first frame; member `sits_out` skips round 20.  Returns the batch's round counters."""
     from dynamic_vins_amd.backend import Batch, Estimator
     dtf = 0.1
     kw = dict(use_imu=use_imu, stereo=1, max_iters=8, ric=[sim.R_IC, sim.R_IC], tic=[sim.T_IC0, sim.T_IC1], **NOISE)
@@ -26,6 +27,8 @@ def test_batched_estimators_equal_single_estimators(gpu_ctx_factory, use_imu, S,
         single.append(Estimator(gpu_ctx_factory(width=64, height=64, max_cnt=10, min_dist=5), **kw))
         batched.append(Estimator(gpu_ctx_factory(width=64, height=64, max_cnt=10, min_dist=5), **kw))
         inputs.append(make_inputs(i, 0.37 * i, use_imu))
+    if setup:
+        setup(single, batched)
     batch = Batch([e.ctx for e in batched])
     imu = [sim.imu_stream(tr, T0 - 0.05, T0 + frames * dtf + 0.1, 200.0, **NOISE) for tr, _, T0 in inputs]
     k = [0] * S
@@ -38,7 +41,7 @@ def test_batched_estimators_equal_single_estimators(gpu_ctx_factory, use_imu, S,
                 single[i].InputIMU(ts[k[i]], acc[k[i]], gyr[k[i]]); batched[i].InputIMU(ts[k[i]], acc[k[i]], gyr[k[i]]); k[i] += 1
             rows.append((fs.frame(t), t))
         if f == 20:        # one member sits a round out: the others are still solved together
-            active = [i for i in range(S) if i != 1]
+            active = [i for i in range(S) if i != sits_out]
         else:
             active = list(range(S))
         ref = {i: single[i].ProcessMeasurements(*rows[i])[1] for i in active}
@@ -51,8 +54,37 @@ def test_batched_estimators_equal_single_estimators(gpu_ctx_factory, use_imu, S,
             assert (sb.frame, sb.nonlinear, sb.iterations, sb.initial_cost, sb.final_cost) == ref[i], f"frame {f}, member {i}"
             assert np.array_equal(batched[i].window(), single[i].window()), f"frame {f}, member {i}"
     info = batch.info()
-    assert info["batched_rounds"] >= frames - 14, info        # every steady-state round went through the shared launches
     batch.close()
+    return info
+
+
+def debug_set(est, key):
+    assert est.ctx.lib.dv_debug_set(est.ctx.h, key.encode(), 1) == 0, key
+
+
+@pytest.mark.parametrize("use_imu,S,frames", [(1, 3, 32), (0, 3, 32), (1, 16, 22)])
+def test_batched_estimators_equal_single_estimators(gpu_ctx_factory, use_imu, S, frames):
+    info = run_group_against_singles(gpu_ctx_factory, use_imu, S, frames)
+    assert info["batched_rounds"] >= frames - 14, info        # every steady-state round went through the shared launches
+
+
+@pytest.mark.parametrize("key", ["batch_single_eval", "batch_single_reduce", "batch_single_solve"])
+def test_one_stage_through_the_members_own_launches(gpu_ctx_factory, key):
+    """dv_debug_set "batch_single_*" on the group's first member: one stage of every shared round loops over the members' single-window launchers (same stream, same
+    order, same bodies) — the round stays a batched one and the results stay those of the estimators alone, bit for bit."""
+    frames = 26
+    info = run_group_against_singles(gpu_ctx_factory, 1, 3, frames, setup=lambda single, batched: debug_set(batched[0], key))
+    assert info["batched_rounds"] >= frames - 14, info
+
+
+def test_mixed_round_runs_the_spare_slots_inside_a_batch(gpu_ctx_factory):
+    """Member 1 (and its twin alone) enqueue max_iters - 2 slots first ("short_first_pass"): the group is not uniform, so every steady-state round goes through the
+    members' own launches on the group's stream, and member 1 collects its frame through the spare-slot continuation of be_solve_fused_end while it is a batch
+    member.  Member 2 is the one that sits a round out, so that no round is left uniform."""
+    frames = 26
+    info = run_group_against_singles(gpu_ctx_factory, 1, 3, frames, sits_out=2,
+                                     setup=lambda single, batched: (debug_set(single[1], "short_first_pass"), debug_set(batched[1], "short_first_pass")))
+    assert info["single_rounds"] >= frames - 14, info
 
 
 def test_member_destroyed_before_its_batch_and_abort(gpu_ctx_factory):
