@@ -272,4 +272,9 @@ int dv_ensure_cand(dv_ctx* ctx, int w, int h);     // the candidate buffer of a 
 struct PyrPlan { bool has_l0, pair; int levels; DvLevel0Job l0; DvPyrJob down[DV_MAX_LEVELS - 1]; DvPyr apron[2]; };
 int dv_plan_pyramids(dv_ctx* ctx, const DvPyr& a, const DvPyr* b, const uint8_t* img0, const uint8_t* img1, int stride, int mem, bool undistort, hipStream_t s, PyrPlan& P);
 void dv_launch_pyramids(const PyrPlan& P, hipStream_t s);
+// The GPU tracker's pyramids (cuda::pyrDown's rounding) on top of an existing level 0, split like the pair above: the plan allocates, points level 0 at the regular
+// pyramids' and fills the level steps; they are launched by value (dv_launch_cuda_pyramids) or scattered into a dv_batch round's table.  dv_build_cuda_pyramids = both, on ctx->stream
+struct CudaPyrPlan { int levels; DvPyrJob down[DV_MAX_LEVELS - 1]; };
+int dv_plan_cuda_pyramids(dv_ctx* ctx, PyrSet& C0, PyrSet* C1, const DvPyr& a0, const DvPyr* b0, int w, int h, int max_level, CudaPyrPlan& P);
+void dv_launch_cuda_pyramids(const CudaPyrPlan& P, hipStream_t s);
 int dv_build_cuda_pyramids(dv_ctx* ctx, PyrSet& C0, PyrSet* C1, const DvPyr& a0, const DvPyr* b0, int w, int h, int max_level);

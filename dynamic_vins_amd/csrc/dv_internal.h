@@ -84,7 +84,7 @@ void dv_launch_lk_generic(const DvPyr& A, const DvPyr& B, const float2* pts_a, i
 // one job of dv_launch_lk_track_multi (device-resident table): FeatureTrackByLK of one object's points between its two pyramids
 // one level step of one image pair for dv_launch_pyr_down_multi (src1 / dst1 may be null: single image)
 struct DvPyrJob { const uint8_t* src0; const uint8_t* src1; uint8_t* dst0; uint8_t* dst1; int sw, sh, spitch, dw, dh, dpitch; uint8_t* cpy0; uint8_t* cpy1; int cpitch, pad_; };      // cpy (optional): the source tile's own pixels also go to a pitched copy (level 0 of the pyramid: frame read once)
-void dv_launch_pyr_down_multi(const DvPyrJob* jobs_dev, int n_jobs, int max_dw, int max_dh, hipStream_t s);
+void dv_launch_pyr_down_multi(const DvPyrJob* jobs_dev, int n_jobs, int max_dw, int max_dh, hipStream_t s, int rn_even = 0);      // rn_even: as dv_launch_pyr_down2
 void dv_launch_pyr_apron_multi(const DvPyr* pyrs_dev, int n_pyr, int max_levels, hipStream_t s);
 // pyramid level 0 of one member of a dv_batch round for dv_launch_level0_multi: remap through the member's own maps (gray or BGR -> gray) or BGR -> gray alone.
 // map0 / map1: the member's map block per camera (w * h short2 of map1, then w * h uint16 of map2), unused by DV_L0_BGR; src1 / dst1 null: single image.  w, h: the group's common geometry
@@ -115,6 +115,7 @@ void dv_launch_finalize_offset(const DvTrackState& tr, const dv_cam& cam0, const
                                dv_feat* out, int* n_out, hipStream_t s);
 // the reference's GPU tracker rule (lk_cuda.hip): A / B are pyramids built with cuda::pyrDown's rounding (dv_launch_pyr_down2(..., rn_even = 1)); level 0 is the frame
 void dv_launch_lk_cuda_track(const DvPyr& A, const DvPyr& B, const float2* pts_a, const int* n_dev, int n_max, int flow_back, float dist_thresh, float2* pts_b, uint8_t* status, hipStream_t s);
+void dv_launch_lk_cuda_track_multi(const DvLkJob* jobs_dev, int n_jobs, int n_max, int flow_back, float dist_thresh, hipStream_t s);      // the same over a job table: grid (n_max, n_jobs), maxLevel 3, 30 iterations
 void dv_launch_lk_cuda_generic(const DvPyr& A, const DvPyr& B, const float2* pts_a, int n, int max_level, int iters, int use_initial, float2* pts_b, uint8_t* status, hipStream_t s);
 void dv_launch_gftt_tile(const GfttTileArgs& a, hipStream_t s);
 // system/main.cpp:217-245: inv_mask(y0 + r, x0 + c) = 255 where roi_mask(r, c) >= 1 (a static instance's pixels become background); roi_mask: w x h bytes in PINNED host memory, read in place

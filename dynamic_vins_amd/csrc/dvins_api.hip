@@ -135,14 +135,27 @@ static int build_pyramids(dv_ctx* ctx, PyrSet& P0, PyrSet* P1, const uint8_t* im
 }
 
 // the pyramid cv::cuda::SparsePyrLKOpticalFlow builds (cuda::pyrDown: round half to even) on top of an existing level 0 (a0 / b0: level 0 of the regular pyramids)
-int dv_build_cuda_pyramids(dv_ctx* ctx, PyrSet& C0, PyrSet* C1, const DvPyr& a0, const DvPyr* b0, int w, int h, int max_level) {
+int dv_plan_cuda_pyramids(dv_ctx* ctx, PyrSet& C0, PyrSet* C1, const DvPyr& a0, const DvPyr* b0, int w, int h, int max_level, CudaPyrPlan& P) {
     DV_CHECK(C0.alloc(w, h, max_level, true));
     if (C1) DV_CHECK(C1->alloc(w, h, max_level, true));
     C0.pyr.L[0] = a0.L[0];
     if (C1) C1->pyr.L[0] = b0->L[0];
-    for (int l = 1; l < C0.pyr.levels; ++l)
-        dv_launch_pyr_down2(C0.pyr.L[l - 1].p, C1 ? C1->pyr.L[l - 1].p : nullptr, C0.pyr.L[l - 1].w, C0.pyr.L[l - 1].h, C0.pyr.L[l - 1].pitch, C0.pyr.L[l].p, C1 ? C1->pyr.L[l].p : nullptr,
-                            C0.pyr.L[l].pitch, nullptr, nullptr, 0, ctx->stream, 1);
+    P.levels = C0.pyr.levels;
+    for (int l = 1; l < P.levels; ++l) {
+        const DvLevel& f = C0.pyr.L[l - 1]; const DvLevel& t = C0.pyr.L[l];
+        DvPyrJob& pj = P.down[l - 1]; pj = DvPyrJob{};
+        pj.src0 = f.p; pj.src1 = C1 ? C1->pyr.L[l - 1].p : nullptr; pj.dst0 = t.p; pj.dst1 = C1 ? C1->pyr.L[l].p : nullptr;
+        pj.sw = f.w; pj.sh = f.h; pj.spitch = f.pitch; pj.dw = t.w; pj.dh = t.h; pj.dpitch = t.pitch;
+    }
+    return 0;
+}
+void dv_launch_cuda_pyramids(const CudaPyrPlan& P, hipStream_t s) {
+    for (int l = 1; l < P.levels; ++l) { const DvPyrJob& j = P.down[l - 1]; dv_launch_pyr_down2(j.src0, j.src1, j.sw, j.sh, j.spitch, j.dst0, j.dst1, j.dpitch, nullptr, nullptr, 0, s, 1); }
+}
+int dv_build_cuda_pyramids(dv_ctx* ctx, PyrSet& C0, PyrSet* C1, const DvPyr& a0, const DvPyr* b0, int w, int h, int max_level) {
+    CudaPyrPlan P;
+    if (dv_plan_cuda_pyramids(ctx, C0, C1, a0, b0, w, h, max_level, P)) return -1;
+    dv_launch_cuda_pyramids(P, ctx->stream);
     DV_CHECK(hipGetLastError());
     return 0;
 }

@@ -1,26 +1,54 @@
 // front_track.hip — the tracker's per-frame entries of the C ABI: dv_track_stereo_enqueue / _collect for one sequence, dv_batch_track_enqueue for a dv_batch group.
 // One frame = pyrDown x3 (stereo pair per launch) -> LK temporal -> compact/sort -> Shi-Tomasi tile -> select/append -> LK stereo -> finalize (<= max_cnt 128-byte
-// rows, written into pinned memory by the kernel).  Both entries take what the stages are given from ONE description of the frame (front_plan): the single entry
-// launches it by value with the single-sequence kernels, the group entry scatters it into the job tables of the _multi kernels.
+// rows, written into pinned memory by the kernel); naive and semantic mode add the GPU tracker's own pyramid levels and, with mask_morphology_size, the mask's erosion.
+// Both entries take what the stages are given from ONE description of the frame (front_plan), mode and mask included: the single entry launches it by value with the
+// single-sequence kernels, the group entry scatters it into the job tables of the _multi kernels — raw members and naive members with masks alike.
 #include "dv_ctx.h"
 
-// What the stages of one raw-mode frame of one context are given, in the job types of the table kernels
+// What the stages of one frame of one context are given, in the job types of the table kernels
 struct FrontPlan {
     bool dev;                                  // the frames are device-addressable (DV_MEM_DEVICE, or pinned + mapped host memory)
     PyrPlan pyr;                               // level 0, the level steps, the two pyramids of the apron stage, the number of levels
+    // FeatureTrackByLKGpu's own pyramids where the reference runs that tracker (naive: TrackLeftGPU + TrackRightGPU; semantic: TrackRightGPU).  cuda_prev: the previous
+    // frame was tracked in another mode, its pyramid of this flavour is built now (the single entry only: such a job does not share a round's launches)
+    bool cuda, cuda_prev; CudaPyrPlan cpyr, cpyr_prev;
+    const uint8_t* mask; int mask_pitch;       // the frame's mask as the device reads it, before the erosion (null: none)
+    bool has_erode; DvErodeJob erode;          // ErodeMask of naive / semantic mode with mask_morphology_size > 0
     DvLkJob lk_temporal, lk_stereo;
+    bool temporal_gpu_rule, stereo_gpu_rule;   // the stage runs the GPU tracker (lk_cuda.hip) on the cpyr pyramids, not lk.hip's
+    float dist_temporal, dist_stereo;
     DvCompactJob compact; GfttTileArgs tile; GfttSelectArgs select; DvFinalizeJob fin;
 };
 
 static int job_stride(const dv_track_job& j, int w) { return j.stride > 0 ? j.stride : w * ((j.mem & DV_FMT_BGR) ? 3 : 1); }
 
-// Everything a frame needs before its first launch: the member-level checks, the lazily created resources, the frames' way into level 0 (copies on s) and the
-// stages' arguments.  The frame is built in the pyramid the ctx is NOT looking at (cur ^ 1) and the ctx is not changed: front_commit does that, once the whole
-// enqueue has succeeded, so that a refused or failed enqueue of either kind leaves no flipped `cur` and no pending frame behind.
+// the mask's way into the stages that read it: eroded first in naive / semantic mode (ErodeMask, background_tracker.cpp:408-416,764-768), then the compaction's mask test
+// (naive / semantic) and the detector's mask.  Called by front_plan, and again by the single entry after dv_track_unmask_static moved the mask into mask_buf
+static int front_plan_mask(dv_ctx* ctx, int mode, const uint8_t* mask, int mask_pitch, FrontPlan& P) {
+    const dv_config& c = ctx->cfg;
+    const int w = c.width, h = c.height;
+    const bool naive = (mode != DV_MODE_RAW);            // naive and semantic share the InstFeat code path (mask test, no sort, >= 10 new)
+    P.mask = mask; P.mask_pitch = mask_pitch;
+    P.has_erode = naive && mask && c.mask_morphology_size > 0;
+    if (P.has_erode) {
+        const int ep = align_up(w, 16);
+        DV_CHECK(ctx->s3.ensure((size_t)ep * h)); DV_CHECK(ctx->s4.ensure((size_t)ep * h));
+        P.erode = DvErodeJob{ mask, (uint8_t*)ctx->s3.p, (uint8_t*)ctx->s4.p, w, h, mask_pitch, ep, ep, c.mask_morphology_size };
+        mask = (const uint8_t*)ctx->s4.p; mask_pitch = ep;
+    }
+    P.compact.mask_pitch = mask_pitch; P.compact.in_mask = naive ? mask : nullptr;
+    P.tile.in_mask = mask; P.tile.mask_pitch = mask_pitch;
+    return 0;
+}
+
+// Everything a frame needs before its first launch: the member-level checks, the lazily created resources, the frames' and the mask's way to the device (copies on s)
+// and the stages' arguments under the frame's mode.  The frame is built in the pyramid the ctx is NOT looking at (cur ^ 1) and the ctx is not changed: front_commit
+// does that, once the whole enqueue has succeeded, so that a refused or failed enqueue of either kind leaves no flipped `cur` and no pending frame behind.
 static int front_plan(dv_ctx* ctx, const dv_track_job& j, hipStream_t s, FrontPlan& P) {
     const dv_config& c = ctx->cfg;
     const int w = c.width, h = c.height;
     const bool stereo = c.stereo && j.gray1;
+    const int mode = j.mode;
     int mem = j.mem;
     if ((mem & 0xff) == DV_MEM_PINNED) mem = (mem & ~0xff) | DV_MEM_DEVICE;      // pinned + mapped host memory is device-addressable: the kernels read it in place
     if ((mem & 0xff) != DV_MEM_HOST && (mem & 0xff) != DV_MEM_DEVICE) DV_FAIL("dv_track_stereo: unknown memory kind");
@@ -31,25 +59,60 @@ static int front_plan(dv_ctx* ctx, const dv_track_job& j, hipStream_t s, FrontPl
     P.dev = (mem & ~DV_FMT_BGR) == DV_MEM_DEVICE;
     if (dv_ensure_hw(ctx, c.min_dist) || dv_ensure_cand(ctx, w, h)) return -1;
     if (ctx->last_front && ctx->last_front != s && ctx->last_done) DV_CHECK(hipStreamWaitEvent(s, ctx->last_done, 0));      // the previous frame ran on the other front-end stream (its own / a dv_batch's)
-    PyrSet& L = ctx->left[ctx->cur ^ 1]; PyrSet& Lp = ctx->left[ctx->cur];
+    const int cur = ctx->cur ^ 1;          // the pyramid slot of this frame
+    PyrSet& L = ctx->left[cur]; PyrSet& Lp = ctx->left[cur ^ 1];
     DV_CHECK(L.alloc(w, h, 3));
     if (stereo) DV_CHECK(ctx->right.alloc(w, h, 3));
     const DvPyr& a = L.pyr; const DvPyr& b = stereo ? ctx->right.pyr : a;
     if (dv_plan_pyramids(ctx, a, stereo ? &b : nullptr, j.gray0, j.gray1, job_stride(j, w), mem, ctx->undist[0], s, P.pyr)) return -1;
+    P.cuda = (mode != DV_MODE_RAW); P.cuda_prev = false;
+    if (P.cuda) {
+        if (dv_plan_cuda_pyramids(ctx, ctx->leftc[cur], stereo ? &ctx->rightc : nullptr, a, stereo ? &ctx->right.pyr : nullptr, w, h, 3, P.cpyr)) return -1;
+        if (mode == DV_MODE_NAIVE && ctx->have_prev && !ctx->leftc_valid[cur ^ 1]) {      // the previous frame was tracked in another mode: its pyramid of this flavour does not exist yet
+            if (dv_plan_cuda_pyramids(ctx, ctx->leftc[cur ^ 1], nullptr, Lp.pyr, nullptr, w, h, 3, P.cpyr_prev)) return -1;
+            P.cuda_prev = true;
+        }
+    }
     const DvTrackState& tr = ctx->tr;
+    // forward/backward consistency: FeatureTrackByLK keeps <= 0.5 px (feature_utils.cpp:56), FeatureTrackByLKGpu <= 1.0 px (:126) (Q12) — and the two are different
+    // trackers (lk.hip / lk_cuda.hip), each used where the reference uses it
+    P.temporal_gpu_rule = (mode == DV_MODE_NAIVE); P.stereo_gpu_rule = (mode != DV_MODE_RAW);      // TrackLeftGPU (naive) vs TrackLeft (raw, semantic); TrackRightGPU in naive and semantic
+    P.dist_temporal = P.temporal_gpu_rule ? 1.0f : 0.5f; P.dist_stereo = P.stereo_gpu_rule ? 1.0f : 0.5f;
     // temporal LK (a sequence's first frame has no previous pyramid: n_feat is 0, nothing is read), stereo LK
-    DvLkJob& t = P.lk_temporal; t = DvLkJob{}; t.A = ctx->have_prev ? Lp.pyr : a; t.B = a; t.pts_a = tr.last_pts; t.n_dev = tr.n_feat; t.pts_b = tr.lk_pts; t.status = tr.lk_status;
-    DvLkJob& r = P.lk_stereo; r = DvLkJob{}; r.A = a; r.B = b; r.pts_a = tr.curr_pts; r.n_dev = tr.n_feat; r.pts_b = tr.right_pts; r.status = tr.right_status;
-    P.compact = DvCompactJob{ tr, nullptr, 0, 1, ctx->n_cand, ctx->max_ord };
+    DvLkJob& t = P.lk_temporal; t = DvLkJob{}; t.pts_a = tr.last_pts; t.n_dev = tr.n_feat; t.pts_b = tr.lk_pts; t.status = tr.lk_status;
+    if (P.temporal_gpu_rule) { t.B = ctx->leftc[cur].pyr; t.A = ctx->have_prev ? ctx->leftc[cur ^ 1].pyr : t.B; }      // TrackLeftGPU -> FeatureTrackByLKGpu (instance_feature.cpp:191-216)
+    else { t.A = ctx->have_prev ? Lp.pyr : a; t.B = a; }
+    DvLkJob& r = P.lk_stereo; r = DvLkJob{}; r.pts_a = tr.curr_pts; r.n_dev = tr.n_feat; r.pts_b = tr.right_pts; r.status = tr.right_status;
+    if (P.stereo_gpu_rule) { r.A = ctx->leftc[cur].pyr; r.B = stereo ? ctx->rightc.pyr : r.A; }      // TrackRightGPU -> FeatureTrackByLKGpu (instance_feature.cpp:278-310)
+    else { r.A = a; r.B = b; }
+    const bool naive = (mode != DV_MODE_RAW);
+    const int min_new = naive ? 10 : 1;                   // Q23: instance_feature.cpp:353-356 vs background_tracker.cpp:82-90
+    // DetectNewFeature(img, use_gpu, ...): TrackImageNaive passes true (background_tracker.cpp:445) -> DetectShiTomasiCornersGpu (feature_utils.cpp:339-348),
+    // TrackSemanticImage passes false (:789) and TrackImage calls cv::goodFeaturesToTrack itself (:85)
+    const int gftt_rule = (mode == DV_MODE_NAIVE) ? DV_GFTT_RULE_CUDA : DV_GFTT_RULE_CPU;
+    P.compact = DvCompactJob{ tr, nullptr, 0, naive ? 0 : 1, ctx->n_cand, ctx->max_ord };
     GfttTileArgs& g = P.tile; g = GfttTileArgs{};
     g.img = a.L[0].p; g.w = w; g.h = h; g.pitch = a.L[0].pitch; g.in_mask = nullptr; g.mask_pitch = 0;
     g.disc_pts = tr.curr_pts; g.n_disc = tr.n_tracked; g.radius = c.min_dist; g.hw = (const uint8_t*)ctx->hw_buf.p;
-    g.n_feat = tr.n_feat; g.max_cnt = c.max_cnt; g.min_new = 1; g.eig_out = nullptr; g.eig_pitch = 0;
-    g.cand = (DvCand*)ctx->cand_buf.p; g.cand_cap = ctx->cand_cap; g.n_cand = ctx->n_cand; g.max_ord = ctx->max_ord; g.rule = DV_GFTT_RULE_CPU;
+    g.n_feat = tr.n_feat; g.max_cnt = c.max_cnt; g.min_new = min_new; g.eig_out = nullptr; g.eig_pitch = 0;
+    g.cand = (DvCand*)ctx->cand_buf.p; g.cand_cap = ctx->cand_cap; g.n_cand = ctx->n_cand; g.max_ord = ctx->max_ord; g.rule = gftt_rule;
     GfttSelectArgs& q = P.select; q = GfttSelectArgs{};
     q.cand = (const DvCand*)ctx->cand_buf.p; q.n_cand = ctx->n_cand; q.cand_cap = ctx->cand_cap; q.max_ord = ctx->max_ord;
-    q.w = w; q.h = h; q.quality = 0.01; q.min_dist = (double)c.min_dist; q.max_n_host = 0; q.n_feat = tr.n_feat; q.max_cnt = c.max_cnt; q.min_new = 1;
-    q.out_xy = nullptr; q.n_out = nullptr; q.tr = tr; q.has_tr = 1; q.err_flag = ctx->err_flag; q.rule = DV_GFTT_RULE_CPU;
+    q.w = w; q.h = h; q.quality = 0.01; q.min_dist = (double)c.min_dist; q.max_n_host = 0; q.n_feat = tr.n_feat; q.max_cnt = c.max_cnt; q.min_new = min_new;
+    q.out_xy = nullptr; q.n_out = nullptr; q.tr = tr; q.has_tr = 1; q.err_flag = ctx->err_flag; q.rule = gftt_rule;
+    // the mask: device-addressable jobs are read in place, host jobs staged into the ctx's own mask_buf on s.  The mask of a BGR job has one channel: rows of w bytes
+    const uint8_t* mask_dev = nullptr; int mask_pitch = 0;
+    if (j.mask) {
+        const int mstride = (mem & DV_FMT_BGR) ? w : job_stride(j, w);
+        if (P.dev) { mask_dev = j.mask; mask_pitch = mstride; }
+        else {
+            mask_pitch = align_up(w, 16);
+            DV_CHECK(ctx->mask_buf.ensure((size_t)mask_pitch * h));
+            DV_CHECK(hipMemcpy2DAsync(ctx->mask_buf.p, mask_pitch, j.mask, mstride, w, h, hipMemcpyHostToDevice, s));
+            mask_dev = (const uint8_t*)ctx->mask_buf.p;
+        }
+    }
+    if (front_plan_mask(ctx, mode, mask_dev, mask_pitch, P)) return -1;
     // the rows, their count and the device error flags go straight into the pinned buffer (three copy dispatches behind the kernel before: ~20 us of the
     // tracker's latency per frame)
     DvFinalizeJob& f = P.fin; f = DvFinalizeJob{};
@@ -58,9 +121,10 @@ static int front_plan(dv_ctx* ctx, const dv_track_job& j, hipStream_t s, FrontPl
     return 0;
 }
 
-// the planned frame is enqueued behind `done` on s: the ctx turns to the pyramid it was built in
-static void front_commit(dv_ctx* ctx, double t, hipEvent_t done, hipStream_t s) {
+// the planned frame is enqueued behind `done` on s: the ctx turns to the pyramid it was built in.  cuda: the frame built the GPU tracker's pyramid levels too
+static void front_commit(dv_ctx* ctx, double t, hipEvent_t done, hipStream_t s, bool cuda) {
     ctx->cur ^= 1; ctx->last_done = done; ctx->last_front = s;
+    ctx->leftc_valid[ctx->cur] = cuda;
     ctx->prev_time = t; ctx->have_prev = true; ctx->pending = true;
 }
 
@@ -89,32 +153,16 @@ int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gr
         dv_launch_pyramids(P.pyr, s);
         DV_CHECK(hipGetLastError());
     }
-    // ---- what the plan of a raw-mode frame does not know: the object tracker's events, the mask, and the GPU tracker's / detector's rules of naive and semantic mode ----
-    const DvPyr& L = P.pyr.apron[0];
+    // ---- the plan, launched by value; what it does not hold: the object tracker's events and the staged dv_track_unmask_static jobs ----
     if (ctx->inst) DV_CHECK(hipEventRecord(ctx->ev_pyr, s));
-    // FeatureTrackByLKGpu's own pyramids where the reference runs that tracker (naive: TrackLeftGPU + TrackRightGPU; semantic: TrackRightGPU)
-    ctx->leftc_valid[cur] = false;
-    if (mode != DV_MODE_RAW) {
+    if (P.cuda) {
         StageScope sc(ctx, "pyr_cuda");
-        if (dv_build_cuda_pyramids(ctx, ctx->leftc[cur], stereo ? &ctx->rightc : nullptr, L, stereo ? &ctx->right.pyr : nullptr, w, h, 3)) return -1;
-        ctx->leftc_valid[cur] = true;
-        if (mode == DV_MODE_NAIVE && ctx->have_prev && !ctx->leftc_valid[cur ^ 1]) {      // the previous frame was tracked in another mode: its pyramid of this flavour does not exist yet
-            if (dv_build_cuda_pyramids(ctx, ctx->leftc[cur ^ 1], nullptr, ctx->left[cur ^ 1].pyr, nullptr, w, h, 3)) return -1;
-            ctx->leftc_valid[cur ^ 1] = true;
-        }
-    }
-    const uint8_t* mask_dev = nullptr; int mask_pitch = 0;
-    if (mask_or_null) {
-        const bool bgr_in = (mem & DV_FMT_BGR) != 0;
-        if (P.dev) { mask_dev = mask_or_null; mask_pitch = bgr_in ? w : stride; }
-        else {
-            mask_pitch = align_up(w, 16);
-            DV_CHECK(ctx->mask_buf.ensure((size_t)mask_pitch * h));
-            DV_CHECK(hipMemcpy2DAsync(ctx->mask_buf.p, mask_pitch, mask_or_null, bgr_in ? w : stride, w, h, hipMemcpyHostToDevice, s));
-            mask_dev = (const uint8_t*)ctx->mask_buf.p;
-        }
+        dv_launch_cuda_pyramids(P.cpyr, s);
+        if (P.cuda_prev) { dv_launch_cuda_pyramids(P.cpyr_prev, s); ctx->leftc_valid[cur ^ 1] = true; }
+        DV_CHECK(hipGetLastError());
     }
     if (!ctx->unmask.empty()) {          // system/main.cpp:217-245: the static instances' pixels leave the merged mask (inv_merge_mask = 255 there) before anything reads it
+        const uint8_t* mask_dev = P.mask; int mask_pitch = P.mask_pitch;
         if (!mask_dev) { ctx->unmask.clear(); DV_FAIL("dv_track_unmask_static: the frame carries no mask"); }
         if (mask_dev != (const uint8_t*)ctx->mask_buf.p) {          // the caller's device buffer is not written to: work on a copy
             const int mp = align_up(w, 16);
@@ -125,55 +173,34 @@ int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gr
         for (const dv_ctx::UnmaskJob& j : ctx->unmask)
             dv_launch_unmask((uint8_t*)ctx->mask_buf.p, mask_pitch, w, h, j.x, j.y, j.w, j.h, (const uint8_t*)ctx->unmask_pinned + j.off, s);
         ctx->unmask.clear();
+        if (front_plan_mask(ctx, mode, mask_dev, mask_pitch, P)) return -1;
     }
-    const bool naive = (mode != DV_MODE_RAW);            // naive and semantic share the InstFeat code path (mask test, no sort, >= 10 new)
-    if (naive && mask_dev && c.mask_morphology_size > 0) {       // ErodeMask (background_tracker.cpp:408-416,764-768)
-        const int ep = align_up(w, 16);
-        DV_CHECK(ctx->s3.ensure((size_t)ep * h)); DV_CHECK(ctx->s4.ensure((size_t)ep * h));
-        dv_launch_erode(mask_dev, w, h, mask_pitch, c.mask_morphology_size, (uint8_t*)ctx->s3.p, ep, (uint8_t*)ctx->s4.p, ep, s);
-        mask_dev = (const uint8_t*)ctx->s4.p; mask_pitch = ep;
-    }
-    // forward/backward consistency: FeatureTrackByLK keeps <= 0.5 px (feature_utils.cpp:56), FeatureTrackByLKGpu <= 1.0 px (:126) (Q12) — and the two are different
-    // trackers (lk.hip / lk_cuda.hip), each used where the reference uses it
-    const float dist_temporal = (mode == DV_MODE_NAIVE) ? 1.0f : 0.5f;       // TrackLeftGPU (naive) vs TrackLeft (raw, semantic)
-    const float dist_stereo = (mode == DV_MODE_RAW) ? 0.5f : 1.0f;           // TrackRightGPU in naive and semantic
+    if (P.has_erode) { const DvErodeJob& k = P.erode; dv_launch_erode(k.src, k.w, k.h, k.spitch, k.k, k.tmp, k.tpitch, k.dst, k.dpitch, s); }
     if (ctx->have_prev) {
         StageScope sc(ctx, "lk_temporal");
         const DvLkJob& k = P.lk_temporal;
-        if (mode == DV_MODE_NAIVE)      // TrackLeftGPU -> FeatureTrackByLKGpu (instance_feature.cpp:191-216): the GPU tracker's rule
-            dv_launch_lk_cuda_track(ctx->leftc[cur ^ 1].pyr, ctx->leftc[cur].pyr, k.pts_a, k.n_dev, c.max_cnt, c.flow_back, dist_temporal, k.pts_b, k.status, s);
-        else
-            dv_launch_lk_track(k.A, k.B, k.pts_a, k.n_dev, c.max_cnt, c.flow_back, dist_temporal, k.pts_b, k.status, s, ctx->tr.lk_order);
+        if (P.temporal_gpu_rule) dv_launch_lk_cuda_track(k.A, k.B, k.pts_a, k.n_dev, c.max_cnt, c.flow_back, P.dist_temporal, k.pts_b, k.status, s);
+        else dv_launch_lk_track(k.A, k.B, k.pts_a, k.n_dev, c.max_cnt, c.flow_back, P.dist_temporal, k.pts_b, k.status, s, ctx->tr.lk_order);
     }
     {
         StageScope sc(ctx, "compact");
-        DvCompactJob& k = P.compact;
-        k.mask_pitch = mask_pitch;
-        if (naive) { k.in_mask = mask_dev; k.sort_by_cnt = 0; }
+        const DvCompactJob& k = P.compact;
         dv_launch_compact(k.tr, k.in_mask, k.mask_pitch, k.sort_by_cnt, k.n_cand, k.max_ord, s);
     }
-    const int min_new = naive ? 10 : 1;                   // Q23: instance_feature.cpp:353-356 vs background_tracker.cpp:82-90
-    // DetectNewFeature(img, use_gpu, ...): TrackImageNaive passes true (background_tracker.cpp:445) -> DetectShiTomasiCornersGpu (feature_utils.cpp:339-348),
-    // TrackSemanticImage passes false (:789) and TrackImage calls cv::goodFeaturesToTrack itself (:85)
-    const int gftt_rule = (mode == DV_MODE_NAIVE) ? DV_GFTT_RULE_CUDA : DV_GFTT_RULE_CPU;
     {
         StageScope sc(ctx, "gftt_eig");
-        P.tile.in_mask = mask_dev; P.tile.mask_pitch = mask_pitch; P.tile.min_new = min_new; P.tile.rule = gftt_rule;
         dv_launch_gftt_tile(P.tile, s);
     }
     {
         StageScope sc(ctx, "gftt_select");
-        P.select.min_new = min_new; P.select.rule = gftt_rule;
         if (dv_launch_gftt_select(P.select, s)) DV_FAIL("gftt_select: cannot set dynamic LDS size");
     }
     if (ctx->inst) DV_CHECK(hipEventRecord(ctx->ev_bg_select, s));
     if (stereo) {
         StageScope sc(ctx, "lk_stereo");
         const DvLkJob& k = P.lk_stereo;
-        if (mode != DV_MODE_RAW)        // TrackRightGPU -> FeatureTrackByLKGpu (instance_feature.cpp:278-310) in naive and semantic mode
-            dv_launch_lk_cuda_track(ctx->leftc[cur].pyr, ctx->rightc.pyr, k.pts_a, k.n_dev, c.max_cnt, c.flow_back, dist_stereo, k.pts_b, k.status, s);
-        else
-            dv_launch_lk_track(k.A, k.B, k.pts_a, k.n_dev, c.max_cnt, c.flow_back, dist_stereo, k.pts_b, k.status, s, ctx->tr.lk_order);
+        if (P.stereo_gpu_rule) dv_launch_lk_cuda_track(k.A, k.B, k.pts_a, k.n_dev, c.max_cnt, c.flow_back, P.dist_stereo, k.pts_b, k.status, s);
+        else dv_launch_lk_track(k.A, k.B, k.pts_a, k.n_dev, c.max_cnt, c.flow_back, P.dist_stereo, k.pts_b, k.status, s, ctx->tr.lk_order);
     }
     {
         StageScope sc(ctx, "finalize");
@@ -182,7 +209,7 @@ int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gr
     }
     DV_CHECK(hipGetLastError());
     DV_CHECK(hipEventRecord(ctx->done, s));
-    front_commit(ctx, t, ctx->done, s);
+    front_commit(ctx, t, ctx->done, s, P.cuda);
     return 0;
 }
 
@@ -248,6 +275,10 @@ int dv_track_stereo(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gray1, int
 // job table in HBM (blockIdx.z / .y / .x = member), so every member's rows are bit-identical to what its own dv_track_stereo_enqueue produces.
 // Members with undistortion maps (cfg::is_undistort_input) or BGR frames differ in level 0 alone: one more launch (level0_multi_kernel, pyramid.hip) fills it for all
 // of them, each through its own maps, and level 1 then reads it; a round without such a member does not launch it.
+// TrackImageNaive members (DV_MODE_NAIVE with a mask, background_tracker.cpp:398-470) are a second class of the same round: they share level 0, the pyramid levels,
+// aprons, compaction, tile, selection and rows with the raw members — their jobs carry the mask, min_new = 10 and the GPU detector's rule — and have three stages of
+// their own: cuda::pyrDown's levels 1..3 (pyr_down_multi_kernel<1>), the masks' erosion (those with mask_morphology_size > 0) and FeatureTrackByLKGpu
+// (lk_cuda_track_multi_kernel at 1.0 px) over their slice of the two LK tables, where the raw slice runs lk_track_multi_kernel at 0.5 px.
 struct DvFrontBatch {
     hipStream_t stream = nullptr; hipEvent_t done = nullptr, ev_copy[2] = { nullptr, nullptr };
     DevBuf tab[2]; void* tab_pinned[2] = { nullptr, nullptr }; size_t tab_bytes = 0; int parity = 0; bool copy_used[2] = { false, false };
@@ -276,38 +307,69 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
         for (int k = 0; k < 2; ++k) DV_CHECK(hipEventCreateWithFlags(&Fp->ev_copy[k], hipEventDisableTiming));
     }
     DvFrontBatch& F = *Fp;
-    // ---- which jobs can share launches: raw mode, no mask, no object tracker, the group's common geometry (gray or BGR frames, with or without the member's own
-    //      undistortion maps: those differ in how level 0 is filled and in nothing behind it) ----
-    std::vector<int> M;                                         // job indices that are batched
-    const dv_config* ref = nullptr;
+    // ---- which jobs can share launches.  Two classes, both without an object tracker or timing on the ctx and of the group's common geometry (gray or BGR frames, with
+    //      or without the member's own undistortion maps: those differ in how level 0 is filled and in nothing behind it):
+    //        raw    DV_MODE_RAW without a mask (FeatureTracker::TrackImage);
+    //        naive  DV_MODE_NAIVE with a mask (TrackImageNaive), no dv_track_unmask_static jobs staged, and the previous frame — if there is one — tracked in naive
+    //               mode too, so that its pyramid of the GPU tracker's flavour exists; at least two of them in the round, a lone one has nothing to share.
+    //      Every other job keeps its member's own launches on its own stream, in this round only. ----
+    enum { K_SINGLE = 0, K_RAW = 1, K_NAIVE = 2 };
+    std::vector<int> kind(n, K_SINGLE);
     for (int i = 0; i < n; ++i) {
         const dv_track_job& j = jobs[i];
         if (j.member < 0 || j.member >= (int)mem.size()) DV_FAIL("dv_batch_track_enqueue: member index out of range");
-        dv_ctx* c = mem[j.member];
         for (int q = 0; q < i; ++q) if (jobs[q].member == j.member) DV_FAIL("dv_batch_track_enqueue: a member appears twice");
-        const bool plain = j.mode == DV_MODE_RAW && !j.mask && !c->inst && !c->timing && j.gray0 && (!c->cfg.stereo || j.gray1);
-        const bool same = !ref || (c->cfg.width == ref->width && c->cfg.height == ref->height && c->cfg.stereo == ref->stereo && c->cfg.flow_back == ref->flow_back);
-        if (plain && same) { if (!ref) ref = &c->cfg; M.push_back(i); }
-        else {      // its own launches on its own stream (ordered behind whatever the batch stream still holds for it: dv_track_stereo_enqueue)
-            if (dv_track_stereo_enqueue(c, j.gray0, j.gray1, c->cfg.width, c->cfg.height, job_stride(j, c->cfg.width), j.t, j.mask, j.mode, j.mem)) { dv_set_error(ctx, c->err); return -1; }
-            F.members_single++;
+        const dv_ctx* c = mem[j.member];
+        if (c->inst || c->timing || !j.gray0 || (c->cfg.stereo && !j.gray1)) continue;
+        if (j.mode == DV_MODE_RAW && !j.mask) kind[i] = K_RAW;
+        else if (j.mode == DV_MODE_NAIVE && j.mask && c->unmask.empty() && !(c->have_prev && !c->leftc_valid[c->cur])) kind[i] = K_NAIVE;
+    }
+    const dv_config* ref = nullptr;
+    int R = 0, N = 0;
+    for (int pass = 0; pass < 2; ++pass) {      // (the second pass: fewer than two naive jobs fit, the geometry is that of the first raw job then)
+        ref = nullptr; R = N = 0;
+        for (int i = 0; i < n; ++i) {
+            if (kind[i] == K_SINGLE) continue;
+            const dv_config& g = mem[jobs[i].member]->cfg;
+            if (!ref) ref = &g;
+            if (g.width != ref->width || g.height != ref->height || g.stereo != ref->stereo || g.flow_back != ref->flow_back) continue;
+            (kind[i] == K_RAW ? R : N)++;
         }
+        if (N == 0 || N >= 2) break;
+        for (int i = 0; i < n; ++i) if (kind[i] == K_NAIVE) kind[i] = K_SINGLE;
+    }
+    std::vector<int> M;                                         // job indices that are batched: the raw ones, then the naive ones (the two slices of the LK tables)
+    for (int cls = K_RAW; cls <= K_NAIVE; ++cls)
+        for (int i = 0; i < n; ++i) {
+            if (kind[i] != cls) continue;
+            const dv_config& g = mem[jobs[i].member]->cfg;
+            if (g.width != ref->width || g.height != ref->height || g.stereo != ref->stereo || g.flow_back != ref->flow_back) kind[i] = K_SINGLE;
+            else M.push_back(i);
+        }
+    if ((int)M.size() == 1) { kind[M[0]] = K_SINGLE; M.clear(); }      // nothing to share
+    for (int i : M) {      // (before anything is enqueued, the single jobs included; with dv_track_stereo_enqueue's text, on the member and on the first one)
+        dv_ctx* c = mem[jobs[i].member];
+        if (c->pending) { dv_set_error(c, "dv_track_stereo_enqueue: previous frame not collected"); dv_set_error(ctx, c->err); return -1; }
+    }
+    for (int i = 0; i < n; ++i) {
+        if (kind[i] != K_SINGLE) continue;      // its own launches on its own stream (ordered behind whatever the batch stream still holds for it: dv_track_stereo_enqueue)
+        const dv_track_job& j = jobs[i]; dv_ctx* c = mem[j.member];
+        if (dv_track_stereo_enqueue(c, j.gray0, j.gray1, c->cfg.width, c->cfg.height, job_stride(j, c->cfg.width), j.t, j.mask, j.mode, j.mem)) { dv_set_error(ctx, c->err); return -1; }
+        F.members_single++;
     }
     const int S = (int)M.size();
     if (S == 0) return 0;
-    if (S == 1) {      // nothing to share
-        const dv_track_job& j = jobs[M[0]]; dv_ctx* c = mem[j.member];
-        if (dv_track_stereo_enqueue(c, j.gray0, j.gray1, c->cfg.width, c->cfg.height, job_stride(j, c->cfg.width), j.t, nullptr, DV_MODE_RAW, j.mem)) { dv_set_error(ctx, c->err); return -1; }
-        F.members_single++;
-        return 0;
-    }
+    R = 0; for (int i : M) R += kind[i] == K_RAW;
+    N = S - R;
     const int w = ref->width, h = ref->height; const bool stereo = ref->stereo != 0;
     hipStream_t s = F.stream;
     // ---- the job tables of the round: one pinned block, one upload ----
-    const size_t o_pyr = 0, o_apr = o_pyr + (size_t)3 * S * sizeof(DvPyrJob), o_lk = (o_apr + (size_t)2 * S * sizeof(DvPyr) + 255) / 256 * 256,
-                 o_cmp = (o_lk + (size_t)2 * S * sizeof(DvLkJob) + 255) / 256 * 256, o_gt = (o_cmp + (size_t)S * sizeof(DvCompactJob) + 255) / 256 * 256,
-                 o_gs = (o_gt + (size_t)S * sizeof(GfttTileArgs) + 255) / 256 * 256, o_fin = (o_gs + (size_t)S * sizeof(GfttSelectArgs) + 255) / 256 * 256,
-                 o_l0 = (o_fin + (size_t)S * sizeof(DvFinalizeJob) + 255) / 256 * 256, total = (o_l0 + (size_t)S * sizeof(DvLevel0Job) + 255) / 256 * 256;
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t o_pyr = 0, o_apr = o_pyr + (size_t)3 * S * sizeof(DvPyrJob), o_lk = up(o_apr + (size_t)2 * S * sizeof(DvPyr)),
+                 o_cmp = up(o_lk + (size_t)2 * S * sizeof(DvLkJob)), o_gt = up(o_cmp + (size_t)S * sizeof(DvCompactJob)),
+                 o_gs = up(o_gt + (size_t)S * sizeof(GfttTileArgs)), o_fin = up(o_gs + (size_t)S * sizeof(GfttSelectArgs)),
+                 o_l0 = up(o_fin + (size_t)S * sizeof(DvFinalizeJob)), o_cp = up(o_l0 + (size_t)S * sizeof(DvLevel0Job)),
+                 o_er = up(o_cp + (size_t)3 * N * sizeof(DvPyrJob)), total = up(o_er + (size_t)N * sizeof(DvErodeJob));
     const int par = F.parity; F.parity ^= 1;
     if (F.copy_used[par]) DV_CHECK(hipEventSynchronize(F.ev_copy[par]));      // the upload that last read this pinned block (two rounds ago) has run
     if (F.tab_bytes < total) {
@@ -325,13 +387,14 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
     DvPyrJob* h_pyr = (DvPyrJob*)(hp + o_pyr); DvPyr* h_apr = (DvPyr*)(hp + o_apr); DvLkJob* h_lk = (DvLkJob*)(hp + o_lk); DvCompactJob* h_cmp = (DvCompactJob*)(hp + o_cmp);
     GfttTileArgs* h_gt = (GfttTileArgs*)(hp + o_gt); GfttSelectArgs* h_gs = (GfttSelectArgs*)(hp + o_gs); DvFinalizeJob* h_fin = (DvFinalizeJob*)(hp + o_fin);
     DvLevel0Job* h_l0 = (DvLevel0Job*)(hp + o_l0); int n_l0 = 0;      // only the members whose level 0 is not a copy of the frame: none in an all-plain round, and no launch then
+    DvPyrJob* h_cp = (DvPyrJob*)(hp + o_cp);                          // the GPU tracker's pyramid levels of the naive members, level-major like h_pyr
+    DvErodeJob* h_er = (DvErodeJob*)(hp + o_er); int n_er = 0;        // only the naive members with mask_morphology_size > 0
     // ---- per member: its plan of the frame, scattered into the tables.  (No ctx changes before the commit below: a member's refusal, a failed upload or LDS
-    //      attribute leave no member with a flipped current pyramid or a pending frame) ----
-    int n_max = 0, levels = 0, lw[DV_MAX_LEVELS] = { 0 }, lh[DV_MAX_LEVELS] = { 0 };
+    //      attribute leave no member with a flipped current pyramid, a pending frame or a GPU-tracker pyramid marked valid) ----
+    int n_max = 0, n_max_raw = 0, n_max_naive = 0, levels = 0, lw[DV_MAX_LEVELS] = { 0 }, lh[DV_MAX_LEVELS] = { 0 }, clevels = 0;
     FrontPlan P;
     for (int k = 0; k < S; ++k) {
         const dv_track_job& j = jobs[M[k]]; dv_ctx* c = mem[j.member];
-        if (c->pending) { dv_set_error(ctx, "dv_batch_track_enqueue: a member's previous frame was not collected"); return -1; }
         if (front_plan(c, j, s, P)) { dv_set_error(ctx, c->err); return -1; }      // (with dv_track_stereo's text, on the member and on the first one)
         if (P.pyr.has_l0) h_l0[n_l0++] = P.pyr.l0;
         levels = P.pyr.levels;
@@ -340,22 +403,39 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
         h_lk[k] = P.lk_temporal; h_lk[S + k] = P.lk_stereo;
         h_cmp[k] = P.compact; h_gt[k] = P.tile; h_gs[k] = P.select; h_fin[k] = P.fin;
         n_max = std::max(n_max, c->cfg.max_cnt);
+        if (k < R) n_max_raw = std::max(n_max_raw, c->cfg.max_cnt);
+        else {
+            n_max_naive = std::max(n_max_naive, c->cfg.max_cnt);
+            clevels = P.cpyr.levels;      // (every level of the size: the same for all members)
+            for (int l = 1; l < clevels; ++l) h_cp[(size_t)(l - 1) * N + (k - R)] = P.cpyr.down[l - 1];
+            if (P.has_erode) h_er[n_er++] = P.erode;
+        }
     }
     DV_CHECK(dv_copy_async(F.tab[par].p, hp, total, s));
     DV_CHECK(hipEventRecord(F.ev_copy[par], s)); F.copy_used[par] = true;
-    // ---- the stages ----
+    // ---- the stages.  A class without a member launches nothing: a round of raw members enqueues the ten launches it always did ----
+    const DvLkJob* d_lk = (const DvLkJob*)(dp + o_lk);
     if (n_l0) dv_launch_level0_multi((const DvLevel0Job*)(dp + o_l0), n_l0, w, h, s);
     for (int l = 1; l < levels; ++l) dv_launch_pyr_down_multi((const DvPyrJob*)(dp + o_pyr) + (size_t)(l - 1) * S, S, lw[l], lh[l], s);
     dv_launch_pyr_apron_multi((const DvPyr*)(dp + o_apr), 2 * S, levels, s);
-    dv_launch_lk_track_multi((const DvLkJob*)(dp + o_lk), S, n_max, ref->flow_back, 0.5f, s);
+    for (int l = 1; l < clevels; ++l) {      // cuda::pyrDown's levels on top of level 0 (all of them: the level sizes follow from the common geometry)
+        const DvPyrJob& j0 = h_cp[(size_t)(l - 1) * N];
+        dv_launch_pyr_down_multi((const DvPyrJob*)(dp + o_cp) + (size_t)(l - 1) * N, N, j0.dw, j0.dh, s, 1);
+    }
+    if (n_er) dv_launch_erode_multi((const DvErodeJob*)(dp + o_er), n_er, w, h, s);
+    dv_launch_lk_track_multi(d_lk, R, n_max_raw, ref->flow_back, 0.5f, s);
+    dv_launch_lk_cuda_track_multi(d_lk + R, N, n_max_naive, ref->flow_back, 1.0f, s);      // FeatureTrackByLKGpu's threshold
     dv_launch_compact_multi((const DvCompactJob*)(dp + o_cmp), S, s);
     dv_launch_gftt_tile_multi((const GfttTileArgs*)(dp + o_gt), S, w, h, s);
     if (dv_launch_gftt_select_multi((const GfttSelectArgs*)(dp + o_gs), S, s)) DV_FAIL("gftt_select: cannot set dynamic LDS size");
-    if (stereo) dv_launch_lk_track_multi((const DvLkJob*)(dp + o_lk) + S, S, n_max, ref->flow_back, 0.5f, s);
+    if (stereo) {
+        dv_launch_lk_track_multi(d_lk + S, R, n_max_raw, ref->flow_back, 0.5f, s);
+        dv_launch_lk_cuda_track_multi(d_lk + S + R, N, n_max_naive, ref->flow_back, 1.0f, s);
+    }
     dv_launch_finalize_multi((const DvFinalizeJob*)(dp + o_fin), S, n_max, s);
     DV_CHECK(hipGetLastError());
     DV_CHECK(hipEventRecord(F.done, s));
-    for (int i : M) front_commit(mem[jobs[i].member], jobs[i].t, F.done, s);
+    for (int k = 0; k < S; ++k) front_commit(mem[jobs[M[k]].member], jobs[M[k]].t, F.done, s, k >= R);
     F.rounds++; F.members_batched += S;
     return 0;
 }

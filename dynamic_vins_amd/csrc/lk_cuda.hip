@@ -183,14 +183,11 @@ __device__ __forceinline__ LkcPt lkc_sparse(const DvPyr& A, const DvPyr& B, floa
     return o;
 }
 
-__global__ __launch_bounds__(256) void lk_cuda_track_kernel(DvPyr A, DvPyr B, const float2* __restrict__ pts_a, const int* __restrict__ n_dev, int n_host, int flow_back, float dist_thresh,
-                                                            int max_level, int iters, float2* __restrict__ pts_b, uint8_t* __restrict__ status) {
-    __shared__ __attribute__((aligned(16))) float sred[48];
-    __shared__ float sI[LKC_IT * LKC_IT], sJ[LKC_JT * LKC_JT];
+// FeatureTrackByLKGpu for the workgroup's point p: forward, backward from the forward result with the previous point as the initial flow, the distance and border
+// tests — the one definition behind the single-sequence kernel and the job-table kernel
+__device__ __forceinline__ void lkc_track_point(const DvPyr& A, const DvPyr& B, const float2* __restrict__ pts_a, int p, int flow_back, float dist_thresh, int max_level, int iters,
+                                                float2* __restrict__ pts_b, uint8_t* __restrict__ status, float* sred, float* sI, float* sJ) {
     LkcRed R{ sred, 0 };
-    const int p = blockIdx.x;
-    const int n = n_dev ? *n_dev : n_host;
-    if (p >= n) return;
     const float2 prev = pts_a[p];
     const LkcPt f = lkc_sparse(A, B, prev.x, prev.y, prev.x, prev.y, max_level, iters, R, sI, sJ);
     bool st = f.st;
@@ -201,6 +198,28 @@ __global__ __launch_bounds__(256) void lk_cuda_track_kernel(DvPyr A, DvPyr B, co
     }
     if (st && !lkc_in_border(f.nx, f.ny, B.L[0].h, B.L[0].w)) st = false;
     if (threadIdx.x == 0) { pts_b[p] = make_float2(f.nx, f.ny); status[p] = st ? 1 : 0; }
+}
+__global__ __launch_bounds__(256) void lk_cuda_track_kernel(DvPyr A, DvPyr B, const float2* __restrict__ pts_a, const int* __restrict__ n_dev, int n_host, int flow_back, float dist_thresh,
+                                                            int max_level, int iters, float2* __restrict__ pts_b, uint8_t* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) float sred[48];
+    __shared__ float sI[LKC_IT * LKC_IT], sJ[LKC_JT * LKC_JT];
+    const int p = blockIdx.x;
+    const int n = n_dev ? *n_dev : n_host;
+    if (p >= n) return;
+    lkc_track_point(A, B, pts_a, p, flow_back, dist_thresh, max_level, iters, pts_b, status, sred, sI, sJ);
+}
+// the same tracker for several independent point sets in ONE launch (the naive-mode front ends of a dv_batch group: blockIdx.y = job, blockIdx.x = point).  The job is
+// workgroup-uniform: its pointers are read once (scalar loads), and so is each level's descriptor pair, at the head of the level as the single kernel reads them from
+// its arguments — nothing of the table is read inside the iteration loop.  The grid covers the largest max_cnt of the table; a workgroup past its own job's point
+// count ends before the first barrier.
+__global__ __launch_bounds__(256) void lk_cuda_track_multi_kernel(const DvLkJob* __restrict__ jobs, int flow_back, float dist_thresh, int max_level, int iters) {
+    __shared__ __attribute__((aligned(16))) float sred[48];
+    __shared__ float sI[LKC_IT * LKC_IT], sJ[LKC_JT * LKC_JT];
+    const DvLkJob& j = jobs[blockIdx.y];
+    const int p = blockIdx.x;
+    if (p >= *j.n_dev) return;
+    const int ml = min(max_level, min(j.A.levels, j.B.levels) - 1);
+    lkc_track_point(j.A, j.B, j.pts_a, p, flow_back, dist_thresh, ml, iters, j.pts_b, j.status, sred, sI, sJ);
 }
 // single direction (parity tests of SparsePyrLKOpticalFlow::calc itself)
 __global__ __launch_bounds__(256) void lk_cuda_generic_kernel(DvPyr A, DvPyr B, const float2* __restrict__ pts_a, int n, int max_level, int iters, int use_initial,
@@ -223,6 +242,10 @@ void dv_launch_lk_cuda_track(const DvPyr& A, const DvPyr& B, const float2* pts_a
     if (n_max <= 0) return;
     const int ml = (A.levels < B.levels ? A.levels : B.levels) - 1;
     hipLaunchKernelGGL(lk_cuda_track_kernel, dim3(n_max), dim3(256), 0, s, A, B, pts_a, n_dev, n_max, flow_back, dist_thresh, ml < 3 ? ml : 3, 30, pts_b, status);
+}
+void dv_launch_lk_cuda_track_multi(const DvLkJob* jobs_dev, int n_jobs, int n_max, int flow_back, float dist_thresh, hipStream_t s) {
+    if (n_jobs <= 0 || n_max <= 0) return;
+    hipLaunchKernelGGL(lk_cuda_track_multi_kernel, dim3(n_max, n_jobs), dim3(256), 0, s, jobs_dev, flow_back, dist_thresh, 3, 30);
 }
 void dv_launch_lk_cuda_generic(const DvPyr& A, const DvPyr& B, const float2* pts_a, int n, int max_level, int iters, int use_initial, float2* pts_b, uint8_t* status, hipStream_t s) {
     if (n <= 0) return;

@@ -113,7 +113,8 @@ __global__ __launch_bounds__(256) void pyr_down_kernel(const uint8_t* __restrict
     pyr_down_tile(img ? src1 : src0, sw, sh, spitch, img ? dst1 : dst0, dw, dh, dpitch, img ? copy1 : copy0, cpitch, tx, ty, rn_even);
 }
 // the same level step for several independent image pairs in ONE launch (the per-object ROI pyramids of dynamic mode: blockIdx.z = 2 * job + image); the grid
-// covers the largest job, tiles outside a smaller one end at once
+// covers the largest job, tiles outside a smaller one end at once.  RN_EVEN: pyr_down_tile's rounding rule (cuda::pyrDown's for the GPU tracker's pyramids of a dv_batch round)
+template <int RN_EVEN>
 __global__ __launch_bounds__(256) void pyr_down_multi_kernel(const DvPyrJob* __restrict__ jobs, int tx_n, int ty_n, int n_z) {
     // the XCD-aware tile order of pyr_down_kernel over (plane z = 2 * job + image, tile row, tile column): one-dimensional grid padded to a multiple of 8
     const int total = tx_n * ty_n * n_z, per = (int)gridDim.x >> 3, L = ((int)blockIdx.x & 7) * per + ((int)blockIdx.x >> 3);
@@ -123,12 +124,13 @@ __global__ __launch_bounds__(256) void pyr_down_multi_kernel(const DvPyrJob* __r
     if (tx * PT_W >= j.dw || ty * PT_H >= j.dh) return;
     const int img = z & 1;
     if (img && !j.src1) return;
-    pyr_down_tile(img ? j.src1 : j.src0, j.sw, j.sh, j.spitch, img ? j.dst1 : j.dst0, j.dw, j.dh, j.dpitch, img ? j.cpy1 : j.cpy0, j.cpitch, tx, ty);
+    pyr_down_tile(img ? j.src1 : j.src0, j.sw, j.sh, j.spitch, img ? j.dst1 : j.dst0, j.dw, j.dh, j.dpitch, img ? j.cpy1 : j.cpy0, j.cpitch, tx, ty, RN_EVEN);
 }
-void dv_launch_pyr_down_multi(const DvPyrJob* jobs_dev, int n_jobs, int max_dw, int max_dh, hipStream_t s) {
+void dv_launch_pyr_down_multi(const DvPyrJob* jobs_dev, int n_jobs, int max_dw, int max_dh, hipStream_t s, int rn_even) {
     if (n_jobs <= 0) return;
     const int tx_n = (max_dw + PT_W - 1) / PT_W, ty_n = (max_dh + PT_H - 1) / PT_H, n_z = 2 * n_jobs, per = (tx_n * ty_n * n_z + 7) / 8;
-    hipLaunchKernelGGL(pyr_down_multi_kernel, dim3(8 * per), dim3(256), 0, s, jobs_dev, tx_n, ty_n, n_z);
+    if (rn_even) hipLaunchKernelGGL(pyr_down_multi_kernel<1>, dim3(8 * per), dim3(256), 0, s, jobs_dev, tx_n, ty_n, n_z);
+    else hipLaunchKernelGGL(pyr_down_multi_kernel<0>, dim3(8 * per), dim3(256), 0, s, jobs_dev, tx_n, ty_n, n_z);
 }
 
 // BORDER_REFLECT_101 apron of every level of one or two pyramids in ONE launch (blockIdx.y = level, blockIdx.z = image): with it no LK tile touches the

@@ -292,7 +292,7 @@ int group_track(dv_runner* R, dv_runner::Group& g, int ahead) {
         const int k = s.next + ahead - (s.skipped && ahead ? 1 : 0);      // (a track-only frame has already advanced s.next)
         if (k >= s.in.n_frames) continue;
         dv_track_job j{};
-        j.member = (int)m; j.mem = s.in.mem; j.gray0 = s.in.left[k]; j.gray1 = s.in.right[k]; j.stride = s.stride; j.mode = s.raw_mode; j.t = s.in.times[k]; j.mask = s.raw_mask ? s.raw_mask[k] : nullptr;      // (a masked / naive member keeps its own launches: dv_batch_track_enqueue)
+        j.member = (int)m; j.mem = s.in.mem; j.gray0 = s.in.left[k]; j.gray1 = s.in.right[k]; j.stride = s.stride; j.mode = s.raw_mode; j.t = s.in.times[k]; j.mask = s.raw_mask ? s.raw_mask[k] : nullptr;      // (naive members with masks share the round's launches when there are two or more of them; a lone one keeps its own: dv_batch_track_enqueue)
         jobs.push_back(j);
     }
     if (jobs.empty()) return 0;

@@ -312,10 +312,16 @@ int dv_batch_info(dv_batch* batch, long long* batched_rounds, long long* single_
  * the members' cameras may differ) share the launches too: one more launch fills pyramid level 0 of all such members of the round (remap, remap + BGR -> gray, or
  * BGR -> gray), their DV_MEM_HOST frames are staged on the group's stream first, DV_MEM_DEVICE / DV_MEM_PINNED frames are read in place.  A round of gray members
  * without maps enqueues exactly the ten launches above.
- * Jobs that cannot share launches (a mode other than DV_MODE_RAW, a mask, an object tracker on the ctx, dv_timing_enable on the ctx, another image size than the
- * first job's) run through their member's own dv_track_stereo_enqueue inside this call.  Every member is collected with dv_track_stereo_collect as usual;
- * its rows are bit-identical to the unbatched path's.  A member whose maps do not fit (another size, camera 1 missing on a stereo member) fails the call with
- * dv_track_stereo's message; no member of the shared part has a frame pending then.
+ * DV_MODE_NAIVE jobs with a mask (TrackImageNaive, what dv_runner_set_mask feeds) share the launches as a second class when the round holds at least two of them:
+ * the GPU tracker runs over their slice of the job tables, one launch per level builds its cuda::pyrDown-rule pyramids and one erodes the masks of the members with
+ * mask_morphology_size > 0; compaction, detection and rows are the group's launches, each job under its own mask and rules.  A DV_MEM_HOST job's mask is staged into
+ * the member's own buffer on the group's stream, a DV_MEM_DEVICE / DV_MEM_PINNED job's mask is read in place (rows of `stride` bytes, of width bytes for a BGR job).
+ * A round without such jobs enqueues nothing for them.
+ * Jobs that cannot share launches (DV_MODE_SEMANTIC, a raw job with a mask, a naive job without one, a lone naive job, a naive job with dv_track_unmask_static jobs
+ * staged or whose previous frame was tracked in another mode, an object tracker on the ctx, dv_timing_enable on the ctx, another image size than the first
+ * shareable job's) run through their member's own dv_track_stereo_enqueue inside this call, in this round only.  Every member is collected with
+ * dv_track_stereo_collect as usual; its rows are bit-identical to the unbatched path's.  A member whose maps do not fit (another size, camera 1 missing on a stereo
+ * member) or whose previous frame was not collected fails the call with dv_track_stereo's message; no member of the shared part has a frame pending then.
  * Between this call and a member's dv_track_stereo_collect, call no image operator (dv_remap, dv_bgr2gray, dv_pyr_down_cuda, ...) on that member: its staging buffers
  * are in use on the group's stream, which the operators' own stream is not ordered against. */
 typedef struct dv_track_job { int32_t member, mem /* DV_MEM_* [| DV_FMT_BGR] */; const uint8_t* gray0; const uint8_t* gray1; int32_t stride /* bytes, 0 = width (3 * width for DV_FMT_BGR) */, mode; double t; const uint8_t* mask; } dv_track_job;
