@@ -355,7 +355,7 @@ static int be_begin_impl(dv_ctx* ctx, dv_ba_problem* P, BeFused* fused, bool eva
     sa.ldl_mf16 = 0;
     if (!w.ldl_generic && !(P->free_blocks & 3)) {      // (free extrinsic / td blocks: the generic form carries the ext entries)
         uint8_t plan[64];
-        if (be_mf16_plan(d.nstate, plan)) { std::memcpy(sa.ldl_col0, plan, sizeof(plan)); sa.ldl_mf16 = 1; }
+        if (be_mf16_plan(d.nstate, plan)) { std::memcpy(sa.ldl_col0, plan, sizeof(plan)); sa.ldl_mf16 = w.ldl_barriers ? 2 : 1; }
     }
     // The first pass enqueues exactly max_iters slots: enough unless a linear solve failed (mu *= 10 retry) or a step was
     // invalid; be_solve_fused_end checks the downloaded control block and, in that rare case, runs the spare slots and the

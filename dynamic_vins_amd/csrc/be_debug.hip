@@ -80,6 +80,7 @@ int dv_debug_set(dv_ctx* ctx, const char* key, int value) {
     if (std::strcmp(key, "wait_tail") == 0) { ctx->be.debug_wait_tail = value != 0; return 0; }
     if (std::strcmp(key, "gpu_reject") == 0) { ctx->be.gpu_reject = value != 0; return 0; }      // 0: OutliersRejection on the host (rounds 1-3 until be_reject_kernel)
     if (std::strcmp(key, "ldl_generic") == 0) { ctx->be.ldl_generic = value != 0; return 0; }      // the generic 4-wide panel LDL^T instead of the 16-wide MFMA form (A/B runs, agreement tests)
+    if (std::strcmp(key, "ldl_barriers") == 0) { ctx->be.ldl_barriers = value != 0; return 0; }      // the MF16 loop on workgroup barriers instead of the LDS-flag hand-off (single-window kernel: A/B runs, bit comparison)
     DV_FAIL(std::string("dv_debug_set: unknown key ") + key);
 }
 

@@ -79,7 +79,7 @@ struct BeSolveArgs {
     double* scale_l; double* diag_l; double* grad_l; double* gn_l;     // [nlm]
     int32_t* prior_col;     // [BE_MAX_STATE] prior index of each state column (-1 if absent)
     int32_t* col_kind; int32_t* col_frame; int32_t* col_comp;          // [n]
-    uint8_t ldl_col0[64]; int32_t ldl_mf16, ldl_pad;      // ldl_mf16 != 0: the 16-wide MFMA factorisation, its tile plan (be_mf16_plan, [16 waves][4 slots]) in ldl_col0; 0: the generic 4-wide panel form
+    uint8_t ldl_col0[64]; int32_t ldl_mf16, ldl_pad;      // ldl_mf16 != 0: the 16-wide MFMA factorisation (2: its loop on workgroup barriers, the A/B form of the single-window kernel), its tile plan (be_mf16_plan, [16 waves][4 slots]) in ldl_col0; 0: the generic 4-wide panel form
     BeShard sh;             // landmark sharding (on = 0: the whole window lives here)
     double xnorm2_extra;    // squared norm of inert free blocks (line blocks under zero sqrt_info) that count in the parameter-tolerance test
     BeExt xt;               // free extrinsic / td blocks (on = 0: constant, the default)

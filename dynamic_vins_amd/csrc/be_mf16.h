@@ -21,6 +21,42 @@ __device__ __forceinline__ double fast_rcp(double d) {      // v_rcp_f64 + two N
 __device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// LDS-flag hand-off: the DATAFLOW form of the window solve's factorisation loop (ldlt_mf16<DF = true>, be_solve.hip).  The barrier form passes two workgroup barriers per
+// block column; here a wave proceeds as soon as what IT reads has been written.  Two kinds of words in LDS, zeroed before the loop behind a barrier, only ever counted up,
+// never reset (a value left by an earlier step can satisfy no wait):
+//   dflag        = number of diagonal tiles finished: set to k + 1 by wave k once W_k (both images), D, 1 / D and y of block k are written;
+//   pcnt[k]      = number of panel tiles of column k written: every owner of a tile (I, k) adds 1 behind its fragment (the chain wave k + 1 for tile (k + 1, k) included);
+//                  full at NB - 1 - k.
+// Wait graph of step k (who waits on whom; every entry is produced by the same wave with the same instructions as in the barrier form):
+//   P(I, k)  panel of tile (I, k), any owner            waits  dflag >= k + 1         <- wave k, diagonal tile k
+//   U(k)     trailing update of a wave's tiles (J > k)  waits  pcnt[k] full           <- every P(., k)           (the chain wave's own update reads its registers only: no wait)
+//   D(k+1)   diagonal tile k + 1 on wave k + 1          waits  nothing for the factorisation; its LAST action, the panel-order image of W_k+1 (ONE image: it overwrites W_k's),
+//                                                        waits  pcnt[k] full           <- every P(., k) has READ W_k (an owner counts behind its panel, so behind its reads)
+// Order the events D(0) < P(., 0) < U(0), D(1) < P(., 1) < U(1), D(2) < ...: every wait points to an event strictly earlier in this order, and a wave runs its own events in this
+// order (P(., k), U(k), then step k + 1), so whatever a waiter waits on can never — directly or through other waves — wait on the waiter: the graph is acyclic.  The sixteen
+// waves of the workgroup are co-resident, so every wait ends.  One workgroup barrier behind the loop (the pivot check and the back substitution read every wave's output).
+// Release / acquire are spelled for LDS alone, like lds_barrier(): the producer drains its LDS operations (s_waitcnt lgkmcnt(0)) before the flag's store or add, a consumer's
+// reads are issued behind the poll that saw the value (one in-order LDS pipe per CU).  No vmcnt wait: global loads and stores stay in flight across a hand-off.
+#define MF_FLAGS 16      // [0] dflag, [1 + k] pcnt[k], k < MF_MAXNB
+__device__ __forceinline__ int mf_flag_peek(const int* f) { return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }      // the request only: the wait sits at the first use
+__device__ __forceinline__ void mf_flag_set(int* f, int v, int lane) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane == 0) __hip_atomic_store(f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void mf_flag_add(int* f, int v, int lane) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane == 0) __hip_atomic_fetch_add(f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// CHAIN: the wave the factorisation waits for polls back to back; everybody else sleeps 64 cycles between polls (they have a diagonal tile's time of slack and share the
+// chain waves' SIMDs and LDS pipe)
+template <bool CHAIN>
+__device__ __forceinline__ void mf_flag_wait(const int* f, int v, int seen = -1) {
+    int cur = __builtin_amdgcn_readfirstlane(seen);      // (seen: a value requested earlier with mf_flag_peek, or none)
+    while (cur < v) { cur = __builtin_amdgcn_readfirstlane(mf_flag_peek(f)); if (!CHAIN && cur < v) __builtin_amdgcn_s_sleep(1); }
+    asm volatile("" ::: "memory");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // MF16 — the same LDL^T re-blocked 16 wide on the f64 matrix cores (v_mfma_f64_16x16x4_f64).
 // Every experiment of rounds 1-2 ended at the same per-step cost (~1.2 us per barrier-separated 4-pivot step, 42 steps): so the steps become 11 sixteen-pivot
 // steps.  The (n+1) x (n+1) system — row n carries the right-hand side, so the forward substitution is part of the factorisation and row n of L is
@@ -36,7 +72,7 @@ __device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_fence(__ATOMI
 // substitution of ITS column (lane c holds A[p..p+3][c] = A[c][p..p+3]); ONE MFMA applies the rank-4 update to the tile and a second one the same elementary
 // block transformation to W (Gauss-Jordan: W <- L_q^-1 W), so that W_k = L_kk^-1 comes out of the factorisation.  Tile ownership (be_mf16_plan): wave j owns
 // diagonal tile j and only off-diagonal tiles of columns < j, so the wave that factors diagonal k+1 has no other tile to update in step k.
-// Two workgroup barriers per 16 pivots.  Same solution as ldlt_wavecol to rounding (different summation order): parity by tolerance (iteration sequences, 1e-6).
+// Two workgroup barriers per 16 pivots (mf16_factor_core, ldlt_mf16<false>) or none (ldlt_mf16<true>: the LDS-flag hand-off above).  Same solution as ldlt_wavecol to rounding (different summation order): parity by tolerance (iteration sequences, 1e-6).
 #define MF_SLOTS 5
 #define MF_MAXNB 11
 #define MF_RHO 1e300
@@ -104,8 +140,10 @@ __device__ __forceinline__ void mf_diag_substep(mf_d4& T, mf_d4& Wt, double* gat
     }
     if (lane == c0) { mf_d4 yy = { lh0, lh1, lh2, lh3 }; *reinterpret_cast<mf_d4*>(yk + P) = yy; }      // row c0 of L_kk = this block's share of y (zero from column c0 on: lh is masked)
 }
-template <bool RR = false>
-__device__ __forceinline__ void mf_diag_factor(mf_d4& T, const MfLds& m, int k, int NB, int n, int* s_fail) {
+// DF (dataflow form): img_cnt / img_need = the count that must be full before the panel-order image of W_k-1 may be overwritten (requested behind the first sub-step,
+// looked at in front of the image's stores: by then it has long been full, and the chain pays no LDS round trip for it)
+template <bool RR = false, bool DF = false>
+__device__ __forceinline__ void mf_diag_factor(mf_d4& T, const MfLds& m, int k, int NB, int n, int* s_fail, const int* img_cnt = nullptr, int img_need = 0) {
     const int lane = threadIdx.x & 63, c = lane & 15, rho = lane >> 4, wave = mf_wave();
     __builtin_amdgcn_s_setprio(3);
     mf_d4 Wt;
@@ -117,6 +155,8 @@ __device__ __forceinline__ void mf_diag_factor(mf_d4& T, const MfLds& m, int k, 
     // row (4 Q > c0) touches nothing that is read again — W stays the identity there, y is zero-initialised, the pivot check below looks at c < nv only — and is
     // skipped (n = 165: two of the last tile's four sub-steps, ~1.1 us per solve).
     mf_diag_substep<0, RR>(T, Wt, gat, m.dv + 16 * k, m.iv + 16 * k, c0, m.yv + 16 * k);
+    int img_seen = 0;
+    if (DF && img_need > 0) img_seen = mf_flag_peek(img_cnt);
     if (c0 < 0 || c0 >= 4) mf_diag_substep<1, RR>(T, Wt, gat, m.dv + 16 * k, m.iv + 16 * k, c0, m.yv + 16 * k);
     if (c0 < 0 || c0 >= 8) mf_diag_substep<2, RR>(T, Wt, gat, m.dv + 16 * k, m.iv + 16 * k, c0, m.yv + 16 * k);
     if (c0 < 0 || c0 >= 12) mf_diag_substep<3, RR>(T, Wt, gat, m.dv + 16 * k, m.iv + 16 * k, c0, m.yv + 16 * k);
@@ -124,7 +164,8 @@ __device__ __forceinline__ void mf_diag_factor(mf_d4& T, const MfLds& m, int k, 
     // ... and a second image in the PANEL's operand order (lane (rho, c) of a panel wave wants W[c][rho + 4 q], q = 0..3: here four consecutive doubles at lane * 4): the
     // transposing read of the result-layout image is a 4-way bank conflict, and all sixteen waves issue it in the same instant behind barrier A — the panel phase was
     // bound by the LDS pipe (0.8 us per step, phase stamps), not by its four MFMAs.  One wave pays the scattered WRITE once instead.  The image lives in the gather
-    // buffers of waves 12-15, idle during the factorisation (diagonal tiles belong to waves <= 10); one image at a time suffices: W_k is dead behind barrier B of step k.
+    // buffers of waves 12-15, idle during the factorisation (diagonal tiles belong to waves <= 10); one image at a time suffices: W_k is dead behind barrier B of step k (DF: once pcnt[k] is full).
+    if (DF && img_need > 0) mf_flag_wait<true>(img_cnt, img_need, img_seen);
     {
         double* wt = m.gat + 768;
 #pragma unroll

@@ -791,7 +791,9 @@ __device__ __forceinline__ void mf_prefetch(const double* __restrict__ Sc, const
 //                                                                 factor diagonal tile k+1, publish W_k+1  ->  A
 //   every other wave:                                             its panel tile of column k  ->  B  ->  trailing update of its tiles with panel k  ->  A
 // so the diagonal chain (the critical path) never waits for the other waves' panels or updates: they run beside it.
-template <class Side, class Side0>
+// DF: the same loop without the barriers — every wave proceeds on the LDS flags of be_mf16.h (wait graph there) and the workgroup meets once behind the loop.  Which wave
+// computes which entry, with which instructions on which operands, is the same in both forms: the results are equal bit for bit (tests/test_solve_dataflow.py).
+template <bool DF, class Side, class Side0>
 __device__ __forceinline__ bool ldlt_mf16(mf_d4 (&U)[MF_SLOTS], const uint8_t* plan, int n, double mu, const double* v_s, const double* v_d, const double* rhs, const MfLds& m, int* s_fail, Side side, Side0 side0) {
     const int tid = threadIdx.x, lane = tid & 63, wave = mf_wave(), c = lane & 15, rho = lane >> 4;      // wave in an SGPR: the slot tests below are scalar branches
     const int NB = (n + 16) >> 4, IB = n >> 4, c0 = n & 15;
@@ -818,15 +820,22 @@ __device__ __forceinline__ bool ldlt_mf16(mf_d4 (&U)[MF_SLOTS], const uint8_t* p
     TS(22);
     for (int i = tid; i < 16 * NB; i += SOL_THREADS) m.yv[i] = 0.0;
     if (tid == 0) *s_fail = 0;
+    __shared__ int s_mf_flag[DF ? MF_FLAGS : 1];
+    if (DF && tid < MF_FLAGS) s_mf_flag[tid] = 0;
 #ifdef BE_SOLVE_TS
     if (tid == 0) { be_dbg_ts[19] = 0; be_dbg_ts[20] = 0; be_dbg_ts[32] = 0; be_dbg_ts[33] = 0; be_dbg_ts[34] = 0; be_dbg_ts[35] = 0; }
 #endif
     lds_barrier();
     TS(4);
     const int k_side = -1; // (NB >= 9 ? 6 : -1: the side work inside the loop costs 70 spilled VGPRs)                 // the step whose slack takes the side work (small systems: beside the first diagonal tile)
-    if (wave == 0) { mf_diag(U[0], m, 0, NB, n, s_fail); if (k_side < 0) side0(); }
+    int* const dflag = s_mf_flag; int* const pcnt = s_mf_flag + (DF ? 1 : 0);
+    if (wave == 0) {
+        mf_diag_factor<false, DF>(U[0], m, 0, NB, n, s_fail);
+        if (DF) mf_flag_set(dflag, 1, lane);             // W_0 published (before this wave's side work: nobody waits for that)
+        if (k_side < 0) side0();
+    }
     else if (k_side < 0) side(0);
-    lds_barrier();                                       // A: W_0 published
+    if (!DF) lds_barrier();                              // A: W_0 published
 #ifdef BE_SOLVE_TS
     long long t_prev = wall_clock64(), acc_panel = 0, acc_update = 0;
     if (tid == 0) be_dbg_ts[16] = t_prev - be_dbg_ts[4];      // load + first diagonal tile
@@ -851,6 +860,66 @@ __device__ __forceinline__ bool ldlt_mf16(mf_d4 (&U)[MF_SLOTS], const uint8_t* p
         }
         return Y0;
     };
+    if constexpr (DF) {
+    for (int k = 0; k + 1 < NB; ++k) {
+        const int np_col = NB - 1 - k;                   // panel tiles of column k
+        if (wave == k + 1) {
+            // ---- the diagonal chain ----
+#ifdef BE_SOLVE_TS
+            const long long t_w = wall_clock64();
+#endif
+            mf_flag_wait<true>(dflag, k + 1);            // W_k, 1 / D_k
+            __builtin_amdgcn_s_setprio(3);
+#ifdef BE_SOLVE_TS
+            const long long t_c0 = wall_clock64();
+#endif
+            const mf_d4 Y0 = panel(U[1], k + 1, k);
+#ifdef BE_SOLVE_TS
+            __builtin_amdgcn_s_waitcnt(0xc07f); const long long t_c1 = wall_clock64();
+#endif
+#pragma unroll
+            for (int q = 0; q < 4; ++q) U[0] = mf_mfma(U[1][q], -Y0[q], U[0]);
+#ifdef BE_SOLVE_TS
+            asm volatile("s_nop 15\n\ts_nop 3\n\tv_mov_b64 %0, %0" : "+v"(U[0][0])); const long long t_c2 = wall_clock64();
+#endif
+            mf_flag_add(pcnt + k, 1, lane);              // tile (k+1, k) written (behind the update's MFMAs: the fragment's store has landed by then)
+#ifdef BE_SOLVE_TS
+            const long long t_u = wall_clock64();
+            if (lane == 0) { be_dbg_ts[32] += t_c0 - t_w; be_dbg_ts[33] += t_c1 - t_c0; be_dbg_ts[34] += t_c2 - t_c1; be_dbg_ts[35] += t_u - t_c2; }
+#endif
+            mf_diag_factor<false, true>(U[0], m, k + 1, NB, n, s_fail, pcnt + k, np_col);
+            mf_flag_set(dflag, k + 2, lane);
+#ifdef BE_SOLVE_TS
+            if (lane == 0) { be_dbg_ts[19] += wall_clock64() - t_u; be_dbg_ts[20] += t_u - t_c0; }
+#endif
+        } else {
+            // ---- everybody else: panel tile of column k behind W_k, the trailing update behind the column's panels; a wave without either passes through ----
+            int np = 0; bool upd = false;
+#pragma unroll
+            for (int s = 0; s < MF_SLOTS; ++s) { np += (s >= 1 && sJ[s] == k) ? 1 : 0; upd = upd || sJ[s] > k; }
+            if (np) {
+                mf_flag_wait<false>(dflag, k + 1);
+#pragma unroll
+                for (int s = 1; s < MF_SLOTS; ++s) if (sJ[s] == k) panel(U[s], sI[s], k);
+                mf_flag_add(pcnt + k, np, lane);
+            }
+            if (upd) {
+                mf_flag_wait<false>(pcnt + k, np_col);
+                double dk[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) dk[q] = -m.dv[16 * k + rho + 4 * q];
+#pragma unroll
+                for (int s = 0; s < MF_SLOTS; ++s) if (sJ[s] > k) {
+                    const mf_d4 a = *reinterpret_cast<const mf_d4*>(m.Tl + (size_t)mf_tix(sJ[s], k, NB) * 256 + lane * 4);
+                    const mf_d4 b = *reinterpret_cast<const mf_d4*>(m.Tl + (size_t)mf_tix(sI[s], k, NB) * 256 + lane * 4);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) U[s] = mf_mfma(a[q], dk[q] * b[q], U[s]);
+                }
+            }
+        }
+    }
+    lds_barrier();                                       // the one meeting point: every D, every fragment, y
+    } else
     for (int k = 0; k + 1 < NB; ++k) {
         if (wave == k + 1) {
             // ---- the diagonal chain: slot 1 of this wave is tile (k+1, k) ----
@@ -1064,20 +1133,21 @@ __device__ __forceinline__ void bs_rows(const double* Lm, int kt, int lane, doub
 
 // The body lives in be_solve_body.inc and is included textually: called through a function taking `const BeSolveArgs&` the single-window kernel lost 4 %
 // (99.2 vs 95.2 us; the by-value kernel arguments stopped being treated as invariant scalar loads).
-template <int NSLOT, bool MF16>
+// BARRIERS (MF16 only): the factorisation loop with two workgroup barriers per block column instead of the LDS-flag hand-off (dv_debug_set "ldl_barriers": A/B runs, bit comparison)
+template <int NSLOT, bool MF16, bool BARRIERS = false>
 __global__ __launch_bounds__(SOL_THREADS) void be_solve_kernel(BeSolveArgs a, int spec) {
-    constexpr bool SHARD = false;
+    constexpr bool SHARD = false, MF_DF = MF16 && !BARRIERS;
 #include "be_solve_body.inc"
 }
 template <int NSLOT, bool MF16>
 __global__ __launch_bounds__(SOL_THREADS) void be_solve_batch_kernel(const BeSolveArgs* __restrict__ tab, int spec) {      // one workgroup per window
     const BeSolveArgs& a = tab[blockIdx.x];
-    constexpr bool SHARD = false;
+    constexpr bool SHARD = false, MF_DF = MF16;
 #include "be_solve_body.inc"
 }
 // one window sharded by landmark (be_kernels.h BeShard): the same step on every rank, landmark sums from the exchanged forms, the rank's own landmarks moved
 __global__ __launch_bounds__(SOL_THREADS) void be_solve_shard_kernel(BeSolveArgs a, int spec) {
-    constexpr int NSLOT = 1; constexpr bool MF16 = true, SHARD = true;
+    constexpr int NSLOT = 1; constexpr bool MF16 = true, SHARD = true, MF_DF = false;      // (the sharded step stays on the barrier loop: its code is the one it was)
 #include "be_solve_body.inc"
 }
 
@@ -1118,6 +1188,7 @@ int be_launch_solve(const BeSolveArgs& a, int spec, hipStream_t s) {
     if (once.run([] {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(be_solve_kernel<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_smem(BE_MAX_STATE)) != hipSuccess) return 1;
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(be_solve_kernel<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_smem(BE_MAX_STATE)) != hipSuccess) return 1;
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(be_solve_kernel<1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess) return 1;
             return hipFuncSetAttribute(reinterpret_cast<const void*>(be_solve_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess ? 1 : 0; })) return -1;      // 160 KB per workgroup less the kernel's static arrays
     const int nbr = (a.dims.nstate + 3) / 4;
     if (a.sh.on) {
@@ -1127,7 +1198,8 @@ int be_launch_solve(const BeSolveArgs& a, int spec, hipStream_t s) {
         hipLaunchKernelGGL(be_solve_shard_kernel, dim3(1), dim3(SOL_THREADS), solve_smem_mf16(a.dims.nstate), s, a, spec);
         return 0;
     }
-    if (a.ldl_mf16) hipLaunchKernelGGL((be_solve_kernel<1, true>), dim3(1), dim3(SOL_THREADS), solve_smem_mf16(a.dims.nstate), s, a, spec);
+    if (a.ldl_mf16 == 2) hipLaunchKernelGGL((be_solve_kernel<1, true, true>), dim3(1), dim3(SOL_THREADS), solve_smem_mf16(a.dims.nstate), s, a, spec);      // "ldl_barriers"
+    else if (a.ldl_mf16) hipLaunchKernelGGL((be_solve_kernel<1, true>), dim3(1), dim3(SOL_THREADS), solve_smem_mf16(a.dims.nstate), s, a, spec);
     else if (nbr * (nbr + 1) / 2 <= SOL_THREADS) hipLaunchKernelGGL((be_solve_kernel<1, false>), dim3(1), dim3(SOL_THREADS), solve_smem(a.dims.nstate), s, a, spec);
     else hipLaunchKernelGGL((be_solve_kernel<2, false>), dim3(1), dim3(SOL_THREADS), solve_smem(a.dims.nstate), s, a, spec);
     return 0;

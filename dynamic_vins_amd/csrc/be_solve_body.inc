@@ -253,7 +253,7 @@
         TS(3);
         // ---------------- Gauss-Newton step: LDL^T of the Schur complement ----------------
         bool ok_f;
-        if (MF16) ok_f = ldlt_mf16(mfU, reinterpret_cast<const uint8_t*>(a.ldl_col0), n, mu, v_s, v_d, v_x, mf, &s_fail, [&](int excl) { side_sums(tid < 64 * excl ? tid : tid - 64, SOL_THREADS - 64, false); },
+        if (MF16) ok_f = ldlt_mf16<MF_DF>(mfU, reinterpret_cast<const uint8_t*>(a.ldl_col0), n, mu, v_s, v_d, v_x, mf, &s_fail, [&](int excl) { side_sums(tid < 64 * excl ? tid : tid - 64, SOL_THREADS - 64, false); },
                                    [&]() { lm_diag_own(); if ((tid & 63) == 0) { red[tid >> 6] = 0.0; red[16 + (tid >> 6)] = 0.0; } });
         else ok_f = ldlt_blocked<NSLOT>(a.Sc[c.cur], gvec, n, mu, v_s, v_d, Lm, PL, PD, dinfo, zfin, dvec, &s_fail);
         if (!ok_f) {
