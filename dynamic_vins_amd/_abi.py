@@ -92,6 +92,8 @@ SIGNATURES = {
     "dv_box_orientation_eval": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "dv_inst_proj_eval": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dv_obj_solve": (C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
+    "dv_batch_obj_solve": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
+    "dv_batch_obj_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "dv_line_solve": (C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
     "dv_est_create": (C.c_int, [_ctx, C.c_void_p]),
     "dv_est_reset": (C.c_int, [_ctx]),
@@ -152,6 +154,7 @@ SIGNATURES = {
     "dv_runner_dynamic_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "dv_runner_set": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "dv_runner_track_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "dv_runner_get_batches": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]),
     "dv_runner_error": (C.c_char_p, [C.c_void_p]),
     "dv_est_get_marg_health": (C.c_int, [_ctx, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p]),
     "dv_set_marg_form": (C.c_int, [_ctx, C.c_int]),

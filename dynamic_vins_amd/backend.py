@@ -522,6 +522,23 @@ class Batch:
         self.lib.dv_batch_track_info(self.h, C.byref(a), C.byref(b), C.byref(c))
         return dict(rounds=a.value, members_batched=b.value, members_single=c.value)
 
+    def obj_solve(self, members, probs):
+        """dv_batch_obj_solve: probs[i] (ObjProblem, or None for a NULL problem) solved on member members[i], all in one launch; the problems are updated in place.
+        -> list of dv_ba_summary"""
+        n = len(members)
+        structs = [None if p is None else p.struct() for p in probs]
+        ptrs = (C.c_void_p * max(n, 1))(*[None if s is None else C.addressof(s) for s in structs])
+        mem = (C.c_int * max(n, 1))(*[int(m) for m in members])
+        out = (dv_ba_summary * max(n, 1))()
+        if self.lib.dv_batch_obj_solve(self.h, mem, ptrs, n, C.cast(out, C.c_void_p)) != 0:
+            raise DvinsError((self.lib.dv_last_error(self.ctxs[0].h) or self.lib.dv_last_error(None) or b"dv_batch_obj_solve failed").decode())
+        return list(out[:n])
+
+    def obj_info(self):
+        a, b, c = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        self.lib.dv_batch_obj_info(self.h, C.byref(a), C.byref(b), C.byref(c))
+        return dict(launches=a.value, jobs=b.value, single=c.value)
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.dv_batch_destroy(self.h)
@@ -658,6 +675,17 @@ class Runner:
         a, b, c = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
         self.lib.dv_runner_track_info(self.h, C.byref(a), C.byref(b), C.byref(c))
         return dict(rounds=a.value, members_batched=b.value, members_single=c.value)
+
+    def obj_rounds(self):
+        """object solves of the groups' dynamic members: shared launches, the jobs in them, solves launched alone (dv_batch_obj_info summed over the groups)"""
+        hs = (C.c_void_p * 4096)(); n = C.c_int(0)
+        self.lib.dv_runner_get_batches(self.h, hs, 4096, C.byref(n))
+        tot = dict(launches=0, jobs=0, single=0)
+        for k in range(min(n.value, 4096)):
+            a, b, c = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+            self.lib.dv_batch_obj_info(hs[k], C.byref(a), C.byref(b), C.byref(c))
+            tot["launches"] += a.value; tot["jobs"] += b.value; tot["single"] += c.value
+        return tot
 
     def batch_timing(self, on=1):
         """-> (avg ms per launch of [be_solve_batch, be_eval_batch, be_reduce_batch], rounds timed, windows per launch)"""

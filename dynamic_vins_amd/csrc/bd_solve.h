@@ -126,8 +126,11 @@ __device__ __forceinline__ bool gn6(const double* H, const double* g, const doub
 }
 
 
+// The whole solve of ONE problem by ONE workgroup: the body of bd_solve_kernel and of bd_solve_group_kernel.  It touches nothing outside prob / a, its static exchange array s_red
+// and (a.lds != 0 only) the first bd_lds_bytes(a.V) bytes of the dynamic region bd_lds; shared memory is indexed by threadIdx alone, every branch hangs on a workgroup-wide
+// reduction, so workgroups of one grid that run it on different problems never meet.
 template <class Prob>
-__global__ __launch_bounds__(BD_THREADS) void bd_solve_kernel(Prob prob, BdArgs a) {
+__device__ __forceinline__ void bd_solve_body(const Prob& prob, const BdArgs& a) {
     __shared__ double s_red[5 * BD_NW];          // block_sum<5> is the widest exchange (it used to be 4 * BD_NW: the fifth value's partials were written past the array — harmless while nothing
                                                   // else lived in LDS, the first state block of the LDS-resident working set otherwise)
     extern __shared__ __attribute__((aligned(16))) double bd_lds[];
@@ -283,6 +286,22 @@ __global__ __launch_bounds__(BD_THREADS) void bd_solve_kernel(Prob prob, BdArgs 
         const double o5[5] = { (double)iterations, (double)successful, (double)termination, initial_cost, x_cost };
         for (int k = 0; k < 5; ++k) { a.out[k] = o5[k]; if (a.h_out) a.h_out[k] = o5[k]; }
     }
+}
+
+template <class Prob>
+__global__ __launch_bounds__(BD_THREADS) void bd_solve_kernel(Prob prob, BdArgs a) {
+    bd_solve_body(prob, a);
+}
+
+// Several independent problems in ONE launch (the object solves of a dv_batch round, be_objsolve.hip): grid = jobs, workgroup b solves jobs[b] and nothing else — no atomics, no
+// flags, no word shared between two workgroups; each ends at its own iteration count and writes its own a.out / a.h_x / a.h_out.  The job is read through a pointer indexed by
+// blockIdx.x alone and copied by value before anything is stored: the loads are wave-uniform (scalar loads into SGPRs, like the single kernel's kernel arguments) and happen once.
+// The launch's dynamic LDS is the largest bd_lds_bytes over the jobs with a.lds != 0; a job with a.lds == 0 keeps its working set in HBM and leaves the dynamic region alone.
+template <class Prob> struct BdJob { Prob prob; BdArgs a; };
+template <class Prob>
+__global__ __launch_bounds__(BD_THREADS) void bd_solve_group_kernel(const BdJob<Prob>* __restrict__ jobs) {
+    const BdJob<Prob> job = jobs[blockIdx.x];
+    bd_solve_body(job.prob, job.a);
 }
 
 

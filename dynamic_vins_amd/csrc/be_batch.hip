@@ -22,8 +22,45 @@ struct dv_batch {
     // the accept decision), on the batch stream they are launched on; harvested when the next round starts (the events of the previous round have completed by then)
     bool timing = false; hipEvent_t tev[4] = { nullptr, nullptr, nullptr, nullptr }; bool tev_pending = false;
     double t_ms[3] = { 0, 0, 0 }; long long t_n = 0; int t_windows = 0;
+    // the members' object solves (dynamic members; dv_batch_obj_solve): their uploads and ONE bd_solve_group_kernel launch per round on the group's object stream, beside the
+    // window solves on `stream`.  Job table: pinned block -> HBM per launch, double-buffered (ev_obj_copy[k] behind the upload that last read pinned block k); ev_obj behind the launch
+    // All of it is created by the FIRST object solve that comes the group's way (obj_ensure): a group without dynamic members owns exactly the streams it always did — one more
+    // stream per group shifts the runtime's round-robin of streams onto hardware queues for every stream created after it, and 16 raw sequences in four groups lost a third
+    // of their rate to that (7100 -> 4700 frames/s, measured)
+    std::mutex obj_mu; int device = 0; size_t obj_cap = 0;
+    hipStream_t obj_stream = nullptr; hipEvent_t ev_obj = nullptr, ev_obj_copy[2] = { nullptr, nullptr };
+    DevBuf obj_tab[2]; void* obj_tab_pinned[2] = { nullptr, nullptr }; int obj_parity = 0; bool obj_copy_used[2] = { false, false };
+    long long obj_launches = 0, obj_jobs = 0, obj_single = 0;      // shared launches, the jobs in them, solves launched alone (dv_batch_obj_info)
 };
 DvFrontBatch*& be_batch_front(dv_batch* B) { return B->front; }
+static void obj_release(dv_batch* B) {
+    if (B->obj_stream) (void)hipStreamDestroy(B->obj_stream);
+    if (B->ev_obj) (void)hipEventDestroy(B->ev_obj);
+    B->obj_stream = nullptr; B->ev_obj = nullptr;
+    for (int k = 0; k < 2; ++k) { if (B->ev_obj_copy[k]) (void)hipEventDestroy(B->ev_obj_copy[k]); B->ev_obj_copy[k] = nullptr; B->obj_tab[k].release(); if (B->obj_tab_pinned[k]) (void)hipHostFree(B->obj_tab_pinned[k]); B->obj_tab_pinned[k] = nullptr; }
+}
+// the group's object stream, its events and job tables: created on first use (members' threads of a team may come here together)
+static bool obj_ensure(dv_batch* B) {
+    std::lock_guard<std::mutex> lk(B->obj_mu);
+    if (B->obj_stream) return true;
+    const size_t bytes = B->obj_cap * be_obj_job_bytes();
+    bool ok = hipSetDevice(B->device) == hipSuccess && hipEventCreateWithFlags(&B->ev_obj, hipEventDisableTiming) == hipSuccess;
+    for (int k = 0; k < 2; ++k)
+        ok = ok && hipEventCreateWithFlags(&B->ev_obj_copy[k], hipEventDisableTiming) == hipSuccess && B->obj_tab[k].ensure(bytes) == hipSuccess &&
+             hipHostMalloc(&B->obj_tab_pinned[k], bytes, hipHostMallocDefault) == hipSuccess;
+    hipStream_t s = nullptr;
+    ok = ok && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess;
+    if (!ok) { obj_release(B); return false; }
+    B->obj_stream = s;
+    return true;
+}
+hipStream_t be_batch_obj_stream(dv_batch* B) { return obj_ensure(B) ? B->obj_stream : nullptr; }      // nullptr: out of resources — the caller keeps its own stream and launch
+// a member leaves (dv_destroy, dv_batch_destroy) with an object solve on the group's object stream — drained by the caller: the upload has landed, a launched solve has
+// written its result — so what is left of it no longer needs the group: a deferred job is launched on the member's own stream when it is collected, a launched one has no event to wait for
+static void obj_member_leaves(dv_ctx* c) {
+    for (ObjPending* p : { &c->obj_pend, &c->obj_op_pend }) { p->ev_ext = nullptr; p->stream = c->obj_stream; }
+    c->be.pend->ev_state_ext = nullptr;      // the same for a window solve inside a shared round: the group's event goes with the group (its stream is drained: the states have landed)
+}
 const std::vector<dv_ctx*>& be_batch_members(dv_batch* B) { return B->members; }
 // dv_destroy of a member: the batch forgets it (a destroyed ctx must never be reached through B->members); threads waiting in dv_batch_arrive
 // for a round this member will never join are released with an error
@@ -35,6 +72,8 @@ void be_batch_detach(dv_ctx* ctx) {
         B->members.erase(std::remove(B->members.begin(), B->members.end(), ctx), B->members.end());
         ctx->batch = nullptr;
         if (B->stream) (void)hipStreamSynchronize(B->stream);
+        if (B->obj_stream) (void)hipStreamSynchronize(B->obj_stream);      // an uploaded (deferred) or launched object solve of this member reads / writes its buffers
+        obj_member_leaves(ctx);
         dv_front_batch_sync(B->front);
         if (ctx->be_stream_own) { ctx->be_stream = ctx->be_stream_own; ctx->be_stream_own = nullptr; }
         if (B->arrived > 0) { B->last_rc = -1; B->arrived = 0; ++B->generation; dv_set_error(nullptr, "dv_batch_arrive: a member was destroyed during the round"); }
@@ -75,7 +114,36 @@ struct BeGroupStages {
     int exchange_system(int) { return 0; } int exchange_cost() { return 0; } int gather_depth() { return 0; }
 };
 
+// The object solves the members' object branches left deferred (est_host.hip dynamic_branch -> be_obj_solve_begin with defer): one job table, one launch, one event.
+// `which` picks the estimator's ObjPending (dv_batch_enqueue) or the operator-level one (dv_batch_obj_solve).
+static int batch_enqueue_objects(dv_batch* B, const std::vector<dv_ctx*>& M, ObjPending dv_ctx::* which) {
+    if (M.empty()) return 0;
+    dv_ctx* ctx = M[0];
+    if (M.size() == 1) {      // nothing to share: the member's own single-workgroup launch
+        B->obj_single++;
+        if (be_obj_solve_launch(M[0], M[0]->*which)) return -1;
+        return 0;
+    }
+    DV_CHECK(hipSetDevice(ctx->cfg.device));
+    const int par = B->obj_parity; B->obj_parity ^= 1;
+    if (B->obj_copy_used[par]) DV_CHECK(hipEventSynchronize(B->ev_obj_copy[par]));      // the upload that last read this pinned block (two launches ago) has run
+    std::vector<ObjPending*> pends;
+    for (dv_ctx* c : M) pends.push_back(&(c->*which));
+    if (be_obj_solve_group_launch(ctx, pends.data(), (int)pends.size(), B->obj_tab_pinned[par], B->obj_tab[par].p, B->obj_stream, B->ev_obj)) return -1;
+    DV_CHECK(hipEventRecord(B->ev_obj_copy[par], B->obj_stream)); B->obj_copy_used[par] = true;
+    B->obj_launches++; B->obj_jobs += (long long)M.size();
+    return 0;
+}
+static int batch_enqueue_windows(dv_batch* B);
+// a round: the window solves' slots and tails on the group's stream, then — beside them, on the group's object stream — the object solves of the dynamic members
 static int batch_enqueue_impl(dv_batch* B) {
+    if (batch_enqueue_windows(B)) return -1;
+    std::vector<dv_ctx*> O;
+    for (dv_ctx* c : B->members) if (c->obj_pend.active && c->obj_pend.deferred) O.push_back(c);
+    if (!O.empty() && batch_enqueue_objects(B, O, &dv_ctx::obj_pend)) { if (O[0] != B->members[0]) dv_set_error(B->members[0], O[0]->err); return -1; }
+    return 0;
+}
+static int batch_enqueue_windows(dv_batch* B) {
     std::vector<dv_ctx*> M;
     for (dv_ctx* c : B->members) if (c->be.pend->active && c->be.pend->deferred && !c->be.pend->trivial) M.push_back(c);
     if (M.empty()) return 0;
@@ -166,6 +234,7 @@ dv_batch* dv_batch_create(dv_ctx* const* ctxs, int n) {
     const size_t bytes = (size_t)n * (sizeof(BeEvalArgs) + sizeof(BeSolveArgs) + sizeof(BeGaugeArgs) + sizeof(BeRejectArgs) + sizeof(BeMargArgs));
     B->tab_bytes = bytes;
     ok = ok && B->tab.ensure(bytes) == hipSuccess && hipHostMalloc(&B->tab_pinned, bytes, hipHostMallocDefault) == hipSuccess;
+    B->device = ctxs[0]->cfg.device; B->obj_cap = (size_t)n;
     if (!ok) { dv_set_error(nullptr, "dv_batch_create: out of resources"); B->members.clear(); dv_batch_destroy(B); return nullptr; }
     // from now on the batch's stream IS every member's BA stream: uploads, window solves (shared or alone), tails and marginalizations of all members are ordered on
     // it — one hardware queue per group instead of one per member (48 streams on 12 queues made unrelated launches wait behind each other's event waits)
@@ -179,11 +248,13 @@ dv_batch* dv_batch_create(dv_ctx* const* ctxs, int n) {
 void dv_batch_destroy(dv_batch* B) {
     if (!B) return;
     if (B->stream) (void)hipStreamSynchronize(B->stream);
-    { std::lock_guard<std::mutex> lk(B->mu); for (dv_ctx* c : B->members) if (c->batch == B) { c->batch = nullptr; if (c->be_stream_own) { c->be_stream = c->be_stream_own; c->be_stream_own = nullptr; } } B->members.clear(); }
+    if (B->obj_stream) (void)hipStreamSynchronize(B->obj_stream);
+    { std::lock_guard<std::mutex> lk(B->mu); for (dv_ctx* c : B->members) if (c->batch == B) { obj_member_leaves(c); c->batch = nullptr; if (c->be_stream_own) { c->be_stream = c->be_stream_own; c->be_stream_own = nullptr; } } B->members.clear(); }
     if (B->front) { dv_front_batch_release(B->front); B->front = nullptr; }
     if (B->stream) (void)hipStreamDestroy(B->stream);
     if (B->ev_state) (void)hipEventDestroy(B->ev_state);
     for (hipEvent_t e : B->tev) if (e) (void)hipEventDestroy(e);
+    obj_release(B);
     B->tab.release();
     if (B->tab_pinned) (void)hipHostFree(B->tab_pinned);
     delete B;
@@ -230,6 +301,43 @@ int dv_batch_timing(dv_batch* B, int on, double* out3, long long* rounds, int* w
     if (out3) for (int k = 0; k < 3; ++k) out3[k] = B->t_n ? B->t_ms[k] / (double)B->t_n : 0.0;
     if (rounds) *rounds = B->t_n;
     if (windows) *windows = B->t_windows;
+    return 0;
+}
+// InstanceManager::Optimization (estimator/estimator_insts.cpp:772-807) of several members at once: problems[i] solved on member members[i], all in ONE launch
+// (bd_solve_group_kernel, one workgroup per problem) on the group's object stream; every result carries the bits dv_obj_solve gives for the same problem.  All problems are
+// checked and packed before anything is enqueued: one bad problem fails the call with dv_obj_solve's message (on its member and on the first member) and nothing is launched.
+int dv_batch_obj_solve(dv_batch* B, const int* members, dv_obj_problem* const* problems, int n, dv_ba_summary* summaries) {
+    if (!B) return -1;
+    dv_ctx* first = B->members.empty() ? nullptr : B->members[0];
+    auto bad = [&](dv_ctx* c, const std::string& m) { if (c && c != first) dv_set_error(c, m); dv_set_error(first, m); return -1; };
+    if (!members || !problems || !summaries || n < 1) return bad(nullptr, "dv_obj_solve: null argument");
+    if (!obj_ensure(B)) return bad(nullptr, "dv_batch_obj_solve: out of resources");
+    std::vector<dv_ctx*> M;
+    for (int i = 0; i < n; ++i) {
+        if (members[i] < 0 || members[i] >= (int)B->members.size()) return bad(nullptr, "dv_batch_obj_solve: member index out of range");
+        dv_ctx* c = B->members[members[i]];
+        if (std::find(M.begin(), M.end(), c) != M.end()) return bad(c, "dv_batch_obj_solve: a member is listed twice (one object solve per member and launch)");
+        if (!problems[i]) return bad(c, "dv_obj_solve: null argument");
+        M.push_back(c);
+    }
+    for (int i = 0; i < n; ++i) if (be_obj_solve_pack(M[i], problems[i], M[i]->s1, M[i]->obj_op_pend)) return bad(M[i], M[i]->err);      // (nothing enqueued yet: the packed ones are simply dropped)
+    int rc = 0;
+    for (int i = 0; i < n && !rc; ++i) { ObjPending& p = M[i]->obj_op_pend; rc = be_obj_solve_upload(M[i], B->obj_stream, M[i]->s1, p); if (!rc) { p.deferred = true; p.active = true; } }
+    if (!rc) rc = batch_enqueue_objects(B, M, &dv_ctx::obj_op_pend);
+    if (rc) {      // a runtime failure half way: drain what was enqueued, drop the solves
+        (void)hipStreamSynchronize(B->obj_stream);
+        std::string m; for (dv_ctx* c : M) { if (m.empty() && !c->err.empty()) m = c->err; c->obj_op_pend.active = c->obj_op_pend.deferred = false; c->obj_op_pend.ev_ext = nullptr; }
+        return bad(nullptr, m.empty() ? "dv_batch_obj_solve: launch failed" : m);
+    }
+    for (int i = 0; i < n; ++i) if (be_obj_solve_end(M[i], problems[i], &summaries[i], M[i]->obj_op_pend)) return bad(M[i], M[i]->err);
+    return 0;
+}
+// shared object-solve launches of the group so far (dv_batch_enqueue rounds and dv_batch_obj_solve calls), the jobs in them, and the solves that were launched alone
+int dv_batch_obj_info(dv_batch* B, long long* launches, long long* jobs, long long* single) {
+    if (!B) return -1;
+    if (launches) *launches = B->obj_launches;
+    if (jobs) *jobs = B->obj_jobs;
+    if (single) *single = B->obj_single;
     return 0;
 }
 int dv_batch_info(dv_batch* B, long long* batched_rounds, long long* single_rounds) {

@@ -164,9 +164,20 @@ struct ObjProb {
 }  // namespace
 
 
-// internal two-phase form: the estimator's dynamic branch enqueues the object solve on its own stream + scratch buffer (pinned staging for both
-// directions, no host synchronisation) so that it runs beside the window solve; _end waits for its event and unpacks
-int be_obj_solve_begin(dv_ctx* ctx, dv_obj_problem* P, hipStream_t s, DevBuf& scratch, ObjPending& pend) {
+// A dv_batch member's object solve (the estimator's object branch, dv_batch_obj_solve) stops after the upload: `pend.job` holds the kernel's arguments, the launch comes from
+// dv_batch_enqueue — ONE bd_solve_group_kernel for the jobs of all members (be_obj_solve_group_launch) — or from be_obj_solve_end if nobody enqueued it.
+using ObjJob = BdJob<ObjProb>;
+static_assert(sizeof(ObjJob) <= sizeof(ObjPending::job) && alignof(ObjJob) <= 16, "ObjPending::job holds a BdJob<ObjProb>");
+static int obj_kernel_attrs() {      // both instantiations take up to BD_LDS_MAX of dynamic LDS: set once per process (and by be_obj_solve_prepare, so that no frame does it)
+    static DevOnce once;
+    return once.run([] {
+        return (hipFuncSetAttribute(reinterpret_cast<const void*>(bd_solve_kernel<ObjProb>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BD_LDS_MAX) != hipSuccess ||
+                hipFuncSetAttribute(reinterpret_cast<const void*>(bd_solve_group_kernel<ObjProb>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BD_LDS_MAX) != hipSuccess) ? 1 : 0; });
+}
+size_t be_obj_job_bytes() { return sizeof(ObjJob); }
+
+// pack: argument checks, the problem bucketed by variable block into the pinned staging block, the device scratch sized, the kernel's arguments in pend.job.  Host work only.
+int be_obj_solve_pack(dv_ctx* ctx, dv_obj_problem* P, DevBuf& scratch, ObjPending& pend) {
     if (!ctx) return -1;
     if (pend.active) DV_FAIL("dv_obj_solve: previous object solve not collected");
     if (!P) DV_FAIL("dv_obj_solve: null argument");
@@ -233,7 +244,6 @@ int be_obj_solve_begin(dv_ctx* ctx, dv_obj_problem* P, hipStream_t s, DevBuf& sc
 
     if (scratch.ensure(std::max<size_t>(off, (size_t)8 << 20)) != hipSuccess) DV_FAIL("dv_obj_solve: out of device memory");      // (floor: a hipFree + hipMalloc per growth step is a device-wide synchronisation)
     uint8_t* base = (uint8_t*)scratch.p;
-    DV_CHECK(dv_copy_async(base, host.data(), up_bytes, s));      // pinned -> HBM by a kernel on the object stream (copy.hip)
     BdArgs a{};          // (x1 <- x0 and the zeroing of H | vec are the kernel's own first phase: two enqueued operations less in front of it)
     a.V = V; a.max_iters = P->max_iters;
     a.x0 = (double*)(base + o_x0); a.x1 = (double*)(base + o_x1); a.H0 = (double*)(base + o_H0); a.H1 = (double*)(base + o_H1); a.vec = (double*)(base + o_vec);
@@ -247,15 +257,53 @@ int be_obj_solve_begin(dv_ctx* ctx, dv_obj_problem* P, hipStream_t s, DevBuf& sc
     a.h_x = (double*)dl; a.h_out = (double*)(dl + 8 * 7 * (size_t)V);
     const size_t lds = bd_lds_bytes(V);
     a.lds = lds <= BD_LDS_MAX ? 1 : 0;          // up to 10 objects the whole working set lives in LDS (bd_solve.h); larger problems keep it in HBM
+    ObjJob job{ pr, a };
+    std::memcpy(pend.job, &job, sizeof(job));
+    pend.lds_bytes = a.lds ? lds : 0;
+    pend.V = V; pend.nblk = nblk; pend.n_obj = n_obj; pend.up_bytes = up_bytes; pend.deferred = false; pend.ev_ext = nullptr;
+    return 0;
+}
+// upload: the packed block, pinned -> HBM by a kernel on s (copy.hip); s is the stream the solve will be launched on
+int be_obj_solve_upload(dv_ctx* ctx, hipStream_t s, DevBuf& scratch, ObjPending& pend) {
+    DV_CHECK(dv_copy_async(scratch.p, pend.pinned, pend.up_bytes, s));
+    pend.stream = s;
+    return 0;
+}
+// launch: one persistent workgroup on the upload's stream, the solve's own event behind it
+int be_obj_solve_launch(dv_ctx* ctx, ObjPending& pend) {
+    ObjJob job; std::memcpy(&job, pend.job, sizeof(job));
+    hipStream_t s = pend.stream;
+    pend.deferred = false; pend.ev_ext = nullptr;
     {
-        static DevOnce once;
-        if (once.run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(bd_solve_kernel<ObjProb>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BD_LDS_MAX) != hipSuccess ? 1 : 0; })) DV_FAIL("dv_obj_solve: cannot set the dynamic LDS size");
+        if (obj_kernel_attrs()) DV_FAIL("dv_obj_solve: cannot set the dynamic LDS size");
         StageScope sc(ctx, "obj_solve", s);
-        hipLaunchKernelGGL(bd_solve_kernel<ObjProb>, dim3(1), dim3(BD_THREADS), a.lds ? lds : 0, s, pr, a);
+        hipLaunchKernelGGL(bd_solve_kernel<ObjProb>, dim3(1), dim3(BD_THREADS), pend.lds_bytes, s, job.prob, job.a);
     }
     DV_CHECK(hipGetLastError());
     DV_CHECK(hipEventRecord(pend.ev, s));
-    pend.active = true; pend.V = V; pend.nblk = nblk; pend.n_obj = n_obj; pend.up_bytes = up_bytes; pend.stream = s;
+    return 0;
+}
+// internal two-phase form: the estimator's dynamic branch enqueues the object solve on its own stream + scratch buffer (pinned staging for both
+// directions, no host synchronisation) so that it runs beside the window solve; _end waits for its event and unpacks
+int be_obj_solve_begin(dv_ctx* ctx, dv_obj_problem* P, hipStream_t s, DevBuf& scratch, ObjPending& pend, bool defer) {
+    if (be_obj_solve_pack(ctx, P, scratch, pend) || be_obj_solve_upload(ctx, s, scratch, pend)) return -1;
+    if (defer) pend.deferred = true;
+    else if (be_obj_solve_launch(ctx, pend)) return -1;
+    pend.active = true;
+    return 0;
+}
+// The jobs of n packed + uploaded solves (uploads on s) in one launch: the table goes pinned -> HBM on s, workgroup b of bd_solve_group_kernel solves job b, `ev` stands behind
+// the launch and replaces every solve's own event.  Dynamic LDS of the launch: the largest working set among the jobs that keep theirs in LDS.
+int be_obj_solve_group_launch(dv_ctx* ctx, ObjPending* const* pends, int n, void* tab_host, void* tab_dev, hipStream_t s, hipEvent_t ev) {
+    if (n < 1) return 0;
+    size_t lds = 0;
+    for (int i = 0; i < n; ++i) { std::memcpy((uint8_t*)tab_host + sizeof(ObjJob) * (size_t)i, pends[i]->job, sizeof(ObjJob)); lds = std::max(lds, pends[i]->lds_bytes); }
+    DV_CHECK(dv_copy_async(tab_dev, tab_host, sizeof(ObjJob) * (size_t)n, s));
+    if (obj_kernel_attrs()) DV_FAIL("dv_obj_solve: cannot set the dynamic LDS size");
+    hipLaunchKernelGGL(bd_solve_group_kernel<ObjProb>, dim3(n), dim3(BD_THREADS), lds, s, (const ObjJob*)tab_dev);
+    DV_CHECK(hipGetLastError());
+    DV_CHECK(hipEventRecord(ev, s));
+    for (int i = 0; i < n; ++i) { pends[i]->deferred = false; pends[i]->ev_ext = ev; pends[i]->stream = s; }
     return 0;
 }
 
@@ -267,8 +315,7 @@ int be_obj_solve_prepare(dv_ctx* ctx, DevBuf& scratch, ObjPending& pend) {
     }
     if (!pend.ev) DV_CHECK(hipEventCreateWithFlags(&pend.ev, hipEventDisableTiming));
     if (scratch.ensure((size_t)8 << 20) != hipSuccess) DV_FAIL("dv_obj_solve: out of device memory");
-    static DevOnce once;
-    if (once.run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(bd_solve_kernel<ObjProb>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BD_LDS_MAX) != hipSuccess ? 1 : 0; })) DV_FAIL("dv_obj_solve: cannot set the dynamic LDS size");
+    if (obj_kernel_attrs()) DV_FAIL("dv_obj_solve: cannot set the dynamic LDS size");      // bd_solve_kernel<ObjProb> and bd_solve_group_kernel<ObjProb>
     return 0;
 }
 
@@ -276,7 +323,9 @@ int be_obj_solve_end(dv_ctx* ctx, dv_obj_problem* P, dv_ba_summary* summary, Obj
     if (!ctx) return -1;
     if (!pend.active) DV_FAIL("dv_obj_solve: nothing to collect");
     pend.active = false;
-    DV_CHECK(hipEventSynchronize(pend.ev));
+    if (pend.deferred && be_obj_solve_launch(ctx, pend)) return -1;      // a dv_batch member collected without dv_batch_enqueue: launched alone, on the stream of its upload
+    DV_CHECK(hipEventSynchronize(pend.ev_ext ? pend.ev_ext : pend.ev));      // (member of a dv_batch round: the group's event behind the shared launch)
+    pend.ev_ext = nullptr;
     if (ctx->timing) { DV_CHECK(hipStreamSynchronize(pend.stream)); dv_harvest_timers(ctx, pend.stream); }
     const double* hxo = (const double*)((const uint8_t*)pend.pinned + pend.up_bytes); const double* hout = hxo + 7 * (size_t)pend.V;
     for (int b = 0; b < pend.nblk; ++b) memcpy(P->state + 7 * (size_t)b, hxo + 7 * (size_t)b, 56);

@@ -151,10 +151,22 @@ int be_solve_fused_end(dv_ctx* ctx, dv_ba_problem* P, dv_ba_summary* summary, Be
 struct dv_obj_problem;
 struct ObjPending {       // an object solve in flight (be_obj_solve_begin / _end): pinned staging for upload + download, its event
     bool active = false; void* pinned = nullptr; size_t pinned_bytes = 0, up_bytes = 0; hipEvent_t ev = nullptr; hipStream_t stream = nullptr; int V = 0, nblk = 0, n_obj = 0;
-    void release() { if (pinned) (void)hipHostFree(pinned); pinned = nullptr; pinned_bytes = 0; if (ev) (void)hipEventDestroy(ev); ev = nullptr; active = false; }
+    // member of a dv_batch: packed and uploaded on the group's object stream, the launch waits for dv_batch_enqueue (be_obj_solve_group_launch: one launch for all members'
+    // jobs) — or for be_obj_solve_end, which launches a job nobody enqueued alone.  job = the kernel's arguments (BdJob<ObjProb> of be_objsolve.hip), lds_bytes = its dynamic LDS
+    // (0: working set in HBM); ev_ext = the group's event behind the shared launch, which replaces `ev` for this solve (as BePending::ev_state_ext does for the window)
+    bool deferred = false; hipEvent_t ev_ext = nullptr; size_t lds_bytes = 0; alignas(16) unsigned char job[192] = {};
+    void release() { if (pinned) (void)hipHostFree(pinned); pinned = nullptr; pinned_bytes = 0; if (ev) (void)hipEventDestroy(ev); ev = nullptr; active = false; deferred = false; ev_ext = nullptr; }
 };
-int be_obj_solve_begin(dv_ctx* ctx, dv_obj_problem* P, hipStream_t s, DevBuf& scratch, ObjPending& pend);
+// begin = pack (host only: checks, staging, the job) + upload (one copy on s) + launch; defer = true (the estimator's object branch of a dv_batch member) stops before the launch
+int be_obj_solve_begin(dv_ctx* ctx, dv_obj_problem* P, hipStream_t s, DevBuf& scratch, ObjPending& pend, bool defer = false);
+int be_obj_solve_pack(dv_ctx* ctx, dv_obj_problem* P, DevBuf& scratch, ObjPending& pend);
+int be_obj_solve_upload(dv_ctx* ctx, hipStream_t s, DevBuf& scratch, ObjPending& pend);
+int be_obj_solve_launch(dv_ctx* ctx, ObjPending& pend);                      // the single-workgroup kernel on pend.stream + pend.ev
+// the jobs of n packed + uploaded solves in ONE bd_solve_group_kernel launch on s (their uploads' stream): job table tab_host (pinned) -> tab_dev, then `ev` recorded behind the launch
+int be_obj_solve_group_launch(dv_ctx* ctx, ObjPending* const* pends, int n, void* tab_host, void* tab_dev, hipStream_t s, hipEvent_t ev);
+size_t be_obj_job_bytes();
 int be_obj_solve_end(dv_ctx* ctx, dv_obj_problem* P, dv_ba_summary* summary, ObjPending& pend);
+hipStream_t be_batch_obj_stream(struct dv_batch* B);      // the group's object stream: uploads and launches of its members' deferred object solves
 int be_obj_solve_prepare(dv_ctx* ctx, DevBuf& scratch, ObjPending& pend);      // the buffers, event and kernel attribute be_obj_solve_begin would create on its first call
 int be_prepare(dv_ctx* ctx, bool dynamic);      // dv_est_create: everything the first window solve / marginalization / object solve would allocate or create lazily (a 3 ms frame otherwise)
 struct dv_estimator;

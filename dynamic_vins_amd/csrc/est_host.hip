@@ -664,7 +664,10 @@ struct dv_estimator {
         { HostScope h1(ctx, "h_dyn_build"); have = im.build_problem(OP, &para_pose_ref[0][0], ric[0]) && (OP.n_boxes > 0 || OP.n_points > 0); }
         if (have) {
             HostScope h1(ctx, "h_dyn_solve_begin");
-            if (be_obj_solve_begin(ctx, &OP, ctx->obj_stream, ctx->obj_buf, ctx->obj_pend)) return -1;      // enqueued; collected in dynamic_branch_finish
+            // enqueued; collected in dynamic_branch_finish.  Member of a dv_batch: uploaded on the group's object stream and left to dv_batch_enqueue, which launches the object
+            // solves of all members as one grid (be_batch.hip); a member with stage timers keeps its own launch (the timers are per stream)
+            hipStream_t gs = ctx->batch ? be_batch_obj_stream(ctx->batch) : nullptr;
+            if (be_obj_solve_begin(ctx, &OP, gs ? gs : ctx->obj_stream, ctx->obj_buf, ctx->obj_pend, gs && !ctx->timing)) return -1;
             obj_solved = true;
         }
         return 0;

@@ -12,6 +12,8 @@
 // Many sequences on one GPU (config 4 of BASELINE.json, "batched"): the sequences of a GROUP run their begin phases back to back, dv_batch_enqueue launches the
 // iteration slots of all their window solves as one launch per stage, and while that runs the host turns to the next group; the end phases of a group follow when
 // its turn comes again.  `threads` host threads each drive their own groups (the reference runs one process — three threads — per sequence).
+// Dynamic sequences may be members of such a group: per member end(k-1), begin_ego(k), enqueue tracking(k+1), attach(k); then ONE dv_batch_enqueue launches the window slots AND
+// the object solves of all members; then every member collects its frame k+1 (dyn_post).
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -47,6 +49,9 @@ struct RSeq {
     bool dynamic = false; dv_seq_dynamic dyn{};
     struct DynBuf { std::vector<dv_feat> rows; int n_rows = 0; std::vector<dv_inst_obs> insts; int n_insts = 0; std::vector<dv_feat> ifeats; int n_ifeats = 0; std::vector<double> pts; int n_pts = 0; bool valid = false; };
     DynBuf db[2]; int cur = 0;
+    // member of a dv_batch group: always the one-thread order (dyn_begin), and the collect of frame k+1's rows waits until the group has enqueued its round (dyn_post) —
+    // the member's host thread must not sit in its own tracker's collect while the solves of the whole group are not launched yet
+    bool grouped = false, collect_due = false; int collect_k1 = 0;
     // tracker thread (T2) -> estimator loop (T3): ring of collected frames.  ring_head = frame index of ring[ring_pos], ring_count frames are ready; tracked_next = the
     // next frame the tracker will take.  Guarded by ring_mu; the tracker fills ring[(ring_pos + ring_count) % RING] outside the lock (the slot is not visible yet).
     static constexpr int RING = 3;
@@ -157,7 +162,11 @@ int dyn_begin(dv_runner* R, RSeq& s) {
     const double t = s.in.times[k];
     s.n_rows = b.n_rows;
     if (s.in.ba_stride > 1 && (k % s.in.ba_stride) != 0) {      // tracked only: both trackers have seen the frame, the back end has not (system/main.cpp:300-312: frames 0, 2, 4, ... outside KITTI)
-        if (k + 1 < s.in.n_frames) { if (dyn_enqueue(R, s, k + 1) || dyn_collect(R, s, s.db[s.cur ^ 1])) return -1; }
+        if (k + 1 < s.in.n_frames) {
+            if (dyn_enqueue(R, s, k + 1)) return -1;
+            if (s.grouped) { s.collect_due = true; s.collect_k1 = k + 1; }
+            else if (dyn_collect(R, s, s.db[s.cur ^ 1])) return -1;
+        }
         b.valid = false; s.cur ^= 1; ++s.next; s.skipped = true;
         return dyn_passed(R, s, k, false);
     }
@@ -173,12 +182,23 @@ int dyn_begin(dv_runner* R, RSeq& s) {
     s.detections += b.n_insts; s.object_features += b.n_ifeats; s.frames_with_objects += b.n_insts > 0; s.min_detections = std::min(s.min_detections, b.n_insts);
     if (dyn_passed(R, s, k, true)) return -1;
     if (k + 1 < s.in.n_frames) {
-        if (seq_feed_imu(R, s, s.in.times[k + 1])) return -1;
-        if (dyn_collect(R, s, s.db[s.cur ^ 1])) return -1;
+        if (s.grouped) { s.collect_due = true; s.collect_k1 = k + 1; }      // behind the group's dv_batch_enqueue: dyn_post
+        else {
+            if (seq_feed_imu(R, s, s.in.times[k + 1])) return -1;
+            if (dyn_collect(R, s, s.db[s.cur ^ 1])) return -1;
+        }
     }
     b.valid = false; s.cur ^= 1;
     s.pending = true; s.pending_t = t;
     return 0;
+}
+// a dynamic member of a dv_batch group, behind the group's dv_batch_enqueue: what dyn_begin left out — the IMU samples up to frame k+1 and the collect of its rows (into the
+// buffer dyn_begin has already made the current one)
+int dyn_post(dv_runner* R, RSeq& s) {
+    if (!s.collect_due) return 0;
+    s.collect_due = false;
+    if (!s.skipped && seq_feed_imu(R, s, s.in.times[s.collect_k1])) return -1;
+    return dyn_collect(R, s, s.db[s.cur]);
 }
 
 // ---- dynamic mode on two threads ----
@@ -248,7 +268,7 @@ int dyn_begin_threaded(dv_runner* R, RSeq& s) {
 // first half of a step: everything up to and including the enqueue of frame k's window solve and of frame k+1's tracking.  own_front = false: the caller enqueues
 // the tracking of the group's frames itself, in shared launches (group_round), and feeds the IMU samples of frame k+1 afterwards.
 int seq_begin(dv_runner* R, RSeq& s, bool own_front = true) {
-    if (s.dynamic) return R->tracker_thread ? dyn_begin_threaded(R, s) : dyn_begin(R, s);
+    if (s.dynamic) return (R->tracker_thread && !s.grouped) ? dyn_begin_threaded(R, s) : dyn_begin(R, s);      // (a group member tracks on the group's host thread: the ring is a group_size 0 feature)
     const int k = s.next;
     if (k >= s.in.n_frames) { s.err = "sequence exhausted"; set_err(R, s.err); return -1; }
     if (!s.enqueued) { if (!own_front) { s.err = "internal: frame not enqueued"; set_err(R, s.err); return -1; } if (seq_enqueue(R, s, k)) return -1; }
@@ -288,7 +308,7 @@ int group_track(dv_runner* R, dv_runner::Group& g, int ahead) {
         // `enqueued` first: in a team round thread 0 comes here (ahead = 0) while its teammates may still be inside seq_end of THEIR members, advancing s.next — every
         // member is `enqueued` then (set by this thread in the previous round, two barriers ago) and its counters are not looked at.  Reading s.next before this test was a
         // data race ThreadSanitizer reported (tests/host/runner_tsan.cpp); the value read was never used, so no result depended on it.
-        if (s.enqueued) continue;
+        if (s.dynamic || s.enqueued) continue;          // (a dynamic member enqueues its own tracking inside dyn_begin: TrackSemanticImage + InstsTrack are not shared)
         const int k = s.next + ahead - (s.skipped && ahead ? 1 : 0);      // (a track-only frame has already advanced s.next)
         if (k >= s.in.n_frames) continue;
         dv_track_job j{};
@@ -299,6 +319,12 @@ int group_track(dv_runner* R, dv_runner::Group& g, int ahead) {
     if (dv_batch_track_enqueue(g.batch, jobs.data(), (int)jobs.size())) { const char* m = dv_last_error(R->seqs[g.members[0]].ctx); set_err(R, std::string("dv_batch_track_enqueue: ") + (m ? m : "")); return -1; }
     for (const dv_track_job& j : jobs) R->seqs[g.members[j.member]].enqueued = true;
     return 0;
+}
+// last phase of a group's round, behind dv_batch_enqueue and the shared tracking launches: the IMU samples up to the member's next frame (and, dynamic member, its rows)
+int seq_post(dv_runner* R, RSeq& s) {
+    if (s.dynamic) return dyn_post(R, s);
+    const int k1 = s.next + (s.skipped ? 0 : 1);
+    return (!s.skipped && k1 < s.in.n_frames) ? seq_feed_imu(R, s, s.in.times[k1]) : 0;
 }
 int seq_end(dv_runner* R, RSeq& s) {
     if (!s.pending) return 0;
@@ -325,12 +351,13 @@ int group_round(dv_runner* R, dv_runner::Group& g) {
         for (int i : g.members) if (seq_begin(R, R->seqs[i], false)) return -1;
         if (dv_batch_enqueue(g.batch)) { set_err(R, std::string("dv_batch_enqueue: ") + (dv_last_error(R->seqs[g.members[0]].ctx) ? dv_last_error(R->seqs[g.members[0]].ctx) : "")); return -1; }
         if (group_track(R, g, 1)) return -1;
-        for (int i : g.members) { RSeq& s = R->seqs[i]; const int k1 = s.next + (s.skipped ? 0 : 1); if (!s.skipped && k1 < s.in.n_frames && seq_feed_imu(R, s, s.in.times[k1])) return -1; }
+        for (int i : g.members) if (seq_post(R, R->seqs[i])) return -1;
         g.pending = true;
         return 0;
     }
     for (int i : g.members) if (seq_begin(R, R->seqs[i])) return -1;
     if (g.batch && dv_batch_enqueue(g.batch)) { set_err(R, std::string("dv_batch_enqueue: ") + (dv_last_error(R->seqs[g.members[0]].ctx) ? dv_last_error(R->seqs[g.members[0]].ctx) : "")); return -1; }
+    for (int i : g.members) if (dyn_post(R, R->seqs[i])) return -1;      // (raw members have fed their samples inside seq_begin)
     g.pending = true;
     return 0;
 }
@@ -358,7 +385,7 @@ int team_round(dv_runner* R, dv_runner::Group& g, int j, int T, bool last) {
         }
         if (rc) B.failed.store(1);
         if (!B.wait()) return -1;                                      // the next frames are enqueued (their `enqueued` flags are set)
-        mine([&](RSeq& s) { const int k1 = s.next + (s.skipped ? 0 : 1); return (!s.skipped && k1 < s.in.n_frames) ? seq_feed_imu(R, s, s.in.times[k1]) : 0; });
+        mine([&](RSeq& s) { return seq_post(R, s); });
     }          // (drain round: g.pending is cleared behind the join in dv_runner_run)
     if (rc) B.failed.store(1);
     return rc;
@@ -405,6 +432,7 @@ dv_runner* dv_runner_create(dv_ctx* const* ctxs, const dv_seq_input* seqs, int n
             std::vector<dv_ctx*> m; for (int i : g.members) m.push_back(R->seqs[i].ctx);
             g.batch = dv_batch_create(m.data(), (int)m.size());
             if (!g.batch) { for (auto& gg : R->groups) if (gg.batch) dv_batch_destroy(gg.batch); return nullptr; }
+            for (int i : g.members) R->seqs[i].grouped = true;
         }
         R->groups.push_back(std::move(g));
     }
@@ -432,7 +460,7 @@ int dv_runner_run(dv_runner* R, int n_rounds, double* wall_seconds) {
     int rc = 0;
     // T2 of every dynamic sequence: may track up to ONE frame past what this call hands to the back end (as the one-thread loop does)
     if (R->tracker_thread && n_rounds > 0)
-        for (auto& s : R->seqs) if (s.dynamic) {
+        for (auto& s : R->seqs) if (s.dynamic && !s.grouped) {
             {
                 std::lock_guard<std::mutex> lk(*s.ring_mu);
                 s.ring_failed = false; s.track_last = std::min(s.next + n_rounds, s.in.n_frames - 1);
@@ -468,7 +496,7 @@ int dv_runner_run(dv_runner* R, int n_rounds, double* wall_seconds) {
     }
     // the call ends when every tracker has delivered its last frame of this call (or has failed); an estimator-side failure takes the bound back so that a parked tracker stays parked
     if (R->tracker_thread && n_rounds > 0)
-        for (auto& s : R->seqs) if (s.dynamic) {
+        for (auto& s : R->seqs) if (s.dynamic && !s.grouped) {
             std::unique_lock<std::mutex> lk(*s.ring_mu);
             if (rc) s.track_last = s.tracked_next - 1;
             s.ring_cv->wait(lk, [&] { return !s.track_busy && (s.ring_failed || s.tracked_next > s.track_last || s.ring_count >= RSeq::RING); });
@@ -546,11 +574,12 @@ int dv_runner_batch_rounds(dv_runner* R, long long* batched_rounds, long long* s
     return 0;
 }
 
+// A dynamic sequence inside a dv_batch group (RSeq::grouped): the one-thread order of dyn_begin whatever "tracker_thread" says, its window solve in the group's shared
+// slots, its object solve in the group's ONE object launch (both deferred by the estimator calls, launched by dv_batch_enqueue), its own tracking launches.
 int dv_runner_set_dynamic(dv_runner* R, int seq, const dv_seq_dynamic* dyn) {
     if (!R || seq < 0 || seq >= (int)R->seqs.size() || !dyn) return -1;
     RSeq& s = R->seqs[seq];
     if (s.next != 0 || s.enqueued || s.pending) { R->err = "dv_runner_set_dynamic: the sequence has already started"; return -1; }
-    for (auto& g : R->groups) if (g.batch) for (int i : g.members) if (i == seq) { R->err = "dv_runner_set_dynamic: a dynamic sequence cannot be a member of a dv_batch group (create the runner with group_size 0 for it)"; return -1; }
     if (!s.ctx->inst) { R->err = "dv_runner_set_dynamic: call dv_inst_config on the sequence's context first"; return -1; }
     if (dyn->inv_mask && dyn->mask_mem != s.in.mem) { R->err = "dv_runner_set_dynamic: mask_mem must equal the frames' mem (dv_track_stereo_enqueue takes frames and mask from one memory kind)"; return -1; }
     s.dynamic = true; s.dyn = *dyn; s.static_unmask = dyn->static_as_background != 0;
@@ -579,6 +608,15 @@ int dv_runner_dynamic_stats(dv_runner* R, int seq, long long* detections, long l
     if (min_detections) *min_detections = s.frames ? s.min_detections : 0;
     return 0;
 }
+int dv_runner_get_batches(dv_runner* R, dv_batch** out, int cap, int* n_out) {
+    if (!R) return -1;
+    int n = 0;
+    for (auto& g : R->groups) if (g.batch) { if (out && n < cap) out[n] = g.batch; ++n; }
+    if (n_out) *n_out = n;
+    return 0;
+}
+// "tracker_thread" governs the dynamic sequences OUTSIDE dv_batch groups; a dynamic member of a group has the group's host thread (or its team thread) as its T3 and tracks on
+// it: dyn_begin's order, bit-identical to the sequence's own run with group_size 0 and tracker_thread 0.
 int dv_runner_set(dv_runner* R, const char* key, int value) {
     if (!R || !key) return -1;
     if (std::strcmp(key, "batch_front") == 0) { R->batch_front = value != 0; runner_layout(R); return 0; }      // (teams need the shared front end)

@@ -297,7 +297,13 @@ int dv_allreduce_reduced_system(dv_ctx* ctx, double* S_g, int n);
  * No counterpart in the reference (one process per sequence).  The members are ordinary contexts with their own estimators; after
  * dv_est_process_begin (or _dynamic_begin) has been called on every member that has a frame, dv_batch_enqueue launches the iteration slots of all
  * pending window solves as one launch per stage (argument tables in HBM, window index in the grid); dv_est_process_end then collects each member
- * as usual.  A member collected without dv_batch_enqueue is solved on its own stream.  Results are bit-identical to the unbatched path. */
+ * as usual.  A member collected without dv_batch_enqueue is solved on its own stream.  Results are bit-identical to the unbatched path.
+ * DYNAMIC members (dv_est_config::dynamic = 1, entered through dv_est_process_dynamic_begin / _begin_ego + _attach): the object solve of a member's object branch
+ * (InstanceManager::Optimization, estimator_insts.cpp:772-807) is packed and uploaded by the member's call and launched by dv_batch_enqueue too — the object solves of
+ * all members of the round as ONE grid of independent workgroups on the group's object stream, beside the window solves (dv_batch_obj_info counts them).  A round
+ * with a single object solve, a member with dv_timing_enable, and a member collected without dv_batch_enqueue use the single-workgroup launch.  dv_destroy of a
+ * member and dv_batch_destroy drain the group's streams first: an uploaded or running object solve never outlives its buffers, and a member that leaves with a solve
+ * not yet launched launches it alone when it is collected. */
 typedef struct dv_batch dv_batch;
 dv_batch* dv_batch_create(dv_ctx* const* ctxs, int n);      /* idle contexts of one device; NULL + dv_last_error(NULL) on failure */
 void dv_batch_destroy(dv_batch* batch);                      /* the members stay valid; dv_destroy of a member before the batch detaches it from the batch */
@@ -432,6 +438,15 @@ typedef struct dv_obj_problem {
     const dv_obj_box* boxes; const dv_obj_point* points;
 } dv_obj_problem;
 int dv_obj_solve(dv_ctx* ctx, dv_obj_problem* problem, dv_ba_summary* summary);
+/* InstanceManager::Optimization (estimator/estimator_insts.cpp:772-807) of several dv_batch members in ONE launch: problems[i] is solved on member members[i] (index into
+ * the array dv_batch_create was given; every member at most once) by one workgroup of a shared grid on the group's object stream, summaries[i] receives its summary.
+ * States, dims and summaries carry the bits dv_obj_solve gives for the same problem on the same member.  Argument checks and messages are dv_obj_solve's, reported on
+ * the problem's member and on the group's first member; all problems are checked before anything is launched, so one bad problem among good ones leaves every problem
+ * untouched.  n = 1 uses dv_obj_solve's own kernel.  This is what dv_batch_enqueue does for the object branches of the group's dynamic members (below). */
+int dv_batch_obj_solve(dv_batch* batch, const int* members, dv_obj_problem* const* problems, int n, dv_ba_summary* summaries);
+/* object solves of the group so far, from dv_batch_enqueue rounds and dv_batch_obj_solve calls alike: shared launches, the jobs in them (jobs / launches = solves per
+ * launch), and solves that were launched alone (a round with one object solve, a member collected without dv_batch_enqueue counts where it is launched: not here) */
+int dv_batch_obj_info(dv_batch* batch, long long* launches, long long* jobs, long long* single);
 
 /* ---- the line-only refinement: replaces ceres::Solve inside Estimator::OptimizationWithOnlyLine
  * (estimator/estimator.cpp:345-395) for the problem AddLineResidualBlock builds (:222-253): one LineOrthParameterization block
@@ -575,7 +590,13 @@ typedef struct dv_runner dv_runner;
  * VIODE::SetViodeMaskSimple or the detector's SetBackgroundMask) in the frames' memory kind, tracked with `mode` = DV_MODE_NAIVE (GPU tracker's + GPU detector's rules).
  * The back end stays the raw one.  Before the first dv_runner_run; a masked sequence inside a dv_batch group keeps its own tracking launches. */
 int dv_runner_set_mask(dv_runner* runner, int seq, const uint8_t* const* inv_mask, int mask_mem, int mode);
-int dv_runner_set_dynamic(dv_runner* runner, int seq, const dv_seq_dynamic* dyn);      /* before the first dv_runner_run; the sequence then runs outside dv_batch groups */
+/* Before the first dv_runner_run.  A dynamic sequence may be a member of a dv_batch group (group_size > 1), beside raw, naive and other dynamic members: its window
+ * solve shares the group's launches, its object solve shares ONE launch with the other dynamic members' (dv_batch_enqueue), its tracking keeps its own launches
+ * (TrackSemanticImage + InstsTrack are not shared across members).  Inside a group it always runs the one-thread order whatever "tracker_thread" says — the group's
+ * host thread (or its team thread) is its T3, the tracker ring is a feature of group_size 0 — per member: end of frame k-1, dv_est_process_dynamic_begin_ego(k), enqueue
+ * tracking(k+1), dv_est_process_dynamic_attach(k), then ONE dv_batch_enqueue for the group, then collect tracking(k+1).  Every member's results are bit-identical to
+ * its own run with group_size 0 and "tracker_thread" 0. */
+int dv_runner_set_dynamic(dv_runner* runner, int seq, const dv_seq_dynamic* dyn);
 /* what the object branch of a dynamic sequence was fed so far: detections, object feature rows, frames with at least one object, fewest detections in a frame */
 int dv_runner_dynamic_stats(dv_runner* runner, int seq, long long* detections, long long* object_features, long long* frames_with_objects, int* min_detections);
 dv_runner* dv_runner_create(dv_ctx* const* ctxs, const dv_seq_input* seqs, int n_seq, int group_size, int threads);      /* group_size <= 1: no batching */
@@ -594,7 +615,12 @@ int dv_runner_get_frame_clock(dv_runner* runner, int seq, int which, double* sec
 int dv_runner_get_row_log(dv_runner* runner, int seq, unsigned long long* rows4, int cap, int* n_rows);
 int dv_runner_batch_rounds(dv_runner* runner, long long* batched_rounds, long long* single_rounds);      /* dv_batch_info summed over the groups */
 int dv_runner_batch_timing(dv_runner* runner, int on, double* out3, long long* rounds, int* windows);      /* dv_batch_timing of the runner's groups, averaged */
-/* switches: "batch_front" (default 1): the members of a dv_batch group are tracked in shared launches (dv_batch_track_enqueue); 0: one set of launches per sequence */
+/* the dv_batch objects of the runner's groups (groups of one sequence have none), for the dv_batch_*_info counters the runner does not sum itself (dv_batch_obj_info).
+ * They stay the runner's: read counters, enqueue nothing. */
+int dv_runner_get_batches(dv_runner* runner, dv_batch** out, int cap, int* n_out);
+/* switches: "batch_front" (default 1): the members of a dv_batch group are tracked in shared launches (dv_batch_track_enqueue); 0: one set of launches per sequence.
+ * "tracker_thread" (default 1): a dynamic sequence OUTSIDE a dv_batch group runs its tracker on a thread of its own (T2 beside T3); 0: the one-thread loop.  Dynamic members
+ * of a dv_batch group always run the one-thread order (dv_runner_set_dynamic).  "teams": see above. */
 int dv_runner_set(dv_runner* runner, const char* key, int value);
 int dv_runner_track_info(dv_runner* runner, long long* rounds, long long* members_batched, long long* members_single);      /* dv_batch_track_info summed over the groups */
 const char* dv_runner_error(dv_runner* runner);
