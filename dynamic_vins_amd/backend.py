@@ -495,8 +495,11 @@ class Batch:
         pointers (ints) or host uint8 arrays for the images; collect every member with its ctx.track_stereo_collect().  mem defaults to DV_MEM_HOST for arrays and
         DV_MEM_DEVICE for pointers; a colour job is mem = DV_MEM_* | DV_FMT_BGR with (h, w, 3) arrays or pointers to 3-channel rows (stride 0 = 3 * width).  Members with
         installed undistortion maps (undistort_setup / set_undistort_maps, maps per member) and colour jobs share the launches like plain gray members, and so do
-        DV_MODE_NAIVE jobs with a mask (a host array, or a device pointer beside device frames) when the round holds at least two of them; semantic mode, a raw job with a
-        mask, a lone naive job or one whose previous frame was raw, staged track_unmask_static jobs, an object tracker or timing on the ctx keep the member's own launches"""
+        DV_MODE_NAIVE and DV_MODE_SEMANTIC jobs with a mask (a host array, or a device pointer beside device frames) when the round holds at least two of them together.
+        A semantic job's ctx may own an object tracker (call its inst_track_enqueue after this call, as after track_stereo_enqueue) and may have track_unmask_static
+        jobs staged: one launch applies those of the whole round, and every return of this call leaves none staged.  A raw job with a mask, a lone naive / semantic job,
+        a naive job whose previous frame was raw or that has track_unmask_static jobs staged, a raw or naive job of a ctx with an object tracker, and timing on the
+        ctx keep the member's own launches"""
         arr = (dv_track_job * max(len(jobs), 1))()
         self._track_keep = []
         for k, j in enumerate(jobs):

@@ -63,6 +63,26 @@ void dv_launch_unmask(uint8_t* inv_mask, int pitch, int W, int H, int x0, int y0
     if (w > 0 && h > 0) hipLaunchKernelGGL(dv_unmask_kernel, dim3((w + 255) / 256, h), dim3(256), 0, s, inv_mask, pitch, W, H, x0, y0, w, h, roi_mask);
 }
 
+// The same over a job table, for the members of a dv_batch round (front_track.hip): ALL staged rectangles of ALL members in one launch, and the copy of a caller's device
+// mask into the member's own buffer with it (the caller's buffer is never written).  Grid (ceil(W / 256), H, jobs); a pixel becomes 255 where any rectangle of its member
+// covers it with roi >= 1 — dv_unmask_kernel's rule, whose writes commute — and keeps the source's value elsewhere
+__global__ __launch_bounds__(256) void dv_unmask_multi_kernel(const DvUnmaskJob* __restrict__ jobs, const DvUnmaskRect* __restrict__ rects) {
+    const DvUnmaskJob j = jobs[blockIdx.z];
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= j.W || y >= j.H) return;
+    uint8_t v = j.src ? j.src[(size_t)y * j.spitch + x] : j.dst[(size_t)y * j.dpitch + x];
+    for (int k = j.first; k < j.first + j.n; ++k) {
+        const DvUnmaskRect r = rects[k];
+        const int c = x - r.x, q = y - r.y;
+        if (c >= 0 && c < r.w && q >= 0 && q < r.h && r.roi[(size_t)q * r.w + c] >= 1) v = 255;
+    }
+    j.dst[(size_t)y * j.dpitch + x] = v;
+}
+void dv_launch_unmask_multi(const DvUnmaskJob* jobs_dev, int n_jobs, const DvUnmaskRect* rects_dev, int w_max, int h_max, hipStream_t s) {
+    if (n_jobs <= 0 || w_max <= 0 || h_max <= 0) return;
+    hipLaunchKernelGGL(dv_unmask_multi_kernel, dim3((w_max + 255) / 256, h_max, n_jobs), dim3(256), 0, s, jobs_dev, rects_dev);
+}
+
 // A queue's first dispatch of a kernel that needs scratch (private-segment) memory makes the runtime allocate that memory for the queue — a device allocation plus a queue
 // reconfiguration, 1 - 2 ms when the device is busy or its memory is held by other processes — and a later kernel with a LARGER per-lane need repeats it.  be_solve (28 B per
 // lane), the gauge kernels (80 B) and the batched solve (132 B) would pay it in the middle of a sequence: at the first window solve (seen as a 3.7 ms frame from a cold process

@@ -173,7 +173,7 @@ struct dv_estimator;
 void dv_est_destroy_internal(dv_estimator* e);
 struct dv_inst_tracker;
 void dv_inst_destroy_internal(dv_inst_tracker* t);
-int dv_inst_wait_before_next_frame(dv_ctx* ctx);
+int dv_inst_wait_before_next_frame(dv_ctx* ctx, hipStream_t s, bool consume = true);
 
 // One window sharded by landmark over several GPUs (be_shard.hip): the transport of the exchange vectors
 struct DvDist {

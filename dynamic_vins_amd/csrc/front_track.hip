@@ -2,7 +2,7 @@
 // One frame = pyrDown x3 (stereo pair per launch) -> LK temporal -> compact/sort -> Shi-Tomasi tile -> select/append -> LK stereo -> finalize (<= max_cnt 128-byte
 // rows, written into pinned memory by the kernel); naive and semantic mode add the GPU tracker's own pyramid levels and, with mask_morphology_size, the mask's erosion.
 // Both entries take what the stages are given from ONE description of the frame (front_plan), mode and mask included: the single entry launches it by value with the
-// single-sequence kernels, the group entry scatters it into the job tables of the _multi kernels — raw members and naive members with masks alike.
+// single-sequence kernels, the group entry scatters it into the job tables of the _multi kernels — raw, semantic and naive members alike.
 #include "dv_ctx.h"
 
 // What the stages of one frame of one context are given, in the job types of the table kernels
@@ -121,7 +121,7 @@ static int front_plan(dv_ctx* ctx, const dv_track_job& j, hipStream_t s, FrontPl
     return 0;
 }
 
-// the planned frame is enqueued behind `done` on s: the ctx turns to the pyramid it was built in.  cuda: the frame built the GPU tracker's pyramid levels too
+// the planned frame is enqueued behind `done` on s: the ctx turns to the pyramid it was built in.  cuda: the frame built the GPU tracker's pyramid levels too (naive, semantic)
 static void front_commit(dv_ctx* ctx, double t, hipEvent_t done, hipStream_t s, bool cuda) {
     ctx->cur ^= 1; ctx->last_done = done; ctx->last_front = s;
     ctx->leftc_valid[ctx->cur] = cuda;
@@ -143,7 +143,7 @@ int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gr
     const bool stereo = c.stereo && gray1;
     hipStream_t s = ctx->stream;
     const int cur = ctx->cur ^ 1;          // the pyramid slot of this frame: the ctx turns to it in front_commit
-    if (dv_inst_wait_before_next_frame(ctx)) DV_FAIL("dv_track_stereo: hipStreamWaitEvent");
+    if (dv_inst_wait_before_next_frame(ctx, s)) DV_FAIL("dv_track_stereo: hipStreamWaitEvent");
     StageScope frame(ctx, "frame");
     FrontPlan P;
     {
@@ -279,6 +279,12 @@ int dv_track_stereo(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gray1, int
 // aprons, compaction, tile, selection and rows with the raw members — their jobs carry the mask, min_new = 10 and the GPU detector's rule — and have three stages of
 // their own: cuda::pyrDown's levels 1..3 (pyr_down_multi_kernel<1>), the masks' erosion (those with mask_morphology_size > 0) and FeatureTrackByLKGpu
 // (lk_cuda_track_multi_kernel at 1.0 px) over their slice of the two LK tables, where the raw slice runs lk_track_multi_kernel at 0.5 px.
+// TrackSemanticImage members (DV_MODE_SEMANTIC with a mask, background_tracker.cpp:757-834 — the background tracking of a DYNAMIC sequence) are the third class, between
+// the two: TrackLeft on the plain pyramids with the raw slice (0.5 px), TrackRightGPU on the GPU tracker's pyramid with the naive slice (1.0 px), the CPU detector's
+// rule, the mask test, min_new = 10 and the erosion as in naive mode.  Two things a dynamic sequence adds ride on the group's stream: the staged
+// dv_track_unmask_static rectangles of all members (ONE launch, dv_unmask_multi_kernel, which also makes the copy of a caller's device mask) and the hand-shake with the
+// member's object tracker (wait for its previous frame, ev_pyr behind the aprons, ev_bg_select behind the selection), so that dv_inst_track_enqueue — still one set of
+// launches per member on the tracker's own stream, like the extra-point stages — sees the order the member's own entry gives it.
 struct DvFrontBatch {
     hipStream_t stream = nullptr; hipEvent_t done = nullptr, ev_copy[2] = { nullptr, nullptr };
     DevBuf tab[2]; void* tab_pinned[2] = { nullptr, nullptr }; size_t tab_bytes = 0; int parity = 0; bool copy_used[2] = { false, false };
@@ -307,26 +313,37 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
         for (int k = 0; k < 2; ++k) DV_CHECK(hipEventCreateWithFlags(&Fp->ev_copy[k], hipEventDisableTiming));
     }
     DvFrontBatch& F = *Fp;
-    // ---- which jobs can share launches.  Two classes, both without an object tracker or timing on the ctx and of the group's common geometry (gray or BGR frames, with
-    //      or without the member's own undistortion maps: those differ in how level 0 is filled and in nothing behind it):
-    //        raw    DV_MODE_RAW without a mask (FeatureTracker::TrackImage);
-    //        naive  DV_MODE_NAIVE with a mask (TrackImageNaive), no dv_track_unmask_static jobs staged, and the previous frame — if there is one — tracked in naive
-    //               mode too, so that its pyramid of the GPU tracker's flavour exists; at least two of them in the round, a lone one has nothing to share.
+    // ---- which jobs can share launches.  Three classes, all without timing on the ctx and of the group's common geometry (gray or BGR frames, with or without the
+    //      member's own undistortion maps: those differ in how level 0 is filled and in nothing behind it):
+    //        raw       DV_MODE_RAW without a mask (FeatureTracker::TrackImage), no object tracker on the ctx;
+    //        semantic  DV_MODE_SEMANTIC with a mask (TrackSemanticImage), with or without an object tracker on the ctx (its hand-shake with dv_inst_track_enqueue is kept on
+    //                  the group's stream, below) and with or without dv_track_unmask_static jobs staged (one launch applies those of the whole round);
+    //        naive     DV_MODE_NAIVE with a mask (TrackImageNaive), no object tracker, no dv_track_unmask_static jobs staged, and the previous frame — if there is one —
+    //                  with a pyramid of the GPU tracker's flavour (a naive or semantic frame).
+    //      Semantic and naive jobs share the GPU tracker's stages: at least two of them together in the round, a lone one has nothing to share.
     //      Every other job keeps its member's own launches on its own stream, in this round only. ----
-    enum { K_SINGLE = 0, K_RAW = 1, K_NAIVE = 2 };
+    enum { K_SINGLE = 0, K_RAW = 1, K_SEMANTIC = 2, K_NAIVE = 3 };
     std::vector<int> kind(n, K_SINGLE);
+    // whatever dv_track_unmask_static staged on the members handed in belongs to THIS frame: applied by the round's launch or by the member's own entry, or dropped with
+    // a refused / failed call — no job survives into a later frame
+    struct UnmaskGuard {
+        const std::vector<dv_ctx*>& mem; const dv_track_job* jobs; int n;
+        ~UnmaskGuard() { for (int i = 0; i < n; ++i) if (jobs[i].member >= 0 && jobs[i].member < (int)mem.size()) mem[jobs[i].member]->unmask.clear(); }
+    } unmask_guard{ mem, jobs, n };
     for (int i = 0; i < n; ++i) {
         const dv_track_job& j = jobs[i];
         if (j.member < 0 || j.member >= (int)mem.size()) DV_FAIL("dv_batch_track_enqueue: member index out of range");
         for (int q = 0; q < i; ++q) if (jobs[q].member == j.member) DV_FAIL("dv_batch_track_enqueue: a member appears twice");
         const dv_ctx* c = mem[j.member];
-        if (c->inst || c->timing || !j.gray0 || (c->cfg.stereo && !j.gray1)) continue;
-        if (j.mode == DV_MODE_RAW && !j.mask) kind[i] = K_RAW;
+        if (c->timing || !j.gray0 || (c->cfg.stereo && !j.gray1)) continue;
+        if (j.mode == DV_MODE_SEMANTIC && j.mask) kind[i] = K_SEMANTIC;
+        else if (c->inst) continue;
+        else if (j.mode == DV_MODE_RAW && !j.mask) kind[i] = K_RAW;
         else if (j.mode == DV_MODE_NAIVE && j.mask && c->unmask.empty() && !(c->have_prev && !c->leftc_valid[c->cur])) kind[i] = K_NAIVE;
     }
     const dv_config* ref = nullptr;
-    int R = 0, N = 0;
-    for (int pass = 0; pass < 2; ++pass) {      // (the second pass: fewer than two naive jobs fit, the geometry is that of the first raw job then)
+    int R = 0, N = 0;      // raw jobs; jobs of the GPU tracker's classes (semantic + naive)
+    for (int pass = 0; pass < 2; ++pass) {      // (the second pass: fewer than two semantic / naive jobs fit, the geometry is that of the first raw job then)
         ref = nullptr; R = N = 0;
         for (int i = 0; i < n; ++i) {
             if (kind[i] == K_SINGLE) continue;
@@ -336,9 +353,9 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
             (kind[i] == K_RAW ? R : N)++;
         }
         if (N == 0 || N >= 2) break;
-        for (int i = 0; i < n; ++i) if (kind[i] == K_NAIVE) kind[i] = K_SINGLE;
+        for (int i = 0; i < n; ++i) if (kind[i] != K_RAW) kind[i] = K_SINGLE;
     }
-    std::vector<int> M;                                         // job indices that are batched: the raw ones, then the naive ones (the two slices of the LK tables)
+    std::vector<int> M;                                         // job indices that are batched: raw, semantic, naive — both LK stages are two contiguous slices of their table then
     for (int cls = K_RAW; cls <= K_NAIVE; ++cls)
         for (int i = 0; i < n; ++i) {
             if (kind[i] != cls) continue;
@@ -360,7 +377,10 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
     const int S = (int)M.size();
     if (S == 0) return 0;
     R = 0; for (int i : M) R += kind[i] == K_RAW;
-    N = S - R;
+    int Q = 0; for (int i : M) Q += kind[i] == K_SEMANTIC;      // raw [0, R) | semantic [R, R + Q) | naive [R + Q, S)
+    N = S - R;                                                  // the jobs with the GPU tracker's pyramid levels, and maybe an erosion: semantic + naive
+    size_t n_rect = 0; int n_umj = 0;                           // staged dv_track_unmask_static rectangles of the round, and the members that have some
+    for (int i : M) { const dv_ctx* c = mem[jobs[i].member]; if (kind[i] == K_SEMANTIC && !c->unmask.empty()) { n_rect += c->unmask.size(); ++n_umj; } }
     const int w = ref->width, h = ref->height; const bool stereo = ref->stereo != 0;
     hipStream_t s = F.stream;
     // ---- the job tables of the round: one pinned block, one upload ----
@@ -369,7 +389,8 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
                  o_cmp = up(o_lk + (size_t)2 * S * sizeof(DvLkJob)), o_gt = up(o_cmp + (size_t)S * sizeof(DvCompactJob)),
                  o_gs = up(o_gt + (size_t)S * sizeof(GfttTileArgs)), o_fin = up(o_gs + (size_t)S * sizeof(GfttSelectArgs)),
                  o_l0 = up(o_fin + (size_t)S * sizeof(DvFinalizeJob)), o_cp = up(o_l0 + (size_t)S * sizeof(DvLevel0Job)),
-                 o_er = up(o_cp + (size_t)3 * N * sizeof(DvPyrJob)), total = up(o_er + (size_t)N * sizeof(DvErodeJob));
+                 o_er = up(o_cp + (size_t)3 * N * sizeof(DvPyrJob)), o_um = up(o_er + (size_t)N * sizeof(DvErodeJob)),
+                 o_ur = up(o_um + (size_t)n_umj * sizeof(DvUnmaskJob)), total = up(o_ur + n_rect * sizeof(DvUnmaskRect));
     const int par = F.parity; F.parity ^= 1;
     if (F.copy_used[par]) DV_CHECK(hipEventSynchronize(F.ev_copy[par]));      // the upload that last read this pinned block (two rounds ago) has run
     if (F.tab_bytes < total) {
@@ -387,15 +408,28 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
     DvPyrJob* h_pyr = (DvPyrJob*)(hp + o_pyr); DvPyr* h_apr = (DvPyr*)(hp + o_apr); DvLkJob* h_lk = (DvLkJob*)(hp + o_lk); DvCompactJob* h_cmp = (DvCompactJob*)(hp + o_cmp);
     GfttTileArgs* h_gt = (GfttTileArgs*)(hp + o_gt); GfttSelectArgs* h_gs = (GfttSelectArgs*)(hp + o_gs); DvFinalizeJob* h_fin = (DvFinalizeJob*)(hp + o_fin);
     DvLevel0Job* h_l0 = (DvLevel0Job*)(hp + o_l0); int n_l0 = 0;      // only the members whose level 0 is not a copy of the frame: none in an all-plain round, and no launch then
-    DvPyrJob* h_cp = (DvPyrJob*)(hp + o_cp);                          // the GPU tracker's pyramid levels of the naive members, level-major like h_pyr
-    DvErodeJob* h_er = (DvErodeJob*)(hp + o_er); int n_er = 0;        // only the naive members with mask_morphology_size > 0
+    DvPyrJob* h_cp = (DvPyrJob*)(hp + o_cp);                          // the GPU tracker's pyramid levels of the semantic and naive members, level-major like h_pyr
+    DvErodeJob* h_er = (DvErodeJob*)(hp + o_er); int n_er = 0;        // only the semantic / naive members with mask_morphology_size > 0
+    DvUnmaskJob* h_um = (DvUnmaskJob*)(hp + o_um); int n_um = 0;      // only the semantic members with staged dv_track_unmask_static jobs
+    DvUnmaskRect* h_ur = (DvUnmaskRect*)(hp + o_ur); int n_ur = 0;
     // ---- per member: its plan of the frame, scattered into the tables.  (No ctx changes before the commit below: a member's refusal, a failed upload or LDS
     //      attribute leave no member with a flipped current pyramid, a pending frame or a GPU-tracker pyramid marked valid) ----
-    int n_max = 0, n_max_raw = 0, n_max_naive = 0, levels = 0, lw[DV_MAX_LEVELS] = { 0 }, lh[DV_MAX_LEVELS] = { 0 }, clevels = 0;
+    int n_max = 0, n_max_cls[3] = { 0, 0, 0 }, levels = 0, lw[DV_MAX_LEVELS] = { 0 }, lh[DV_MAX_LEVELS] = { 0 }, clevels = 0;
     FrontPlan P;
     for (int k = 0; k < S; ++k) {
         const dv_track_job& j = jobs[M[k]]; dv_ctx* c = mem[j.member];
+        // a member with an object tracker: the objects of its previous frame (dv_inst_track_enqueue, on the tracker's own stream) still read the pyramids this frame's
+        // uploads and levels overwrite
+        if (c->inst && dv_inst_wait_before_next_frame(c, s, false)) { dv_set_error(c, "dv_track_stereo: hipStreamWaitEvent"); dv_set_error(ctx, c->err); return -1; }
         if (front_plan(c, j, s, P)) { dv_set_error(ctx, c->err); return -1; }      // (with dv_track_stereo's text, on the member and on the first one)
+        if (kind[M[k]] == K_SEMANTIC && !c->unmask.empty()) {      // the static instances' pixels leave the mask in the member's own mask_buf: a host mask is there already, a device mask is copied by the launch that applies the rectangles
+            const int mp = align_up(w, 16);
+            if (c->mask_buf.ensure((size_t)mp * h) != hipSuccess) { dv_set_error(c, "dv_track_unmask_static: cannot allocate the mask copy"); dv_set_error(ctx, c->err); return -1; }
+            const bool own = P.mask == (const uint8_t*)c->mask_buf.p;
+            h_um[n_um++] = DvUnmaskJob{ (uint8_t*)c->mask_buf.p, own ? nullptr : P.mask, mp, P.mask_pitch, w, h, n_ur, (int)c->unmask.size() };
+            for (const dv_ctx::UnmaskJob& u : c->unmask) h_ur[n_ur++] = DvUnmaskRect{ (const uint8_t*)c->unmask_pinned + u.off, u.x, u.y, u.w, u.h };
+            if (front_plan_mask(c, j.mode, (const uint8_t*)c->mask_buf.p, mp, P)) { dv_set_error(ctx, c->err); return -1; }
+        }
         if (P.pyr.has_l0) h_l0[n_l0++] = P.pyr.l0;
         levels = P.pyr.levels;
         for (int l = 1; l < levels; ++l) { h_pyr[(size_t)(l - 1) * S + k] = P.pyr.down[l - 1]; lw[l] = P.pyr.down[l - 1].dw; lh[l] = P.pyr.down[l - 1].dh; }
@@ -403,9 +437,8 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
         h_lk[k] = P.lk_temporal; h_lk[S + k] = P.lk_stereo;
         h_cmp[k] = P.compact; h_gt[k] = P.tile; h_gs[k] = P.select; h_fin[k] = P.fin;
         n_max = std::max(n_max, c->cfg.max_cnt);
-        if (k < R) n_max_raw = std::max(n_max_raw, c->cfg.max_cnt);
-        else {
-            n_max_naive = std::max(n_max_naive, c->cfg.max_cnt);
+        int& cls_max = n_max_cls[k < R ? 0 : k < R + Q ? 1 : 2]; cls_max = std::max(cls_max, c->cfg.max_cnt);
+        if (k >= R) {
             clevels = P.cpyr.levels;      // (every level of the size: the same for all members)
             for (int l = 1; l < clevels; ++l) h_cp[(size_t)(l - 1) * N + (k - R)] = P.cpyr.down[l - 1];
             if (P.has_erode) h_er[n_er++] = P.erode;
@@ -413,24 +446,28 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
     }
     DV_CHECK(dv_copy_async(F.tab[par].p, hp, total, s));
     DV_CHECK(hipEventRecord(F.ev_copy[par], s)); F.copy_used[par] = true;
-    // ---- the stages.  A class without a member launches nothing: a round of raw members enqueues the ten launches it always did ----
+    // ---- the stages.  A class without a member launches nothing: a round of raw members enqueues the ten launches it always did, no event besides ----
     const DvLkJob* d_lk = (const DvLkJob*)(dp + o_lk);
     if (n_l0) dv_launch_level0_multi((const DvLevel0Job*)(dp + o_l0), n_l0, w, h, s);
     for (int l = 1; l < levels; ++l) dv_launch_pyr_down_multi((const DvPyrJob*)(dp + o_pyr) + (size_t)(l - 1) * S, S, lw[l], lh[l], s);
     dv_launch_pyr_apron_multi((const DvPyr*)(dp + o_apr), 2 * S, levels, s);
+    for (int k = R; k < R + Q; ++k) { dv_ctx* c = mem[jobs[M[k]].member]; if (c->inst) DV_CHECK(hipEventRecord(c->ev_pyr, s)); }      // the member's object tracker may start: this frame's pyramids exist
     for (int l = 1; l < clevels; ++l) {      // cuda::pyrDown's levels on top of level 0 (all of them: the level sizes follow from the common geometry)
         const DvPyrJob& j0 = h_cp[(size_t)(l - 1) * N];
         dv_launch_pyr_down_multi((const DvPyrJob*)(dp + o_cp) + (size_t)(l - 1) * N, N, j0.dw, j0.dh, s, 1);
     }
+    if (n_um) dv_launch_unmask_multi((const DvUnmaskJob*)(dp + o_um), n_um, (const DvUnmaskRect*)(dp + o_ur), w, h, s);      // system/main.cpp:217-245, before anything reads the masks
     if (n_er) dv_launch_erode_multi((const DvErodeJob*)(dp + o_er), n_er, w, h, s);
-    dv_launch_lk_track_multi(d_lk, R, n_max_raw, ref->flow_back, 0.5f, s);
-    dv_launch_lk_cuda_track_multi(d_lk + R, N, n_max_naive, ref->flow_back, 1.0f, s);      // FeatureTrackByLKGpu's threshold
+    // temporal: FeatureTrackByLK at 0.5 px over raw + semantic (TrackLeft), FeatureTrackByLKGpu at 1.0 px over naive (TrackLeftGPU)
+    dv_launch_lk_track_multi(d_lk, R + Q, std::max(n_max_cls[0], n_max_cls[1]), ref->flow_back, 0.5f, s);
+    dv_launch_lk_cuda_track_multi(d_lk + R + Q, N - Q, n_max_cls[2], ref->flow_back, 1.0f, s);
     dv_launch_compact_multi((const DvCompactJob*)(dp + o_cmp), S, s);
     dv_launch_gftt_tile_multi((const GfttTileArgs*)(dp + o_gt), S, w, h, s);
     if (dv_launch_gftt_select_multi((const GfttSelectArgs*)(dp + o_gs), S, s)) DV_FAIL("gftt_select: cannot set dynamic LDS size");
-    if (stereo) {
-        dv_launch_lk_track_multi(d_lk + S, R, n_max_raw, ref->flow_back, 0.5f, s);
-        dv_launch_lk_cuda_track_multi(d_lk + S + R, N, n_max_naive, ref->flow_back, 1.0f, s);
+    for (int k = R; k < R + Q; ++k) { dv_ctx* c = mem[jobs[M[k]].member]; if (c->inst) DV_CHECK(hipEventRecord(c->ev_bg_select, s)); }      // the shared id counter: background first, then the member's objects
+    if (stereo) {      // FeatureTrackByLK over raw (TrackRight), FeatureTrackByLKGpu over semantic + naive (TrackRightGPU)
+        dv_launch_lk_track_multi(d_lk + S, R, n_max_cls[0], ref->flow_back, 0.5f, s);
+        dv_launch_lk_cuda_track_multi(d_lk + S + R, N, std::max(n_max_cls[1], n_max_cls[2]), ref->flow_back, 1.0f, s);
     }
     dv_launch_finalize_multi((const DvFinalizeJob*)(dp + o_fin), S, n_max, s);
     DV_CHECK(hipGetLastError());

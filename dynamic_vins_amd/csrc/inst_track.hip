@@ -110,11 +110,13 @@ struct dv_inst_tracker {
 };
 
 void dv_inst_destroy_internal(dv_inst_tracker* t) { delete t; }
-// the background tracker's next frame must not rebuild the right pyramid while the objects of the previous frame still read it
-int dv_inst_wait_before_next_frame(dv_ctx* ctx) {
+// the background tracker's next frame, built on s (the ctx's own stream, or its dv_batch's front-end stream), must not rebuild the right pyramid while the objects of the
+// previous frame still read it.  consume = false: the wait is enqueued and the ctx is left as it is (the group entry changes no ctx before its round's commit: a refused
+// round must leave the member's next frame its wait, and a second wait for an event that has fired costs nothing)
+int dv_inst_wait_before_next_frame(dv_ctx* ctx, hipStream_t s, bool consume) {
     if (!ctx->inst || !ctx->inst->frame_enqueued) return 0;
-    ctx->inst->frame_enqueued = false;
-    return hipStreamWaitEvent(ctx->stream, ctx->inst->done, 0) == hipSuccess ? 0 : -1;
+    if (consume) ctx->inst->frame_enqueued = false;
+    return hipStreamWaitEvent(s, ctx->inst->done, 0) == hipSuccess ? 0 : -1;
 }
 
 static void circle_half_widths_i(int radius, std::vector<uint8_t>& hw) {      // cv::circle's midpoint rasteriser (as dvins_api.hip)

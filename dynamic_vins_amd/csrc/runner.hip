@@ -12,8 +12,10 @@
 // Many sequences on one GPU (config 4 of BASELINE.json, "batched"): the sequences of a GROUP run their begin phases back to back, dv_batch_enqueue launches the
 // iteration slots of all their window solves as one launch per stage, and while that runs the host turns to the next group; the end phases of a group follow when
 // its turn comes again.  `threads` host threads each drive their own groups (the reference runs one process — three threads — per sequence).
-// Dynamic sequences may be members of such a group: per member end(k-1), begin_ego(k), enqueue tracking(k+1), attach(k); then ONE dv_batch_enqueue launches the window slots AND
-// the object solves of all members; then every member collects its frame k+1 (dyn_post).
+// Dynamic sequences may be members of such a group: per member end(k-1), begin_ego(k), attach(k); then ONE dv_batch_enqueue launches the window slots AND the object solves
+// of all members; then ONE dv_batch_track_enqueue tracks the background of frame k+1 of all members (TrackSemanticImage in the group's shared launches, the members' static
+// instances unmasked by one launch) and every member enqueues InstsTrack(k+1) on its object tracker's stream; then every member collects its frame k+1 (dyn_post).  With
+// "batch_front" 0, or a static-report lag of 1, a member enqueues tracking(k+1) itself between begin_ego(k) and attach(k), as a sequence outside a group does.
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -52,6 +54,9 @@ struct RSeq {
     // member of a dv_batch group: always the one-thread order (dyn_begin), and the collect of frame k+1's rows waits until the group has enqueued its round (dyn_post) —
     // the member's host thread must not sit in its own tracker's collect while the solves of the whole group are not launched yet
     bool grouped = false, collect_due = false; int collect_k1 = 0;
+    // a frame of this dynamic sequence has been enqueued (by dyn_enqueue or by the group's shared launches): from then on it always has its next frame in flight or
+    // collected when a round starts, so group_track's first-round pass has nothing to do for it — and does not look at the fields its team thread may be writing
+    bool started = false;
     // tracker thread (T2) -> estimator loop (T3): ring of collected frames.  ring_head = frame index of ring[ring_pos], ring_count frames are ready; tracked_next = the
     // next frame the tracker will take.  Guarded by ring_mu; the tracker fills ring[(ring_pos + ring_count) % RING] outside the lock (the slot is not visible yet).
     static constexpr int RING = 3;
@@ -132,21 +137,32 @@ int dyn_passed(dv_runner* R, RSeq& s, int k, bool with_snapshot) {
     return 0;
 }
 // ---- dynamic mode: TrackSemanticImage + InstsTrack of frame k (one enqueue), their collect, and the three-phase back end ----
-int dyn_enqueue(dv_runner* R, RSeq& s, int k) {
+// the three steps of frame k's enqueue: the static instances' rectangles staged for it | TrackSemanticImage | InstsTrack.  dyn_enqueue runs them back to back on the
+// member's own stream; a dv_batch group with shared tracking launches (group_track) runs the first and the last per member around ONE dv_batch_track_enqueue
+int dyn_stage_unmask(dv_runner* R, RSeq& s, int k) {
     const dv_seq_dynamic& d = s.dyn;
-    const int mode = d.mode ? d.mode : DV_MODE_SEMANTIC;
     if (s.static_unmask && d.inv_mask && d.dets && d.n_dets && d.n_dets[k] > 0) {
         std::vector<uint32_t> ids;
         { std::lock_guard<std::mutex> lk(*s.ring_mu); int best = -1; for (const RSeq::StaticSnap& sn : s.snaps) if (sn.frame >= 0 && sn.frame <= k - static_lag() && sn.frame > best) { best = sn.frame; ids = sn.ids; } }
         if (dv_track_unmask_static(s.ctx, d.dets[k], d.n_dets[k], ids.data(), (int)ids.size())) return fail(R, s, "dv_track_unmask_static");
     }
-    // (frames and mask share `mem` in dv_track_stereo_enqueue: a device-resident sequence keeps both in HBM)
-    if (dv_track_stereo_enqueue(s.ctx, s.in.left[k], s.in.right[k], s.w, s.h, s.stride, s.in.times[k], d.inv_mask ? d.inv_mask[k] : nullptr, mode, s.in.mem)) return fail(R, s, "dv_track_stereo_enqueue");
+    return 0;
+}
+int dyn_enqueue_objects(dv_runner* R, RSeq& s, int k) {
+    const dv_seq_dynamic& d = s.dyn;
     if (d.disp && d.disp[k] && dv_inst_set_disparity(s.ctx, d.disp[k], d.disp_stride, d.disp_mem, d.baseline)) return fail(R, s, "dv_inst_set_disparity");
     if (d.right_keys && d.right_keys[k] && dv_inst_set_right_keys(s.ctx, d.right_keys[k], 0, d.right_keys_mem)) return fail(R, s, "dv_inst_set_right_keys");
     if (dv_inst_track_enqueue(s.ctx, s.in.times[k], d.dets ? d.dets[k] : nullptr, d.n_dets ? d.n_dets[k] : 0, d.boxes3d ? d.boxes3d[k] : nullptr, d.n_boxes3d ? d.n_boxes3d[k] : 0)) return fail(R, s, "dv_inst_track_enqueue");
-    s.enqueued = true;
+    s.enqueued = true; s.started = true;
     return 0;
+}
+int dyn_enqueue(dv_runner* R, RSeq& s, int k) {
+    const dv_seq_dynamic& d = s.dyn;
+    const int mode = d.mode ? d.mode : DV_MODE_SEMANTIC;
+    if (dyn_stage_unmask(R, s, k)) return -1;
+    // (frames and mask share `mem` in dv_track_stereo_enqueue: a device-resident sequence keeps both in HBM)
+    if (dv_track_stereo_enqueue(s.ctx, s.in.left[k], s.in.right[k], s.w, s.h, s.stride, s.in.times[k], d.inv_mask ? d.inv_mask[k] : nullptr, mode, s.in.mem)) return fail(R, s, "dv_track_stereo_enqueue");
+    return dyn_enqueue_objects(R, s, k);
 }
 int dyn_collect(dv_runner* R, RSeq& s, RSeq::DynBuf& b) {
     if (dv_track_stereo_collect(s.ctx, b.rows.data(), &b.n_rows)) return fail(R, s, "dv_track_stereo_collect");
@@ -154,16 +170,21 @@ int dyn_collect(dv_runner* R, RSeq& s, RSeq::DynBuf& b) {
     b.valid = true; s.enqueued = false;
     return 0;
 }
-int dyn_begin(dv_runner* R, RSeq& s) {
+// own_front = false: member of a dv_batch group whose tracking runs in the group's shared launches — group_track has enqueued frame k before the first round and
+// enqueues frame k+1 behind the group's dv_batch_enqueue; what is left here is the order of the estimator calls and the hand-over to dyn_post
+int dyn_begin(dv_runner* R, RSeq& s, bool own_front = true) {
     const int k = s.next;
     if (k >= s.in.n_frames) { s.err = "sequence exhausted"; set_err(R, s.err); return -1; }
     RSeq::DynBuf& b = s.db[s.cur];
-    if (!b.valid) { if (!s.enqueued && dyn_enqueue(R, s, k)) return -1; if (dyn_collect(R, s, b)) return -1; }
+    if (!b.valid) {
+        if (!s.enqueued) { if (!own_front) { s.err = "internal: frame not enqueued"; set_err(R, s.err); return -1; } if (dyn_enqueue(R, s, k)) return -1; }
+        if (dyn_collect(R, s, b)) return -1;
+    }
     const double t = s.in.times[k];
     s.n_rows = b.n_rows;
     if (s.in.ba_stride > 1 && (k % s.in.ba_stride) != 0) {      // tracked only: both trackers have seen the frame, the back end has not (system/main.cpp:300-312: frames 0, 2, 4, ... outside KITTI)
         if (k + 1 < s.in.n_frames) {
-            if (dyn_enqueue(R, s, k + 1)) return -1;
+            if (own_front && dyn_enqueue(R, s, k + 1)) return -1;
             if (s.grouped) { s.collect_due = true; s.collect_k1 = k + 1; }
             else if (dyn_collect(R, s, s.db[s.cur ^ 1])) return -1;
         }
@@ -177,7 +198,7 @@ int dyn_begin(dv_runner* R, RSeq& s) {
     const int rc = dv_est_process_dynamic_begin_ego(s.ctx, b.rows.data(), b.n_rows, t);
     if (rc < 0) return fail(R, s, "dv_est_process_dynamic_begin_ego");
     if (rc > 0) { s.err = "IMU stream does not cover the frame"; set_err(R, s.err); return -1; }
-    if (k + 1 < s.in.n_frames && dyn_enqueue(R, s, k + 1)) return -1;
+    if (own_front && k + 1 < s.in.n_frames && dyn_enqueue(R, s, k + 1)) return -1;
     if (dv_est_process_dynamic_attach(s.ctx, b.n_insts ? b.insts.data() : nullptr, b.n_insts, b.n_ifeats ? b.ifeats.data() : nullptr, b.n_pts ? b.pts.data() : nullptr)) return fail(R, s, "dv_est_process_dynamic_attach");
     s.detections += b.n_insts; s.object_features += b.n_ifeats; s.frames_with_objects += b.n_insts > 0; s.min_detections = std::min(s.min_detections, b.n_insts);
     if (dyn_passed(R, s, k, true)) return -1;
@@ -265,10 +286,14 @@ int dyn_begin_threaded(dv_runner* R, RSeq& s) {
     return 0;
 }
 
+// Do the dynamic members of a dv_batch group track in the group's shared launches?  With shared tracking launches on, and a static-report lag of two frames or more:
+// the shared launches of frame k+1 come BEHIND the object branch of frame k (dyn_passed), where the member's own enqueue comes before it — with lag 1 the snapshot of
+// frame k would be read in one order and not in the other, so lag 1 keeps the enqueue inside dyn_begin (fourth finding).  A constant of the run.
+bool dyn_shares_front(const dv_runner* R) { return R->batch_front && static_lag() >= 2; }
 // first half of a step: everything up to and including the enqueue of frame k's window solve and of frame k+1's tracking.  own_front = false: the caller enqueues
 // the tracking of the group's frames itself, in shared launches (group_round), and feeds the IMU samples of frame k+1 afterwards.
 int seq_begin(dv_runner* R, RSeq& s, bool own_front = true) {
-    if (s.dynamic) return (R->tracker_thread && !s.grouped) ? dyn_begin_threaded(R, s) : dyn_begin(R, s);      // (a group member tracks on the group's host thread: the ring is a group_size 0 feature)
+    if (s.dynamic) return (R->tracker_thread && !s.grouped) ? dyn_begin_threaded(R, s) : dyn_begin(R, s, own_front || !dyn_shares_front(R));      // (a group member tracks on the group's host thread: the ring is a group_size 0 feature)
     const int k = s.next;
     if (k >= s.in.n_frames) { s.err = "sequence exhausted"; set_err(R, s.err); return -1; }
     if (!s.enqueued) { if (!own_front) { s.err = "internal: frame not enqueued"; set_err(R, s.err); return -1; } if (seq_enqueue(R, s, k)) return -1; }
@@ -301,23 +326,37 @@ int seq_begin(dv_runner* R, RSeq& s, bool own_front = true) {
     return 0;
 }
 // the tracking of frame `s.next + ahead` of every member of a dv_batch group in shared launches (dv_batch_track_enqueue)
+// Dynamic members (dyn_shares_front): per member its static instances' rectangles are staged first (dv_track_unmask_static, the snapshot dyn_enqueue would pick), then the
+// ONE dv_batch_track_enqueue, then per member InstsTrack of the same frame on its object tracker's own stream (dv_inst_track_enqueue: not shared, like the extra-point stages).
 int group_track(dv_runner* R, dv_runner::Group& g, int ahead) {
     std::vector<dv_track_job> jobs;
+    const bool dyn_shared = dyn_shares_front(R);
     for (size_t m = 0; m < g.members.size(); ++m) {
         RSeq& s = R->seqs[g.members[m]];
         // `enqueued` first: in a team round thread 0 comes here (ahead = 0) while its teammates may still be inside seq_end of THEIR members, advancing s.next — every
         // member is `enqueued` then (set by this thread in the previous round, two barriers ago) and its counters are not looked at.  Reading s.next before this test was a
         // data race ThreadSanitizer reported (tests/host/runner_tsan.cpp); the value read was never used, so no result depended on it.
-        if (s.dynamic || s.enqueued) continue;          // (a dynamic member enqueues its own tracking inside dyn_begin: TrackSemanticImage + InstsTrack are not shared)
+        // A dynamic member's flags (`enqueued`, its buffers) are written by dyn_post, which a teammate may still be running for the previous round: in the first-round pass
+        // `started` alone is read — written by this thread or before the threads started — and a started member is left alone.
+        if (s.dynamic ? (!dyn_shared || (ahead == 0 && s.started)) : s.enqueued) continue;          // (dynamic member with its own front end: it enqueues its tracking inside dyn_begin)
         const int k = s.next + ahead - (s.skipped && ahead ? 1 : 0);      // (a track-only frame has already advanced s.next)
         if (k >= s.in.n_frames) continue;
         dv_track_job j{};
-        j.member = (int)m; j.mem = s.in.mem; j.gray0 = s.in.left[k]; j.gray1 = s.in.right[k]; j.stride = s.stride; j.mode = s.raw_mode; j.t = s.in.times[k]; j.mask = s.raw_mask ? s.raw_mask[k] : nullptr;      // (naive members with masks share the round's launches when there are two or more of them; a lone one keeps its own: dv_batch_track_enqueue)
+        j.member = (int)m; j.mem = s.in.mem; j.gray0 = s.in.left[k]; j.gray1 = s.in.right[k]; j.stride = s.stride; j.t = s.in.times[k];
+        if (s.dynamic) {
+            if (s.enqueued) continue;
+            if (dyn_stage_unmask(R, s, k)) return -1;
+            j.mode = s.dyn.mode ? s.dyn.mode : DV_MODE_SEMANTIC; j.mask = s.dyn.inv_mask ? s.dyn.inv_mask[k] : nullptr;
+        } else { j.mode = s.raw_mode; j.mask = s.raw_mask ? s.raw_mask[k] : nullptr; }      // (naive members with masks share the round's launches when the round holds two or more naive / semantic jobs; a lone one keeps its own: dv_batch_track_enqueue)
         jobs.push_back(j);
     }
     if (jobs.empty()) return 0;
     if (dv_batch_track_enqueue(g.batch, jobs.data(), (int)jobs.size())) { const char* m = dv_last_error(R->seqs[g.members[0]].ctx); set_err(R, std::string("dv_batch_track_enqueue: ") + (m ? m : "")); return -1; }
-    for (const dv_track_job& j : jobs) R->seqs[g.members[j.member]].enqueued = true;
+    for (const dv_track_job& j : jobs) {
+        RSeq& s = R->seqs[g.members[j.member]];
+        if (s.dynamic) { if (dyn_enqueue_objects(R, s, s.next + ahead - (s.skipped && ahead ? 1 : 0))) return -1; }      // (sets `enqueued`)
+        else s.enqueued = true;
+    }
     return 0;
 }
 // last phase of a group's round, behind dv_batch_enqueue and the shared tracking launches: the IMU samples up to the member's next frame (and, dynamic member, its rows)
@@ -575,7 +614,8 @@ int dv_runner_batch_rounds(dv_runner* R, long long* batched_rounds, long long* s
 }
 
 // A dynamic sequence inside a dv_batch group (RSeq::grouped): the one-thread order of dyn_begin whatever "tracker_thread" says, its window solve in the group's shared
-// slots, its object solve in the group's ONE object launch (both deferred by the estimator calls, launched by dv_batch_enqueue), its own tracking launches.
+// slots, its object solve in the group's ONE object launch (both deferred by the estimator calls, launched by dv_batch_enqueue), its background tracking in the group's
+// shared tracking launches (group_track; its own launches with "batch_front" 0 or a static-report lag of 1), InstsTrack and the extra-point stages in its own launches.
 int dv_runner_set_dynamic(dv_runner* R, int seq, const dv_seq_dynamic* dyn) {
     if (!R || seq < 0 || seq >= (int)R->seqs.size() || !dyn) return -1;
     RSeq& s = R->seqs[seq];

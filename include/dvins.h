@@ -323,9 +323,17 @@ int dv_batch_info(dv_batch* batch, long long* batched_rounds, long long* single_
  * mask_morphology_size > 0; compaction, detection and rows are the group's launches, each job under its own mask and rules.  A DV_MEM_HOST job's mask is staged into
  * the member's own buffer on the group's stream, a DV_MEM_DEVICE / DV_MEM_PINNED job's mask is read in place (rows of `stride` bytes, of width bytes for a BGR job).
  * A round without such jobs enqueues nothing for them.
- * Jobs that cannot share launches (DV_MODE_SEMANTIC, a raw job with a mask, a naive job without one, a lone naive job, a naive job with dv_track_unmask_static jobs
- * staged or whose previous frame was tracked in another mode, an object tracker on the ctx, dv_timing_enable on the ctx, another image size than the first
- * shareable job's) run through their member's own dv_track_stereo_enqueue inside this call, in this round only.  Every member is collected with
+ * DV_MODE_SEMANTIC jobs with a mask (TrackSemanticImage: the background tracking of a dynamic sequence, what dv_runner_set_dynamic feeds) are the third class, and the
+ * only one whose member may own an object tracker (dv_inst_config): TrackLeft runs with the raw jobs' slice, TrackRightGPU with the naive jobs' slice, the GPU
+ * tracker's pyramid levels and the erosion are those of the naive class, and semantic and naive jobs are counted together for the "at least two" rule.  Whatever
+ * dv_track_unmask_static staged on such a member is applied by ONE launch for all members of the round, in the member's own copy of the mask (made by the same launch
+ * for a DV_MEM_DEVICE / DV_MEM_PINNED mask: the caller's buffer is never written).  The group's stream keeps the hand-shake with the member's object tracker — it
+ * waits for the objects of the previous frame, and dv_inst_track_enqueue of this frame (call it per member after this call, as after dv_track_stereo_enqueue; it
+ * stays one set of launches per member) starts behind the round's pyramids and draws its ids behind the round's corner selection.
+ * On EVERY return of this call, 0 or -1, the dv_track_unmask_static jobs of the members handed in are gone: none survives into a later frame.
+ * Jobs that cannot share launches (a semantic or naive job without a mask, a raw job with one, a lone semantic / naive job, a naive job with dv_track_unmask_static
+ * jobs staged or whose previous frame was tracked in raw mode, a raw or naive job of a member with an object tracker, dv_timing_enable on the ctx, another image
+ * size than the first shareable job's) run through their member's own dv_track_stereo_enqueue inside this call, in this round only.  Every member is collected with
  * dv_track_stereo_collect as usual; its rows are bit-identical to the unbatched path's.  A member whose maps do not fit (another size, camera 1 missing on a stereo
  * member) or whose previous frame was not collected fails the call with dv_track_stereo's message; no member of the shared part has a frame pending then.
  * Between this call and a member's dv_track_stereo_collect, call no image operator (dv_remap, dv_bgr2gray, dv_pyr_down_cuda, ...) on that member: its staging buffers
