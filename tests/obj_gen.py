@@ -127,22 +127,25 @@ def _small_rot(rng, sigma):
     return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
 
 
-def make_obj_scene(seed, n_obj=4, pts_per_obj=60, box_prob=0.8, pose_noise=(0.4, 0.08), dims_noise=0.3, outside=0.25, max_iters=10, plane_kind=0):
+def make_obj_scene(seed, n_obj=4, pts_per_obj=60, box_prob=0.8, pose_noise=(0.4, 0.08), dims_noise=0.3, outside=0.25, max_iters=10, plane_kind=0,
+                   pts_per_block=None, body_shift=0.0):
     """A window of 11 body poses driving along x, n_obj objects moving at constant velocity, each observed in a random
     sub-range of frames: noisy 3-D detections (dims, R_cioi) on a fraction of the frames and triangulated points spread
     inside (and, for a fraction `outside`, beyond) the object's box.  Returns a backend.ObjProblem whose state / dims are
-    the noisy initial values (what InstanceManager holds before the solve)."""
+    the noisy initial values (what InstanceManager holds before the solve).
+    pts_per_block: a sequence cycled over the observed (object, frame) blocks in order: the block gets exactly that many points (the object's first ones) instead
+    of a random 60 %.  body_shift: added to every body position's x (no factor reads the body positions: only |x| of the solve sees them)."""
     from dynamic_vins_amd.backend import ObjProblem, OBJBOX_DTYPE, OBJPT_DTYPE
     rng = np.random.default_rng(seed)
     R_bc = np.array([[0, 0, 1.0], [-1, 0, 0], [0, -1, 0]]) @ _small_rot(rng, 0.02)
     body = np.zeros((11, 7))
     for f in range(11):
         Rwb = _rz(0.02 * f) @ _small_rot(rng, 0.01)
-        body[f, :3] = [0.8 * f, 0.05 * np.sin(f), 0.0]
+        body[f, :3] = [0.8 * f + body_shift, 0.05 * np.sin(f), 0.0]
         body[f, 3:] = _q_from_R(Rwb)
     state = np.zeros((n_obj, 11, 7))
     dims = np.zeros((n_obj, 3))
-    boxes, points = [], []
+    boxes, points, nblock = [], [], 0
     for o in range(n_obj):
         d_true = rng.uniform([3.2, 1.5, 1.3], [4.8, 2.1, 1.9])
         p0 = np.array([rng.uniform(6, 30), rng.uniform(-8, 8), rng.uniform(-0.2, 0.2)])
@@ -168,7 +171,11 @@ def make_obj_scene(seed, n_obj=4, pts_per_obj=60, box_prob=0.8, pose_noise=(0.4,
                 b = np.zeros((), OBJBOX_DTYPE)
                 b["obj"], b["frame"], b["dims"], b["R_cioi"] = o, f, d_true + rng.normal(0, 0.15, 3), R_cioi.ravel()
                 boxes.append(b)
-            seen = rng.random(pts_per_obj) < 0.6
+            if pts_per_block is None:
+                seen = rng.random(pts_per_obj) < 0.6
+            else:
+                seen = np.arange(pts_per_obj) < pts_per_block[nblock % len(pts_per_block)]
+                nblock += 1
             for k in np.nonzero(seen)[0]:
                 p = np.zeros((), OBJPT_DTYPE)
                 p["obj"], p["frame"], p["p_w"] = o, f, Pwo + Rwo @ local[k] + rng.normal(0, 0.03, 3)
@@ -190,11 +197,13 @@ def o_obj_solve(lib, prob):
 
 
 # ---- synthetic scenes for the line-only refinement (Estimator::OptimizationWithOnlyLine) ----
-def make_line_scene(seed, n_lines=40, max_iters=10, pix_sigma=0.002, orth_noise=0.03, sqrt_info=(460 / 1.5, 0, 0, 460 / 1.5), empty_lines=2, min_obs=5):
+def make_line_scene(seed, n_lines=40, max_iters=10, pix_sigma=0.002, orth_noise=0.03, sqrt_info=(460 / 1.5, 0, 0, 460 / 1.5), empty_lines=2, min_obs=5,
+                    obs_counts=None):
     """11 body poses moving along x and looking along +x (camera z), 3-D line segments ahead of them observed in a run of >= min_obs
     consecutive frames (para::kLineMinObs = 5, estimator/vio_parameters.cpp:47: AddLineResidualBlock skips landmarks with fewer) as noisy
     end points on the normalised plane; the initial orthonormal parameters are the true ones plus noise.
-    The last `empty_lines` lines have no observation (they must not move and do not count in |x|)."""
+    The last `empty_lines` lines have no observation (they must not move and do not count in |x|).
+    obs_counts: a sequence cycled over the observed lines: line k is seen in exactly that many consecutive frames (1..11) instead of a random run."""
     from tests import line_geometry_np as LG
     from dynamic_vins_amd.backend import LINEOBS_DTYPE, LineProblem
     rng = np.random.default_rng(seed)
@@ -215,8 +224,13 @@ def make_line_scene(seed, n_lines=40, max_iters=10, pix_sigma=0.002, orth_noise=
         orth[k] = LG.plk_to_orth(plk) + rng.normal(0, orth_noise, 4)
         if k >= n_lines - empty_lines:
             continue
-        f0 = int(rng.integers(0, 12 - min_obs))
-        f1 = int(rng.integers(f0 + min_obs - 1, 11))
+        if obs_counts is None:
+            f0 = int(rng.integers(0, 12 - min_obs))
+            f1 = int(rng.integers(f0 + min_obs - 1, 11))
+        else:
+            n = int(obs_counts[k % len(obs_counts)])
+            f0 = int(rng.integers(0, 12 - n))
+            f1 = f0 + n - 1
         for f in range(f0, f1 + 1):
             Rwb = _qR(pose[f, 3:])
             Rwc, twc = Rwb @ R_bc, Rwb @ ex[:3] + pose[f, :3]
