@@ -127,6 +127,31 @@ def imu_eval(ctx, imu_rec, g_norm, pose_i, sb_i, pose_j, sb_j):
     return out[:15], out[15:].reshape(15, 30)
 
 
+def ba_gauge(ctx, pose, speed_bias, inv_depth, nframes, use_imu, R0, ypr0, P0):
+    """dv_ba_gauge -> (pose[11, 7], speed_bias[11, 9], inv_depth[nlm]) after Double2vector's yaw / position fix"""
+    pose, sb = np.ascontiguousarray(pose, np.float64).reshape(11, 7), np.ascontiguousarray(speed_bias, np.float64).reshape(11, 9)
+    lam = np.ascontiguousarray(inv_depth, np.float64).reshape(-1)
+    a = [np.ascontiguousarray(x, np.float64).reshape(-1) for x in (R0, ypr0, P0)]
+    assert a[0].size == 9 and a[1].size == 3 and a[2].size == 3
+    op, osb, ol = np.zeros((11, 7)), np.zeros((11, 9)), np.zeros(len(lam))
+    _chk(ctx, ctx.lib.dv_ba_gauge(ctx.h, pose.ctypes.data, sb.ctypes.data, lam.ctypes.data if len(lam) else None, len(lam), int(nframes), int(use_imu),
+                                  a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, op.ctypes.data, osb.ctypes.data, ol.ctypes.data if len(lam) else None))
+    return op, osb, ol
+
+
+def ba_reject(ctx, pose, ex_pose, inv_depth, factors, landmarks, nframes, ric, tic, focal, ex_from_state):
+    """dv_ba_reject -> flags[nlm] (uint8) of OutliersRejection at the given states"""
+    pose, ex = np.ascontiguousarray(pose, np.float64).reshape(11, 7), np.ascontiguousarray(ex_pose, np.float64).reshape(2, 7)
+    lam = np.ascontiguousarray(inv_depth, np.float64).reshape(-1)
+    fac, lms = np.ascontiguousarray(factors, FACTOR_DTYPE), np.ascontiguousarray(landmarks, LM_DTYPE)
+    ric, tic = np.ascontiguousarray(ric, np.float64).reshape(18), np.ascontiguousarray(tic, np.float64).reshape(6)
+    assert len(lam) == len(lms)
+    flags = np.zeros(len(lms), np.uint8)
+    _chk(ctx, ctx.lib.dv_ba_reject(ctx.h, pose.ctypes.data, ex.ctypes.data, lam.ctypes.data, fac.ctypes.data, len(fac), lms.ctypes.data, len(lms), int(nframes),
+                                   ric.ctypes.data, tic.ctypes.data, float(focal), int(ex_from_state), flags.ctypes.data))
+    return flags
+
+
 def marginalize(ctx, sub: WindowProblem, mode):
     """dv_marginalize -> (dv_ba_prior, A, b, diag)"""
     out = dv_ba_prior()

@@ -584,4 +584,76 @@ int dv_imu_eval(dv_ctx* ctx, const dv_ba_imu* imu, double g_norm, const double* 
     return 0;
 }
 
+// the BeState the tail kernels read, from the caller's flat blocks (absent blocks stay zero)
+static void be_op_state(BeState& h, const double* pose, const double* sb, const double* ex, const double* inv_depth, int nlm) {
+    std::memset(&h, 0, sizeof(h));
+    std::memcpy(h.pose, pose, sizeof(h.pose));
+    if (sb) std::memcpy(h.sb, sb, sizeof(h.sb));
+    if (ex) std::memcpy(h.ex, ex, sizeof(h.ex));
+    if (nlm > 0) std::memcpy(h.inv_depth, inv_depth, 8 * (size_t)nlm);
+}
+
+int dv_ba_gauge(dv_ctx* ctx, const double* pose, const double* speed_bias, const double* inv_depth, int nlm, int nframes, int use_imu,
+                const double* R0, const double* ypr0, const double* P0, double* out_pose, double* out_speed_bias, double* out_inv_depth) {
+    if (!ctx) return -1;
+    if (!pose || !speed_bias || !R0 || !ypr0 || !P0 || !out_pose || !out_speed_bias) DV_FAIL("dv_ba_gauge: null argument");
+    if (nframes < 1 || nframes > BE_NF || nlm < 0 || nlm > BE_MAX_LM || (nlm > 0 && (!inv_depth || !out_inv_depth))) DV_FAIL("dv_ba_gauge: bad argument");
+    if (ctx->be.pend && ctx->be.pend->active) DV_FAIL("dv_ba_gauge: a solve is in flight");
+    DV_CHECK(hipSetDevice(ctx->cfg.device));
+    hipStream_t s = ctx->be_stream;
+    DV_CHECK(ctx->s0.ensure(2 * sizeof(BeState) + 256));
+    BeState* dx = (BeState*)ctx->s0.p; BeState* dout = dx + 1;
+    std::vector<BeState> hs(1);
+    BeState& h = hs[0];
+    be_op_state(h, pose, speed_bias, nullptr, inv_depth, nlm);
+    DV_CHECK(hipMemcpyAsync(dx, &h, sizeof(h), hipMemcpyHostToDevice, s));
+    DV_CHECK(hipMemsetAsync(dout, 0, sizeof(BeState), s));
+    BeGaugeArgs ga{};
+    ga.x = dx; ga.out = dout; ga.nframes = nframes; ga.use_imu = use_imu ? 1 : 0; ga.nlm = nlm;
+    std::memcpy(ga.R0, R0, sizeof(ga.R0)); std::memcpy(ga.ypr0, ypr0, sizeof(ga.ypr0)); std::memcpy(ga.P0, P0, sizeof(ga.P0));
+    be_launch_gauge(ga, s);
+    DV_CHECK(hipGetLastError());
+    DV_CHECK(hipMemcpyAsync(&h, dout, sizeof(h), hipMemcpyDeviceToHost, s));
+    DV_CHECK(hipStreamSynchronize(s));
+    std::memcpy(out_pose, h.pose, sizeof(h.pose)); std::memcpy(out_speed_bias, h.sb, sizeof(h.sb));
+    if (nlm > 0) std::memcpy(out_inv_depth, h.inv_depth, 8 * (size_t)nlm);
+    return 0;
+}
+
+int dv_ba_reject(dv_ctx* ctx, const double* pose, const double* ex_pose, const double* inv_depth, const dv_ba_factor* factors, int nfac,
+                 const dv_ba_lm* landmarks, int nlm, int nframes, const double* ric, const double* tic, double focal, int ex_from_state, uint8_t* flags) {
+    if (!ctx) return -1;
+    if (!pose || !ex_pose || !inv_depth || !factors || !landmarks || !ric || !tic || !flags) DV_FAIL("dv_ba_reject: null argument");
+    if (nframes < 1 || nframes > BE_NF || nlm < 1 || nlm > BE_MAX_LM || nfac < 1) DV_FAIL("dv_ba_reject: bad argument");
+    for (int l = 0; l < nlm; ++l) {        // everything the kernel indexes with: one half-wave (32 lanes) per landmark, frames < nframes
+        const dv_ba_lm& L = landmarks[l];
+        if (L.first < 0 || L.count < 1 || L.count > BE_MAX_OBS_FACTORS || L.first > nfac - L.count || L.anchor < 0 || L.anchor >= nframes) DV_FAIL("dv_ba_reject: bad landmark record");
+        for (int k = 0; k < L.count; ++k) {
+            const dv_ba_factor& f = factors[L.first + k];
+            if (f.kind < 0 || f.kind > 2 || f.fj < 0 || f.fj >= nframes) DV_FAIL("dv_ba_reject: bad factor record");
+        }
+    }
+    if (ctx->be.pend && ctx->be.pend->active) DV_FAIL("dv_ba_reject: a solve is in flight");
+    DV_CHECK(hipSetDevice(ctx->cfg.device));
+    hipStream_t s = ctx->be_stream;
+    const size_t nf = sizeof(BeFactor) * (size_t)nfac, nl = sizeof(BeLm) * (size_t)nlm, nflag = ((size_t)nlm + 255) & ~(size_t)255;
+    DV_CHECK(ctx->s0.ensure(sizeof(BeState) + nf + nl + nflag + 256));
+    uint8_t* b = (uint8_t*)ctx->s0.p;
+    BeState* dx = (BeState*)b; BeFactor* dfac = (BeFactor*)(b + sizeof(BeState)); BeLm* dlm = (BeLm*)(b + sizeof(BeState) + nf); uint8_t* dflag = b + sizeof(BeState) + nf + nl;
+    std::vector<BeState> hs(1);
+    be_op_state(hs[0], pose, nullptr, ex_pose, inv_depth, nlm);
+    DV_CHECK(hipMemcpyAsync(dx, &hs[0], sizeof(BeState), hipMemcpyHostToDevice, s));
+    DV_CHECK(hipMemcpyAsync(dfac, factors, nf, hipMemcpyHostToDevice, s));
+    DV_CHECK(hipMemcpyAsync(dlm, landmarks, nl, hipMemcpyHostToDevice, s));
+    DV_CHECK(hipMemsetAsync(dflag, 0xff, nflag, s));        // a landmark the kernel skips shows as 255
+    BeRejectArgs r{};
+    r.st = dx; r.fac = dfac; r.lm = dlm; r.nlm = nlm; r.nframes = nframes; r.focal = focal; r.flags = dflag; r.ex_from_state = ex_from_state ? 1 : 0;
+    std::memcpy(r.ric, ric, sizeof(r.ric)); std::memcpy(r.tic, tic, sizeof(r.tic));
+    be_launch_reject(r, s);
+    DV_CHECK(hipGetLastError());
+    DV_CHECK(hipMemcpyAsync(flags, dflag, (size_t)nlm, hipMemcpyDeviceToHost, s));
+    DV_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
 }  // extern "C"

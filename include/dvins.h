@@ -379,6 +379,17 @@ int dv_proj_eval(dv_ctx* ctx, const dv_ba_factor* factors, int n, const double* 
 /* out: 15 whitened residuals followed by the whitened 15 x 30 Jacobian (pose_i 6, sb_i 9, pose_j 6, sb_j 9) */
 int dv_imu_eval(dv_ctx* ctx, const dv_ba_imu* imu, double g_norm, const double* pose_i, const double* sb_i,
                 const double* pose_j, const double* sb_j, double* out);
+/* operator-level entries of the two kernels behind a window solve, for tests against a float64 restatement.
+ * dv_ba_gauge: the yaw / position gauge fix of Estimator::Double2vector -> BodyState::GetOptimizationParameters (estimator/estimator.cpp:1110-1154,
+ * estimator/body.cpp:61-129) on a caller-given solved window.  pose 11 x 7 (x y z qx qy qz qw), speed_bias 11 x 9, inv_depth[nlm] (nlm <= 1000, may be NULL at 0);
+ * R0 (3x3 row-major), ypr0 (degrees, Utility::R2ypr) and P0: frame 0 before the solve.  Frames >= nframes are copied.  Outputs in the same layouts. */
+int dv_ba_gauge(dv_ctx* ctx, const double* pose, const double* speed_bias, const double* inv_depth, int nlm, int nframes, int use_imu,
+                const double* R0, const double* ypr0, const double* P0, double* out_pose, double* out_speed_bias, double* out_inv_depth);
+/* dv_ba_reject: OutliersRejection / ReprojectionError (estimator/vio_util.cpp:381-444): flags[l] = 1 when the mean over landmark l's residual blocks of the
+ * normalised reprojection error, times focal, exceeds 3.  pose 11 x 7, ex_pose 2 x 7, inv_depth[nlm]; ric 2 x (3x3 row-major), tic 2 x 3: the extrinsics used
+ * unless ex_from_state != 0, which takes them from ex_pose (free extrinsic blocks).  count <= 24 per landmark, frames < nframes. */
+int dv_ba_reject(dv_ctx* ctx, const double* pose, const double* ex_pose, const double* inv_depth, const dv_ba_factor* factors, int nfac,
+                 const dv_ba_lm* landmarks, int nlm, int nframes, const double* ric, const double* tic, double focal, int ex_from_state, uint8_t* flags);
 
 /* ---- line and dynamic-object factors: residual + Jacobians, one record per residual block.
  * Jacobians are returned in LOCAL sizes, row-major (pose blocks 6 wide: the reference's 7th column is always zero).
