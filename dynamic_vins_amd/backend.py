@@ -590,6 +590,11 @@ class dv_seq_dynamic(C.Structure):
                 ("right_keys", C.c_void_p), ("right_keys_mem", C.c_int32), ("static_as_background", C.c_int32)]
 
 
+class dv_seq_viode(C.Structure):
+    _fields_ = [("seg0", C.c_void_p), ("seg1", C.c_void_p), ("mem", C.c_int32), ("stride", C.c_int32), ("dyn_keys", C.c_void_p), ("nkeys", C.c_int32), ("min_inst_size", C.c_int32),
+                ("static_as_background", C.c_int32), ("reserved", C.c_int32), ("disp", C.c_void_p), ("disp_mem", C.c_int32), ("disp_stride", C.c_int32), ("baseline", C.c_double)]
+
+
 class Runner:
     """dv_runner: the per-frame host loop of pipeline.Pipeline in C++ inside the library, for one or many sequences (include/dvins.h).  `pipes` are Pipeline
     objects (each owns its Context + Estimator and a SyntheticSequence whose frames are resident in HBM); the runner takes over driving them."""
@@ -633,7 +638,9 @@ class Runner:
         if not self.h:
             raise DvinsError((self.lib.dv_last_error(None) or b"dv_runner_create failed").decode())
         for i, p in enumerate(pipes):
-            if getattr(p, "mode", 0) != 0:          # a DynamicPipeline: hand the per-frame perception outputs of its sequence to the runner's dynamic loop
+            if getattr(p, "live_masks", False):     # a DynamicPipeline over a VIODE-style sequence, fed with its label images frame by frame
+                self._set_viode(i, p, first_frame)
+            elif getattr(p, "mode", 0) != 0:          # a DynamicPipeline: hand the per-frame perception outputs of its sequence to the runner's dynamic loop
                 self._set_dynamic(i, p, first_frame)
 
     def _set_dynamic(self, i, p, first_frame):
@@ -675,6 +682,30 @@ class Runner:
             self._keep += [rk, rkp]
         self._keep += [masks, det_ptrs, n_dets, box_ptrs, n_boxes, disps, dyn]
         if self.lib.dv_runner_set_dynamic(self.h, i, C.byref(dyn)) != 0:
+            raise DvinsError(self.lib.dv_runner_error(self.h).decode())
+
+    def _set_viode(self, i, p, first_frame):
+        """dv_runner_set_viode: the sequence's label images (q.seg0 / q.seg1, host arrays -> resident tensors beside the frames) instead of masks, detections and keys"""
+        import torch
+        from .frontend import DV_MEM_DEVICE
+        from . import viode as _viode
+        q = p.seq
+        dev = q.frames[0][0].device
+        seg0 = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in q.seg0[first_frame:]]
+        seg1 = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in q.seg1[first_frame:]]
+        torch.cuda.synchronize()
+        nf = len(seg0)
+        p0, p1 = (C.c_void_p * nf)(*[a.data_ptr() for a in seg0]), (C.c_void_p * nf)(*[a.data_ptr() for a in seg1])
+        keys = np.ascontiguousarray(q.dyn_keys, np.uint32)
+        v = dv_seq_viode()
+        v.seg0, v.seg1, v.mem, v.stride = C.cast(p0, C.c_void_p), C.cast(p1, C.c_void_p), DV_MEM_DEVICE, 0
+        v.dyn_keys, v.nkeys, v.min_inst_size = keys.ctypes.data, len(keys), _viode.MIN_INST_SIZE
+        v.static_as_background = 1 if getattr(p, "static_as_background", False) else 0
+        use_disp = getattr(p, "extra_from_disparity", False) and len(getattr(q, "disp_dev", [])) > 0
+        disps = (C.c_void_p * nf)(*[d.data_ptr() for d in q.disp_dev[first_frame:]]) if use_disp else None
+        v.disp, v.disp_mem, v.disp_stride, v.baseline = (C.cast(disps, C.c_void_p) if use_disp else None), DV_MEM_DEVICE, 0, float(q.baseline)
+        self._keep += [seg0, seg1, p0, p1, keys, disps, v]
+        if self.lib.dv_runner_set_viode(self.h, i, C.byref(v)) != 0:
             raise DvinsError(self.lib.dv_runner_error(self.h).decode())
 
     def dynamic_stats(self, i):

@@ -63,6 +63,18 @@ void dv_launch_unmask(uint8_t* inv_mask, int pitch, int W, int H, int x0, int y0
     if (w > 0 && h > 0) hipLaunchKernelGGL(dv_unmask_kernel, dim3((w + 255) / 256, h), dim3(256), 0, s, inv_mask, pitch, W, H, x0, y0, w, h, roi_mask);
 }
 
+// The key-image form (dv_track_unmask_static_keys): the instance's ROI mask is the comparison of the frame's key image with the instance's key, read where it lies
+// (HBM, or the caller's pinned host memory), one dword per lane along a row; the rectangle was checked against the image by the entry
+__global__ __launch_bounds__(256) void dv_unmask_keys_kernel(uint8_t* __restrict__ inv_mask, int pitch, int W, int H, int x0, int y0, int w, int h, const uint32_t* __restrict__ key, int kpitch, uint32_t id) {
+    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
+    if (c >= w || r >= h) return;
+    const int x = x0 + c, y = y0 + r;
+    if (x < W && y < H && key[(size_t)y * kpitch + x] == id) inv_mask[(size_t)y * pitch + x] = 255;
+}
+void dv_launch_unmask_keys(uint8_t* inv_mask, int pitch, int W, int H, int x0, int y0, int w, int h, const uint32_t* key, int kpitch, uint32_t id, hipStream_t s) {
+    if (w > 0 && h > 0) hipLaunchKernelGGL(dv_unmask_keys_kernel, dim3((w + 63) / 64, (h + 3) / 4), dim3(64, 4), 0, s, inv_mask, pitch, W, H, x0, y0, w, h, key, kpitch, id);
+}
+
 // The same over a job table, for the members of a dv_batch round (front_track.hip): ALL staged rectangles of ALL members in one launch, and the copy of a caller's device
 // mask into the member's own buffer with it (the caller's buffer is never written).  Grid (ceil(W / 256), H, jobs); a pixel becomes 255 where any rectangle of its member
 // covers it with roi >= 1 — dv_unmask_kernel's rule, whose writes commute — and keeps the source's value elsewhere

@@ -211,6 +211,13 @@ struct dv_ctx {
     // kernel behind the mask's upload in dv_track_stereo_enqueue
     struct UnmaskJob { int x, y, w, h; size_t off; };
     std::vector<UnmaskJob> unmask; void* unmask_pinned = nullptr; size_t unmask_pinned_bytes = 0;
+    // dv_track_unmask_static_keys: the same rectangles, the per-pixel test being key_image == id.  The key image is read in place (device / pinned) or staged once
+    // into unmask_keys_buf by the enqueue (host).  Dropped on EVERY return of the next dv_track_stereo_enqueue / dv_batch_track_enqueue
+    struct UnmaskKeyJob { int x, y, w, h; uint32_t id; };
+    std::vector<UnmaskKeyJob> unmask_keys; const uint32_t* unmask_key_img = nullptr; int unmask_key_stride = 0, unmask_key_mem = 0; DevBuf unmask_keys_buf;
+    // dv_viode_frame_enqueue / _collect: thread T1's per-frame stage (label images -> inverse merged mask, key images, boxes) on the ctx's stream.  Two buffer sets
+    // used alternately: set[cur] belongs to the frame enqueued last; the key images of the frame before stay intact while its objects are tracked
+    struct ViodeFrame* viode = nullptr;      // (defined in dvins_api.hip, released by dv_destroy)
     DevBuf undist_buf[2]; bool undist[2] = { false, false }; int undist_w = 0, undist_h = 0;      // cfg::is_undistort_input: fixed-point maps per camera (map1 | map2)
     bool cam_switched = false; dv_cam cam_orig[2]{};      // dv_undistort_setup: cfg.cam0 / cam1 hold (newK, 0); the cameras the ctx was created with, restored when the maps are removed
     DevBuf out_buf; dv_feat* out_dev = nullptr; int* nout_dev = nullptr;

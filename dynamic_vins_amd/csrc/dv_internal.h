@@ -124,6 +124,12 @@ void dv_launch_unmask(uint8_t* inv_mask, int pitch, int W, int H, int x0, int y0
 struct DvUnmaskRect { const uint8_t* roi; int x, y, w, h; };
 struct DvUnmaskJob { uint8_t* dst; const uint8_t* src; int dpitch, spitch, W, H, first, n; };
 void dv_launch_unmask_multi(const DvUnmaskJob* jobs_dev, int n_jobs, const DvUnmaskRect* rects_dev, int w_max, int h_max, hipStream_t s);
+// the key-image form (dv_track_unmask_static_keys): inv_mask(y0 + r, x0 + c) = 255 where key(y0 + r, x0 + c) == id; key: W x H uint32 (VIODE::PixelToKey), rows of kpitch ELEMENTS, device-addressable
+void dv_launch_unmask_keys(uint8_t* inv_mask, int pitch, int W, int H, int x0, int y0, int w, int h, const uint32_t* key, int kpitch, uint32_t id, hipStream_t s);
+// the ROI masks of all visible objects of a frame from its key image in ONE launch (dv_inst_track_enqueue_keys): dst(r, c) = key(y0 + r, x0 + c) == id ? 255 : 0 for
+// c < w, 0 for w <= c < dpitch (the padding carries a defined value), r < h.  kpitch in ELEMENTS; the rectangle lies inside the key image (checked by the caller)
+struct DvKeyRoiJob { const uint32_t* key; uint8_t* dst; int kpitch, x0, y0, w, h, dpitch; uint32_t id; int pad_; };
+void dv_launch_key_roi_mask_multi(const DvKeyRoiJob* jobs_dev, int n_jobs, int dpitch_max, int h_max, hipStream_t s);
 hipError_t dv_copy_async(void* dst, const void* src, size_t bytes, hipStream_t s);      // copy.hip: device <-> PINNED host (or device <-> device) as a kernel on s — no copy engine in the per-frame path
 int  dv_launch_gftt_select(const GfttSelectArgs& a, hipStream_t s);
 void dv_launch_compact(const DvTrackState& tr, const uint8_t* in_mask, int mask_pitch, int sort_by_cnt, int* n_cand,

@@ -7,6 +7,7 @@
 //   * Shi-Tomasi candidate records + the pinned host staging buffer for the frame's output.
 // The per-frame orchestration of the tracker (one sequence, or a dv_batch group in shared launches) is front_track.hip.
 #include "dv_ctx.h"
+#include "viode_host.h"
 
 static std::string g_last_error;
 static std::mutex g_err_mutex;
@@ -160,6 +161,25 @@ int dv_build_cuda_pyramids(dv_ctx* ctx, PyrSet& C0, PyrSet* C1, const DvPyr& a0,
     return 0;
 }
 
+// dv_viode_frame_enqueue / _collect: thread T1's per-frame stage on the ctx's stream.  Two buffer sets used alternately: set[cur] belongs to the frame enqueued last, the
+// inverse mask and key images of the frame before stay intact while that frame is tracked.
+struct ViodeFrame {
+    struct Set { DevBuf inv, keys0, keys1; } set[2];
+    int cur = 1;
+    DevBuf seg[2], scratch /* planes nobody reads: the merged mask, the right image's two masks */, small /* keys (256 B) | boxes left (1024 B) | boxes right (1024 B) */;
+    uint8_t* pinned = nullptr;      // box initialiser (1024 B) | keys (256 B) | the frame's boxes (1024 B)
+    hipEvent_t ev = nullptr; bool pending = false, has_right = false; int nkeys = 0, keys_on_dev = 0; uint32_t keys[64] = { 0 };
+};
+static void dv_viode_frame_release(dv_ctx* ctx) {
+    ViodeFrame* V = ctx->viode;
+    if (!V) return;
+    for (ViodeFrame::Set& q : V->set) { q.inv.release(); q.keys0.release(); q.keys1.release(); }
+    V->seg[0].release(); V->seg[1].release(); V->scratch.release(); V->small.release();
+    if (V->pinned) (void)hipHostFree(V->pinned);
+    if (V->ev) (void)hipEventDestroy(V->ev);
+    delete V; ctx->viode = nullptr;
+}
+
 extern "C" {
 
 void* dv_pinned_alloc(size_t bytes) {
@@ -248,6 +268,8 @@ void dv_destroy(dv_ctx* ctx) {
     if (ctx->be_stream) (void)hipStreamDestroy(ctx->be_stream);
     if (ctx->out_pinned) (void)hipHostFree(ctx->out_pinned);
     if (ctx->unmask_pinned) (void)hipHostFree(ctx->unmask_pinned);
+    ctx->unmask_keys_buf.release();
+    dv_viode_frame_release(ctx);
     if (ctx->done) (void)hipEventDestroy(ctx->done);
     if (ctx->ev_pyr) (void)hipEventDestroy(ctx->ev_pyr);
     if (ctx->ev_bg_select) (void)hipEventDestroy(ctx->ev_bg_select);
@@ -499,6 +521,89 @@ int dv_viode_mask(dv_ctx* ctx, const uint8_t* seg_bgr, int w, int h, int stride,
     DV_CHECK(hipMemcpyAsync(boxes, d_box, 16 * (size_t)nkeys, hipMemcpyDeviceToHost, s));
     DV_CHECK(hipStreamSynchronize(s));
     for (int k = 0; k < nkeys; ++k) if (boxes[4 * k + 1] < 0) { boxes[4 * k] = boxes[4 * k + 2] = -1; boxes[4 * k + 3] = -1; }      // key not present
+    return 0;
+}
+
+// ImageProcessor::Run's VIODE branch for ONE frame (image_process/image_process.cpp:161-178 -> VIODE::SetViodeMaskAndRoi, utils/dataset/viode_utils.cpp:21-218) as enqueue +
+// collect: viode_mask_kernel on the left label image (and on the right one: its key image is what TrackRightByPad tests) into library-owned device buffers; the boxes of
+// the left image — nkeys x 16 bytes — are the frame's ONLY device -> host traffic (the host sizes the job tables of the object tracker from the rectangles).
+int dv_viode_frame_enqueue(dv_ctx* ctx, const uint8_t* seg0_bgr, const uint8_t* seg1_bgr_or_null, int w, int h, int stride, int mem, const uint32_t* dyn_keys, int nkeys) {
+    if (!ctx) return -1;
+    if (!seg0_bgr || !dyn_keys) DV_FAIL("dv_viode_frame_enqueue: null label image / key table");
+    if (w != ctx->cfg.width || h != ctx->cfg.height) DV_FAIL("dv_viode_frame_enqueue: image size differs from config");
+    if (stride == 0) stride = 3 * w;
+    if (stride < 3 * w) DV_FAIL("dv_viode_frame_enqueue: stride below 3 * width");
+    if (nkeys < 1 || nkeys > 64) DV_FAIL("dv_viode_frame_enqueue: 1..64 dynamic keys");
+    if (mem != DV_MEM_HOST && mem != DV_MEM_DEVICE && mem != DV_MEM_PINNED) DV_FAIL("dv_viode_frame_enqueue: unknown memory kind");
+    if (ctx->viode && ctx->viode->pending) DV_FAIL("dv_viode_frame_enqueue: previous frame not collected");
+    DV_CHECK(hipSetDevice(ctx->cfg.device));
+    hipStream_t s = ctx->stream;
+    if (!ctx->viode) {
+        ViodeFrame* N = new ViodeFrame();
+        ctx->viode = N;          // (a half-built one is completed by the next call or released by dv_destroy)
+    }
+    ViodeFrame& V = *ctx->viode;
+    if (!V.ev) DV_CHECK(hipEventCreateWithFlags(&V.ev, hipEventDisableTiming));
+    if (!V.pinned) {
+        void* p = nullptr;
+        DV_CHECK(hipHostMalloc(&p, 1024 + 256 + 1024, hipHostMallocDefault));
+        V.pinned = (uint8_t*)p;
+        int32_t* init = (int32_t*)V.pinned;
+        for (int k = 0; k < 64; ++k) { init[4 * k] = 0x7fffffff; init[4 * k + 1] = -1; init[4 * k + 2] = 0x7fffffff; init[4 * k + 3] = -1; }
+    }
+    const int mp = w, sp = align_up(3 * w, 16);          // the masks are tightly packed: the inverse mask goes to dv_track_stereo_enqueue as a DV_MEM_DEVICE mask beside gray frames of stride w
+    const size_t plane = ((size_t)mp * h + 255) / 256 * 256;
+    ViodeFrame::Set& Q = V.set[V.cur ^ 1];
+    DV_CHECK(Q.inv.ensure(plane)); DV_CHECK(Q.keys0.ensure((size_t)4 * w * h));
+    if (seg1_bgr_or_null) DV_CHECK(Q.keys1.ensure((size_t)4 * w * h));
+    DV_CHECK(V.scratch.ensure(3 * plane)); DV_CHECK(V.small.ensure(256 + 2048));
+    // the set about to be overwritten held the frame before the last: the objects of that frame may still read its key images on the object tracker's stream
+    if (dv_inst_wait_before_next_frame(ctx, s, false)) DV_FAIL("dv_viode_frame_enqueue: hipStreamWaitEvent");
+    uint32_t* d_keys = (uint32_t*)V.small.p; int32_t* d_box0 = (int32_t*)((uint8_t*)V.small.p + 256); int32_t* d_box1 = d_box0 + 256;
+    if (V.keys_on_dev != nkeys || std::memcmp(V.keys, dyn_keys, 4 * (size_t)nkeys) != 0) {      // (no frame is in flight: the pinned copy of the table is not being read)
+        std::memcpy(V.keys, dyn_keys, 4 * (size_t)nkeys); std::memcpy(V.pinned + 1024, dyn_keys, 4 * (size_t)nkeys);
+        DV_CHECK(dv_copy_async(d_keys, V.pinned + 1024, 256, s));
+        V.keys_on_dev = nkeys;
+    }
+    V.nkeys = nkeys;
+    DV_CHECK(dv_copy_async(d_box0, V.pinned, 1024, s));          // the box buffers start every frame at (max, -1, max, -1)
+    if (seg1_bgr_or_null) DV_CHECK(dv_copy_async(d_box1, V.pinned, 1024, s));
+    const uint8_t* src[2] = { seg0_bgr, seg1_bgr_or_null }; int spitch = stride;
+    if (mem == DV_MEM_HOST) {
+        for (int i = 0; i < 2; ++i) if (src[i]) {
+            DV_CHECK(V.seg[i].ensure((size_t)sp * h));
+            DV_CHECK(hipMemcpy2DAsync(V.seg[i].p, sp, src[i], stride, (size_t)3 * w, h, hipMemcpyHostToDevice, s));
+            src[i] = (const uint8_t*)V.seg[i].p;
+        }
+        spitch = sp;
+    }
+    uint8_t* sc = (uint8_t*)V.scratch.p;
+    {
+        StageScope sc_t(ctx, "viode_frame");
+        dv_launch_viode_mask(src[0], w, h, spitch, d_keys, nkeys, sc, (uint8_t*)Q.inv.p, mp, (uint32_t*)Q.keys0.p, d_box0, s);
+        if (src[1]) dv_launch_viode_mask(src[1], w, h, spitch, d_keys, nkeys, sc + plane, sc + 2 * plane, mp, (uint32_t*)Q.keys1.p, d_box1, s);
+    }
+    DV_CHECK(hipGetLastError());
+    DV_CHECK(dv_copy_async(V.pinned + 1280, d_box0, 1024, s));
+    DV_CHECK(hipEventRecord(V.ev, s));
+    V.cur ^= 1; V.pending = true; V.has_right = seg1_bgr_or_null != nullptr;
+    return 0;
+}
+
+int dv_viode_frame_collect(dv_ctx* ctx, int min_inst_size, dv_inst_det* dets, int cap, int* n_dets, const uint8_t** inv_mask_dev, const uint32_t** keys0_dev, const uint32_t** keys1_dev) {
+    if (!ctx) return -1;
+    if (!ctx->viode || !ctx->viode->pending) DV_FAIL("dv_viode_frame_collect: nothing enqueued");
+    if (!n_dets || cap < 0 || (cap > 0 && !dets)) DV_FAIL("dv_viode_frame_collect: bad argument");
+    ViodeFrame& V = *ctx->viode;
+    DV_CHECK(hipEventSynchronize(V.ev));
+    V.pending = false;
+    const int n = dv_viode_build_dets((const int32_t*)(V.pinned + 1280), V.keys, V.nkeys, min_inst_size, dets, cap);
+    if (n < 0) DV_FAIL("dv_viode_frame_collect: more detections than `cap`");
+    *n_dets = n;
+    const ViodeFrame::Set& Q = V.set[V.cur];
+    if (inv_mask_dev) *inv_mask_dev = (const uint8_t*)Q.inv.p;
+    if (keys0_dev) *keys0_dev = (const uint32_t*)Q.keys0.p;
+    if (keys1_dev) *keys1_dev = V.has_right ? (const uint32_t*)Q.keys1.p : nullptr;
     return 0;
 }
 

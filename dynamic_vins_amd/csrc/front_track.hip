@@ -134,6 +134,8 @@ int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gr
                             const uint8_t* mask_or_null, int mode, int mem) {
     if (!ctx) return -1;
     HostScope hs(ctx, "h_front_enqueue");
+    // what dv_track_unmask_static_keys staged belongs to THIS call: applied below, or dropped with whichever return ends the call
+    struct KeyJobsGuard { dv_ctx* c; ~KeyJobsGuard() { c->unmask_keys.clear(); c->unmask_key_img = nullptr; } } key_jobs_guard{ ctx };
     if (!gray0) DV_FAIL("dv_track_stereo: gray0 is null");
     if (w != ctx->cfg.width || h != ctx->cfg.height) DV_FAIL("dv_track_stereo: image size differs from config (reference: std::terminate, main.cpp:95-99)");
     if (ctx->pending) DV_FAIL("dv_track_stereo_enqueue: previous frame not collected");
@@ -173,6 +175,25 @@ int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gr
         for (const dv_ctx::UnmaskJob& j : ctx->unmask)
             dv_launch_unmask((uint8_t*)ctx->mask_buf.p, mask_pitch, w, h, j.x, j.y, j.w, j.h, (const uint8_t*)ctx->unmask_pinned + j.off, s);
         ctx->unmask.clear();
+        if (front_plan_mask(ctx, mode, mask_dev, mask_pitch, P)) return -1;
+    }
+    if (!ctx->unmask_keys.empty()) {     // the key-image form of the same step (dv_track_unmask_static_keys): the per-pixel test is key == id
+        const uint8_t* mask_dev = P.mask; int mask_pitch = P.mask_pitch;
+        if (!mask_dev) DV_FAIL("dv_track_unmask_static_keys: the frame carries no mask");
+        if (mask_dev != (const uint8_t*)ctx->mask_buf.p) {          // the caller's device buffer is not written to: work on a copy
+            const int mp = align_up(w, 16);
+            DV_CHECK(ctx->mask_buf.ensure((size_t)mp * h));
+            DV_CHECK(hipMemcpy2DAsync(ctx->mask_buf.p, mp, mask_dev, mask_pitch, w, h, hipMemcpyDeviceToDevice, s));
+            mask_dev = (const uint8_t*)ctx->mask_buf.p; mask_pitch = mp;
+        }
+        const uint32_t* kimg = ctx->unmask_key_img; int kpitch = ctx->unmask_key_stride / 4;
+        if (ctx->unmask_key_mem == DV_MEM_HOST) {                   // staged once for the frame
+            DV_CHECK(ctx->unmask_keys_buf.ensure((size_t)4 * w * h));
+            DV_CHECK(hipMemcpy2DAsync(ctx->unmask_keys_buf.p, (size_t)4 * w, kimg, (size_t)ctx->unmask_key_stride, (size_t)4 * w, h, hipMemcpyHostToDevice, s));
+            kimg = (const uint32_t*)ctx->unmask_keys_buf.p; kpitch = w;
+        }
+        for (const dv_ctx::UnmaskKeyJob& j : ctx->unmask_keys)
+            dv_launch_unmask_keys((uint8_t*)ctx->mask_buf.p, mask_pitch, w, h, j.x, j.y, j.w, j.h, kimg, kpitch, j.id, s);
         if (front_plan_mask(ctx, mode, mask_dev, mask_pitch, P)) return -1;
     }
     if (P.has_erode) { const DvErodeJob& k = P.erode; dv_launch_erode(k.src, k.w, k.h, k.spitch, k.k, k.tmp, k.tpitch, k.dst, k.dpitch, s); }
@@ -239,6 +260,33 @@ int dv_track_unmask_static(dv_ctx* ctx, const dv_inst_det* dets, int n_dets, con
         ctx->unmask.push_back({ d.x, d.y, d.w, d.h, off });
         off += ((size_t)d.w * d.h + 15) / 16 * 16;
     }
+    return 0;
+}
+
+// the key-image form: the same rectangle jobs, the ROI mask of detection d being key_image(y + d.y, x + d.x) == d.track_id (dv_inst_det::mask is ignored).  The key
+// image is read in place by the next dv_track_stereo_enqueue (device / pinned) or staged there once (host): it must stay valid until that call returns — host — or
+// until the frame is collected — device / pinned
+int dv_track_unmask_static_keys(dv_ctx* ctx, const dv_inst_det* dets, int n_dets, const uint32_t* static_ids, int n_static, const uint32_t* key_image, int stride_bytes, int mem) {
+    if (!ctx) return -1;
+    ctx->unmask_keys.clear(); ctx->unmask_key_img = nullptr;
+    if (n_static <= 0 || n_dets <= 0) return 0;
+    if (!dets || !static_ids) DV_FAIL("dv_track_unmask_static_keys: null argument");
+    if (!key_image) DV_FAIL("dv_track_unmask_static_keys: null key image");
+    if (mem != DV_MEM_HOST && mem != DV_MEM_DEVICE && mem != DV_MEM_PINNED) DV_FAIL("dv_track_unmask_static_keys: unknown memory kind");
+    if (stride_bytes == 0) stride_bytes = 4 * ctx->cfg.width;
+    if (stride_bytes < 4 * ctx->cfg.width || (stride_bytes & 3)) DV_FAIL("dv_track_unmask_static_keys: bad stride");
+    if (ctx->pending) DV_FAIL("dv_track_unmask_static_keys: call it before dv_track_stereo_enqueue of the frame it belongs to");
+    for (int i = 0; i < n_dets; ++i) {          // every rectangle is checked before a job is staged: the kernel's reads are bounded by them
+        const dv_inst_det& d = dets[i];
+        if (std::find(static_ids, static_ids + n_static, d.track_id) == static_ids + n_static) continue;
+        if (d.w <= 0 || d.h <= 0 || d.x < 0 || d.y < 0 || d.w > ctx->cfg.width || d.h > ctx->cfg.height || d.x > ctx->cfg.width - d.w || d.y > ctx->cfg.height - d.h) DV_FAIL("dv_track_unmask_static_keys: detection rectangle outside the image");
+    }
+    for (int i = 0; i < n_dets; ++i) {
+        const dv_inst_det& d = dets[i];
+        if (std::find(static_ids, static_ids + n_static, d.track_id) == static_ids + n_static) continue;
+        ctx->unmask_keys.push_back({ d.x, d.y, d.w, d.h, d.track_id });
+    }
+    if (!ctx->unmask_keys.empty()) { ctx->unmask_key_img = key_image; ctx->unmask_key_stride = stride_bytes; ctx->unmask_key_mem = mem; }
     return 0;
 }
 
@@ -328,7 +376,7 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
     // a refused / failed call — no job survives into a later frame
     struct UnmaskGuard {
         const std::vector<dv_ctx*>& mem; const dv_track_job* jobs; int n;
-        ~UnmaskGuard() { for (int i = 0; i < n; ++i) if (jobs[i].member >= 0 && jobs[i].member < (int)mem.size()) mem[jobs[i].member]->unmask.clear(); }
+        ~UnmaskGuard() { for (int i = 0; i < n; ++i) if (jobs[i].member >= 0 && jobs[i].member < (int)mem.size()) { mem[jobs[i].member]->unmask.clear(); mem[jobs[i].member]->unmask_keys.clear(); } }
     } unmask_guard{ mem, jobs, n };
     for (int i = 0; i < n; ++i) {
         const dv_track_job& j = jobs[i];
@@ -336,6 +384,7 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
         for (int q = 0; q < i; ++q) if (jobs[q].member == j.member) DV_FAIL("dv_batch_track_enqueue: a member appears twice");
         const dv_ctx* c = mem[j.member];
         if (c->timing || !j.gray0 || (c->cfg.stereo && !j.gray1)) continue;
+        if (!c->unmask_keys.empty()) continue;          // dv_track_unmask_static_keys jobs: the member's own entry applies them (the round's unmask launch reads host masks)
         if (j.mode == DV_MODE_SEMANTIC && j.mask) kind[i] = K_SEMANTIC;
         else if (c->inst) continue;
         else if (j.mode == DV_MODE_RAW && !j.mask) kind[i] = K_RAW;

@@ -34,6 +34,19 @@ __global__ __launch_bounds__(256) void roi_pad_multi_kernel(const RoiJob* __rest
     j.dst[(size_t)y * j.dpitch + x] = (x < j.w && y < j.h) ? j.src[(size_t)(j.y0 + y) * j.spitch + j.x0 + x] : (uint8_t)0;
 }
 
+// dv_inst_track_enqueue_keys: the ROI masks of ALL visible objects of the frame from its key image (VIODE::PixelToKey of seg0), in the layout the host copy of
+// dv_inst_track_enqueue produces (pitch align_up(w, 16)).  blockIdx.z = object, a workgroup covers 64 columns x 4 rows of the padded slice: a wave reads 64 consecutive
+// dwords of one key-image row (256 contiguous bytes, dword aligned whatever x0 and the row stride are) and writes 64 consecutive mask bytes; the padding columns are
+// written as zero, so no byte of the slice depends on an earlier frame.
+__global__ __launch_bounds__(256) void key_roi_mask_multi_kernel(const DvKeyRoiJob* __restrict__ jobs) {
+    const DvKeyRoiJob j = jobs[blockIdx.z];
+    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
+    if (c >= j.dpitch || r >= j.h) return;
+    uint8_t v = 0;
+    if (c < j.w) v = j.key[(size_t)(j.y0 + r) * j.kpitch + j.x0 + c] == j.id ? (uint8_t)255 : (uint8_t)0;
+    j.dst[(size_t)r * j.dpitch + c] = v;
+}
+
 struct RoiPyr {          // pyramid storage with a fixed capacity (the full frame), re-laid-out per frame without re-allocation
     DevBuf buf; DvPyr pyr{}; int w = 0, h = 0;
     hipError_t reserve(int W, int H) {
@@ -89,11 +102,12 @@ struct dv_inst_tracker {
     std::vector<unsigned> out_order;                            // ids written this frame, in output order
     // extra points from the frame's disparity map (dv_inst_set_disparity; extra_points.hip): the reference's second thread = a side stream
     const float* disp_user = nullptr; int disp_stride = 0, disp_mem = 0; double disp_baseline = 0; bool disp_next = false, xp_frame = false, xp_inflight = false;
-    const uint32_t* keys_user = nullptr; int keys_stride = 0, keys_mem = 0; bool keys_next = false; DevBuf keys_buf;      // VIODE: seg1's key image of the next frame (dv_inst_set_right_keys)
+    const uint32_t* keys_user = nullptr; int keys_stride = 0, keys_mem = 0; bool keys_next = false; DevBuf keys_buf;
+    DevBuf keys0_buf;          // dv_inst_track_enqueue_keys with a DV_MEM_HOST key image: staged once per frame      // VIODE: seg1's key image of the next frame (dv_inst_set_right_keys)
     DevBuf disp_buf, xp_pool; hipStream_t xstream = nullptr; hipEvent_t ev_xin = nullptr, ev_xdone = nullptr;
     void* xp_pinned = nullptr; size_t xp_cap_slots = 0;          // per output slot: count (64 bytes) + 3 * DV_XP_CAP doubles, written by the kernel straight into pinned memory
     ~dv_inst_tracker() {
-        disp_buf.release(); xp_pool.release(); keys_buf.release();
+        disp_buf.release(); xp_pool.release(); keys_buf.release(); keys0_buf.release();
         if (xstream) { (void)hipStreamSynchronize(xstream); (void)hipStreamDestroy(xstream); }
         if (ev_xin) (void)hipEventDestroy(ev_xin);
         if (ev_xdone) (void)hipEventDestroy(ev_xdone);
@@ -110,6 +124,10 @@ struct dv_inst_tracker {
 };
 
 void dv_inst_destroy_internal(dv_inst_tracker* t) { delete t; }
+void dv_launch_key_roi_mask_multi(const DvKeyRoiJob* jobs_dev, int n_jobs, int dpitch_max, int h_max, hipStream_t s) {
+    if (n_jobs <= 0 || dpitch_max <= 0 || h_max <= 0) return;
+    hipLaunchKernelGGL(key_roi_mask_multi_kernel, dim3((dpitch_max + 63) / 64, (h_max + 3) / 4, n_jobs), dim3(64, 4), 0, s, jobs_dev);
+}
 // the background tracker's next frame, built on s (the ctx's own stream, or its dv_batch's front-end stream), must not rebuild the right pyramid while the objects of the
 // previous frame still read it.  consume = false: the wait is enqueued and the ctx is left as it is (the group entry changes no ctx before its round's commit: a refused
 // round must leave the member's next frame its wait, and a second wait for an event that has fired costs nothing)
@@ -203,8 +221,10 @@ int dv_inst_reset(dv_ctx* ctx) {
     return 0;
 }
 
-int dv_inst_track_enqueue(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_dets, const dv_box3d* boxes3d, int n_boxes3d) {
-    if (!ctx) return -1;
+// the frame's object masks: the detections' own host masks (dv_inst_track_enqueue: ks == nullptr) or the comparison of the frame's key image with each detection's
+// track id, done on the device (dv_inst_track_enqueue_keys)
+struct InstKeySrc { const uint32_t* img; int stride_bytes, mem; };
+static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_dets, const dv_box3d* boxes3d, int n_boxes3d, const InstKeySrc* ks) {
     HostScope hs(ctx, "h_inst_enqueue");
     if (!ctx->inst) DV_FAIL("dv_inst_track: call dv_inst_config first");
     if (n_dets < 0 || (n_dets > 0 && !dets) || n_boxes3d < 0 || (n_boxes3d > 0 && !boxes3d)) DV_FAIL("dv_inst_track: bad argument");
@@ -229,7 +249,7 @@ int dv_inst_track_enqueue(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_
     for (int i = 0; i < n_dets; ++i) {
         const dv_inst_det& d = dets[i];
         if (d.w <= 0 || d.h <= 0 || d.x < 0 || d.y < 0 || d.x + d.w > W || d.y + d.h > H) DV_FAIL("dv_inst_track: detection rectangle outside the image");
-        if (!d.mask) DV_FAIL("dv_inst_track: detection without a mask");
+        if (!ks && !d.mask) DV_FAIL("dv_inst_track: detection without a mask");
         auto it = T.slots.find(d.track_id);
         if (it == T.slots.end()) {
             it = T.slots.emplace(d.track_id, Slot()).first; it->second.id = d.track_id;
@@ -238,7 +258,8 @@ int dv_inst_track_enqueue(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_
         Slot& S = it->second;
         if (S.visible) DV_FAIL("dv_inst_track: two detections with the same track id");
         S.visible = true; S.has_box2d = true; S.class_id = d.class_id; S.rx = d.x; S.ry = d.y; S.rw = d.w; S.rh = d.h;
-        S.pts_copy.assign(d.points ? d.points : nullptr, d.points ? d.points + 3 * (size_t)std::max(d.n_points, 0) : nullptr);
+        if (ks) S.pts_copy.clear();          // (the key form ignores dv_inst_det::points)
+        else S.pts_copy.assign(d.points ? d.points : nullptr, d.points ? d.points + 3 * (size_t)std::max(d.n_points, 0) : nullptr);
         mask_bytes += (size_t)align_up(d.w, 16) * d.h;
     }
     // ---- InstsTrack (dynamic_tracker.cpp:348-493) ----
@@ -272,7 +293,7 @@ int dv_inst_track_enqueue(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_
         //  hipHostFree + hipHostMalloc resp. two stream synchronisations + hipFree + hipMalloc — 5 - 8 ms during which the estimator thread's HIP calls wait for the runtime's
         //  locks too; seen as one 6 ms frame somewhere in the first frames of the dynamic bench line's timed region in every second run)
         const size_t mask_floor = 2 * (size_t)align_up(W, 16) * H + 4096;
-        if (T.pinned_in_bytes < mask_bytes) {
+        if (!ks && T.pinned_in_bytes < mask_bytes) {
             if (T.pinned_in) (void)hipHostFree(T.pinned_in);
             T.pinned_in = nullptr; T.pinned_in_bytes = 0;
             const size_t want = std::max(mask_bytes * 2 + 4096, mask_floor);
@@ -315,7 +336,8 @@ int dv_inst_track_enqueue(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_
         // one stream: with four objects a chain of ~50 dependent launches per frame, ~0.8 ms of latency between the enqueue and the rows) ----
         {
             const size_t need = ((size_t)na * 2 * sizeof(RoiJob) + (size_t)na * DV_MAX_LEVELS * sizeof(DvPyrJob) + (size_t)na * sizeof(DvExtraJob) +
-                                 (size_t)na * (sizeof(DvCompactJob) + sizeof(DvErodeJob) + sizeof(GfttTileArgs) + sizeof(GfttSelectArgs) + sizeof(DvFinalizeJob)) + 4096);
+                                 (size_t)na * (sizeof(DvCompactJob) + sizeof(DvErodeJob) + sizeof(GfttTileArgs) + sizeof(GfttSelectArgs) + sizeof(DvFinalizeJob)) + 4096) +
+                                (ks ? (size_t)na * sizeof(DvKeyRoiJob) + 256 : 0);
             if (need > T.arena_cap) {
                 DV_CHECK(hipStreamSynchronize(s));
                 const size_t cap = need * 2;
@@ -337,10 +359,19 @@ int dv_inst_track_enqueue(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_
         // the tables of stages C and E behind them
         auto up256 = [](size_t v) { return (v + 255) / 256 * 256; };
         const size_t cj_off = up256(xp_off + (size_t)na * sizeof(DvExtraJob)), ej_off = up256(cj_off + (size_t)na * sizeof(DvCompactJob)), gt_off = up256(ej_off + (size_t)na * sizeof(DvErodeJob)),
-                     gs_off = up256(gt_off + (size_t)na * sizeof(GfttTileArgs)), fj_off = up256(gs_off + (size_t)na * sizeof(GfttSelectArgs)), arena_used = fj_off + (size_t)na * sizeof(DvFinalizeJob);
+                     gs_off = up256(gt_off + (size_t)na * sizeof(GfttTileArgs)), fj_off = up256(gs_off + (size_t)na * sizeof(GfttSelectArgs)),
+                     kj_off = up256(fj_off + (size_t)na * sizeof(DvFinalizeJob)), arena_used = ks ? kj_off + (size_t)na * sizeof(DvKeyRoiJob) : fj_off + (size_t)na * sizeof(DvFinalizeJob);
         DvCompactJob* h_cj = (DvCompactJob*)((uint8_t*)T.arena_pinned + cj_off); DvErodeJob* h_ej = (DvErodeJob*)((uint8_t*)T.arena_pinned + ej_off);
         GfttTileArgs* h_gt = (GfttTileArgs*)((uint8_t*)T.arena_pinned + gt_off); GfttSelectArgs* h_gs = (GfttSelectArgs*)((uint8_t*)T.arena_pinned + gs_off);
         DvFinalizeJob* h_fj = (DvFinalizeJob*)((uint8_t*)T.arena_pinned + fj_off);
+        // the key form: one job per object for key_roi_mask_multi_kernel behind the other tables in the same upload; a host key image is staged once for the frame
+        DvKeyRoiJob* h_kj = (DvKeyRoiJob*)((uint8_t*)T.arena_pinned + kj_off); int key_P = 0, key_H = 0;
+        const uint32_t* kimg0 = ks ? ks->img : nullptr; int kpitch0 = ks ? ks->stride_bytes / 4 : 0;
+        if (ks && na > 0 && ks->mem == DV_MEM_HOST) {
+            DV_CHECK(T.keys0_buf.ensure((size_t)W * H * 4));
+            DV_CHECK(hipMemcpy2DAsync(T.keys0_buf.p, (size_t)W * 4, ks->img, (size_t)ks->stride_bytes, (size_t)W * 4, H, hipMemcpyHostToDevice, s));
+            kimg0 = (const uint32_t*)T.keys0_buf.p; kpitch0 = W;
+        }
         int ero_W = 0, ero_H = 0, nj = 0;
         const double dt_fin = dt;
         T.xp_frame = T.disp_next; T.disp_next = false;
@@ -357,10 +388,16 @@ int dv_inst_track_enqueue(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_
             Slot& S = *Sp;
             const int w = S.rw, h = S.rh;
             const int mp = align_up(w, 16);
-            uint8_t* hm = (uint8_t*)T.pinned_in + moff; moff += (size_t)mp * h;
-            const dv_inst_det* det = nullptr; for (int i = 0; i < n_dets; ++i) if (dets[i].track_id == S.id) det = &dets[i];
-            for (int y = 0; y < h; ++y) std::memcpy(hm + (size_t)y * mp, det->mask + (size_t)y * w, w);
-            S.mask = (uint8_t*)T.mask_all.p + (hm - (uint8_t*)T.pinned_in);
+            S.mask = (uint8_t*)T.mask_all.p + moff;
+            if (ks) {
+                h_kj[nj] = DvKeyRoiJob{ kimg0, S.mask, kpitch0, S.rx, S.ry, w, h, mp, S.id, 0 };
+                key_P = std::max(key_P, mp); key_H = std::max(key_H, h);
+            } else {
+                uint8_t* hm = (uint8_t*)T.pinned_in + moff;
+                const dv_inst_det* det = nullptr; for (int i = 0; i < n_dets; ++i) if (dets[i].track_id == S.id) det = &dets[i];
+                for (int y = 0; y < h; ++y) std::memcpy(hm + (size_t)y * mp, det->mask + (size_t)y * w, w);
+            }
+            moff += (size_t)mp * h;
             if (T.xp_frame) {          // ProcessExtraPoints visits the visible objects (ExecInst + is_curr_visible); slot k of the pinned output = k-th active object = its output index
                 uint8_t* xo = (uint8_t*)T.xp_pinned + (size_t)n_xp * xp_slot_bytes;
                 h_xp[n_xp++] = DvExtraJob{ (const uint8_t*)S.mask, mp, w, h, S.rx, S.ry, dv_extra_points_step(h, w), (double*)(xo + 64), (int*)xo };
@@ -410,8 +447,9 @@ int dv_inst_track_enqueue(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_
             }
         }
         if (na > 0) {
-            DV_CHECK(dv_copy_async(T.mask_all.p, T.pinned_in, moff, s));
+            if (!ks) DV_CHECK(dv_copy_async(T.mask_all.p, T.pinned_in, moff, s));
             DV_CHECK(dv_copy_async(T.arena.p, T.arena_pinned, arena_used, s));
+            if (ks) dv_launch_key_roi_mask_multi((const DvKeyRoiJob*)((const uint8_t*)T.arena.p + kj_off), na, key_P, key_H, s);
             if (T.xp_frame && n_xp > 0) {
                 // the reference starts a thread for this (dynamic_tracker.cpp:378): a side stream behind the mask + table uploads; the objects' tracking goes on meanwhile
                 DV_CHECK(hipEventRecord(T.ev_xin, s));
@@ -487,6 +525,26 @@ int dv_inst_track_enqueue(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_
     DV_CHECK(hipEventRecord(T.done, s));
     T.last_time = T.cur_time; T.pending = true; T.frame_enqueued = true;
     return 0;
+}
+
+int dv_inst_track_enqueue(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_dets, const dv_box3d* boxes3d, int n_boxes3d) {
+    if (!ctx) return -1;
+    return inst_track_enqueue_impl(ctx, t, dets, n_dets, boxes3d, n_boxes3d, nullptr);
+}
+
+// the key-image form (include/dvins.h): mask of detection d = key_image(y + d.y, x + d.x) == d.track_id over its rectangle, cut on the device
+int dv_inst_track_enqueue_keys(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_dets, const uint32_t* key_image, int stride_bytes, int mem, const dv_box3d* boxes3d, int n_boxes3d) {
+    if (!ctx) return -1;
+    if (!key_image) DV_FAIL("dv_inst_track_enqueue_keys: null key image");
+    if (mem != DV_MEM_HOST && mem != DV_MEM_DEVICE && mem != DV_MEM_PINNED) DV_FAIL("dv_inst_track_enqueue_keys: unknown memory kind");
+    if (stride_bytes == 0) stride_bytes = 4 * ctx->cfg.width;
+    if (stride_bytes < 4 * ctx->cfg.width || (stride_bytes & 3)) DV_FAIL("dv_inst_track_enqueue_keys: bad stride");
+    for (int i = 0; i < n_dets && dets; ++i) {          // (checked again by the common part; here for the entry's own message)
+        const dv_inst_det& d = dets[i];
+        if (d.w <= 0 || d.h <= 0 || d.x < 0 || d.y < 0 || d.x + d.w > ctx->cfg.width || d.y + d.h > ctx->cfg.height) DV_FAIL("dv_inst_track_enqueue_keys: detection rectangle outside the image");
+    }
+    const InstKeySrc ks{ key_image, stride_bytes, mem };
+    return inst_track_enqueue_impl(ctx, t, dets, n_dets, boxes3d, n_boxes3d, &ks);
 }
 
 // VIODE: the keys of SemanticImage::seg1 of the frame the NEXT dv_inst_track_enqueue processes (include/dvins.h)

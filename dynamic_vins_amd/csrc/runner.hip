@@ -28,6 +28,13 @@
 #include <vector>
 #include "dv_ctx.h"
 
+// The entries of a label-image sequence (dv_runner_set_viode).  Weak references: this file is also linked, as plain C++, into host-only sanitizer harnesses whose
+// stand-in C ABI knows only the entries of the pre-computed path; dv_runner_set_viode refuses when they are absent.  In the library they bind as usual.
+#pragma weak dv_viode_frame_enqueue
+#pragma weak dv_viode_frame_collect
+#pragma weak dv_track_unmask_static_keys
+#pragma weak dv_inst_track_enqueue_keys
+
 namespace {
 // choice T1: DV_STATIC_REPORT_LAG (DVINS_STATIC_LAG in the environment: experiments only — the Python pipeline and the parity harness read the same variable)
 int static_lag() { static const int v = [] { const char* e = std::getenv("DVINS_STATIC_LAG"); const int k = e ? std::atoi(e) : DV_STATIC_REPORT_LAG; return k >= 1 && k <= 3 ? k : DV_STATIC_REPORT_LAG; }(); return v; }
@@ -71,6 +78,10 @@ struct RSeq {
     // that enqueue), in every host layout.  snaps / est_passed are guarded by ring_mu.
     struct StaticSnap { int frame = -1; std::vector<uint32_t> ids; };
     bool static_unmask = false; StaticSnap snaps[4]; int snap_next = 0, est_passed = -1;
+    // dv_runner_set_viode: thread T1's stage per frame.  live_dets / live_* = what dv_viode_frame_collect handed back for the frame being enqueued; live_enq = the frame whose
+    // stage is enqueued and not collected yet (-1: none).  Touched by the thread that enqueues the tracking alone (T2, or the one-thread loop)
+    bool live = false; dv_seq_viode vio{}; std::vector<dv_inst_det> live_dets; int live_n = 0, live_enq = -1;
+    const uint8_t* live_inv = nullptr; const uint32_t* live_k0 = nullptr; const uint32_t* live_k1 = nullptr;
     // TrackImageNaive over the sequence (dv_runner_set_mask): per frame the inverse merged instance mask, and the tracking mode that takes it
     const uint8_t* const* raw_mask = nullptr; int raw_mode = DV_MODE_RAW;
 };
@@ -156,7 +167,34 @@ int dyn_enqueue_objects(dv_runner* R, RSeq& s, int k) {
     s.enqueued = true; s.started = true;
     return 0;
 }
+// a label-image sequence (dv_runner_set_viode): T1's stage of frame k is collected (enqueued first, if frame k - 1 did not do it), then FeatureTrack's calls in their
+// key-image forms, then T1's stage of frame k + 1 is enqueued behind them — its boxes arrive while the host is busy with frame k
+int dyn_viode_stage(dv_runner* R, RSeq& s, int k) {
+    const dv_seq_viode& v = s.vio;
+    if (dv_viode_frame_enqueue(s.ctx, v.seg0[k], v.seg1 ? v.seg1[k] : nullptr, s.w, s.h, v.stride, v.mem, v.dyn_keys, v.nkeys)) return fail(R, s, "dv_viode_frame_enqueue");
+    s.live_enq = k;
+    return 0;
+}
+int dyn_enqueue_live(dv_runner* R, RSeq& s, int k) {
+    const dv_seq_dynamic& d = s.dyn;
+    if (s.live_enq != k && dyn_viode_stage(R, s, k)) return -1;
+    s.live_enq = -1;
+    if (dv_viode_frame_collect(s.ctx, s.vio.min_inst_size, s.live_dets.data(), (int)s.live_dets.size(), &s.live_n, &s.live_inv, &s.live_k0, &s.live_k1)) return fail(R, s, "dv_viode_frame_collect");
+    if (s.static_unmask && s.live_n > 0) {
+        std::vector<uint32_t> ids;
+        { std::lock_guard<std::mutex> lk(*s.ring_mu); int best = -1; for (const RSeq::StaticSnap& sn : s.snaps) if (sn.frame >= 0 && sn.frame <= k - static_lag() && sn.frame > best) { best = sn.frame; ids = sn.ids; } }
+        if (dv_track_unmask_static_keys(s.ctx, s.live_dets.data(), s.live_n, ids.data(), (int)ids.size(), s.live_k0, 0, DV_MEM_DEVICE)) return fail(R, s, "dv_track_unmask_static_keys");
+    }
+    if (dv_track_stereo_enqueue(s.ctx, s.in.left[k], s.in.right[k], s.w, s.h, s.stride, s.in.times[k], s.live_inv, DV_MODE_SEMANTIC, s.in.mem)) return fail(R, s, "dv_track_stereo_enqueue");
+    if (d.disp && d.disp[k] && dv_inst_set_disparity(s.ctx, d.disp[k], d.disp_stride, d.disp_mem, d.baseline)) return fail(R, s, "dv_inst_set_disparity");
+    if (s.live_k1 && dv_inst_set_right_keys(s.ctx, s.live_k1, 0, DV_MEM_DEVICE)) return fail(R, s, "dv_inst_set_right_keys");
+    if (dv_inst_track_enqueue_keys(s.ctx, s.in.times[k], s.live_n ? s.live_dets.data() : nullptr, s.live_n, s.live_k0, 0, DV_MEM_DEVICE, nullptr, 0)) return fail(R, s, "dv_inst_track_enqueue_keys");
+    s.enqueued = true; s.started = true;
+    if (k + 1 < s.in.n_frames && dyn_viode_stage(R, s, k + 1)) return -1;
+    return 0;
+}
 int dyn_enqueue(dv_runner* R, RSeq& s, int k) {
+    if (s.live) return dyn_enqueue_live(R, s, k);
     const dv_seq_dynamic& d = s.dyn;
     const int mode = d.mode ? d.mode : DV_MODE_SEMANTIC;
     if (dyn_stage_unmask(R, s, k)) return -1;
@@ -622,7 +660,26 @@ int dv_runner_set_dynamic(dv_runner* R, int seq, const dv_seq_dynamic* dyn) {
     if (s.next != 0 || s.enqueued || s.pending) { R->err = "dv_runner_set_dynamic: the sequence has already started"; return -1; }
     if (!s.ctx->inst) { R->err = "dv_runner_set_dynamic: call dv_inst_config on the sequence's context first"; return -1; }
     if (dyn->inv_mask && dyn->mask_mem != s.in.mem) { R->err = "dv_runner_set_dynamic: mask_mem must equal the frames' mem (dv_track_stereo_enqueue takes frames and mask from one memory kind)"; return -1; }
-    s.dynamic = true; s.dyn = *dyn; s.static_unmask = dyn->static_as_background != 0;
+    s.dynamic = true; s.live = false; s.dyn = *dyn; s.static_unmask = dyn->static_as_background != 0;
+    for (auto& b : s.db) { b.rows.resize(DV_MAX_FEATS); b.insts.resize(64); b.ifeats.resize(64 * 256); b.pts.resize((size_t)3 * 65536); b.valid = false; }
+    for (auto& b : s.ring) { b.rows.resize(DV_MAX_FEATS); b.insts.resize(64); b.ifeats.resize(64 * 256); b.pts.resize((size_t)3 * 65536); b.valid = false; }
+    return 0;
+}
+// A label-image sequence: the dynamic loop above with T1's stage inside it (dyn_enqueue_live)
+int dv_runner_set_viode(dv_runner* R, int seq, const dv_seq_viode* v) {
+    if (!R || seq < 0 || seq >= (int)R->seqs.size() || !v) return -1;
+    RSeq& s = R->seqs[seq];
+    if (s.grouped) { R->err = "dv_runner_set_viode: a sequence of a dv_batch group is not supported (the group's shared unmask launch reads host masks)"; return -1; }
+    if (s.next != 0 || s.enqueued || s.pending || s.tracked_next != 0) { R->err = "dv_runner_set_viode: the sequence has already started"; return -1; }
+    if (!dv_viode_frame_enqueue || !dv_viode_frame_collect || !dv_track_unmask_static_keys || !dv_inst_track_enqueue_keys) { R->err = "dv_runner_set_viode: the label-image entries are not linked into this build"; return -1; }
+    if (!s.ctx->inst) { R->err = "dv_runner_set_viode: call dv_inst_config on the sequence's context first"; return -1; }
+    if (!v->seg0 || !v->dyn_keys || v->nkeys < 1 || v->nkeys > 64) { R->err = "dv_runner_set_viode: label images and 1..64 dynamic keys are needed"; return -1; }
+    if (v->mem != DV_MEM_HOST && v->mem != DV_MEM_DEVICE && v->mem != DV_MEM_PINNED) { R->err = "dv_runner_set_viode: unknown memory kind of the label images"; return -1; }
+    if (s.in.mem != DV_MEM_DEVICE && s.in.mem != DV_MEM_PINNED) { R->err = "dv_runner_set_viode: the frames must be DV_MEM_DEVICE or DV_MEM_PINNED (the inverse mask stays on the device and travels with them)"; return -1; }
+    if (s.stride != s.w) { R->err = "dv_runner_set_viode: the frames' row stride must equal the width (the inverse mask is tightly packed)"; return -1; }
+    s.dynamic = true; s.live = true; s.vio = *v; s.live_enq = -1; s.live_dets.assign(64, dv_inst_det{});
+    s.dyn = dv_seq_dynamic{}; s.dyn.mode = DV_MODE_SEMANTIC; s.dyn.disp = v->disp; s.dyn.disp_mem = v->disp_mem; s.dyn.disp_stride = v->disp_stride; s.dyn.baseline = v->baseline;
+    s.dyn.static_as_background = v->static_as_background; s.static_unmask = v->static_as_background != 0;
     for (auto& b : s.db) { b.rows.resize(DV_MAX_FEATS); b.insts.resize(64); b.ifeats.resize(64 * 256); b.pts.resize((size_t)3 * 65536); b.valid = false; }
     for (auto& b : s.ring) { b.rows.resize(DV_MAX_FEATS); b.insts.resize(64); b.ifeats.resize(64 * 256); b.pts.resize((size_t)3 * 65536); b.valid = false; }
     return 0;

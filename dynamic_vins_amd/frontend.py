@@ -146,6 +146,62 @@ class Context:
             arr[k].track_id, arr[k].x, arr[k].y, arr[k].w, arr[k].h, arr[k].mask = int(d["track_id"]), x, y, w, h, m.ctypes.data
         self._check(self.lib.dv_track_unmask_static(self.h, C.addressof(arr), len(dets), ids.ctypes.data, len(ids)))
 
+    @staticmethod
+    def _det_array(dets):
+        """dv_inst_det[len(dets)] with the rectangles and track ids alone (the key-image entries ignore mask and points)"""
+        arr = (dv_inst_det * max(len(dets), 1))()
+        for k, d in enumerate(dets):
+            x, y, w, h = [int(v) for v in d["rect"]]
+            arr[k].track_id, arr[k].class_id, arr[k].x, arr[k].y, arr[k].w, arr[k].h = int(d["track_id"]), int(d.get("class_id", 0)), x, y, w, h
+        return arr
+
+    def _key_image(self, key_img, mem, stride_bytes):
+        """(pointer, stride in bytes, mem) of a key image: a uint32 [h, w] numpy array (host, kept alive on self) or a raw pointer (int) with the caller's mem / stride"""
+        if isinstance(key_img, np.ndarray):
+            assert key_img.dtype == np.uint32 and key_img.strides[1] == 4
+            self._keyimg_keep = key_img
+            return key_img.ctypes.data, key_img.strides[0], DV_MEM_HOST
+        return (None if key_img is None else int(key_img)), int(stride_bytes), int(mem)
+
+    def inst_track_enqueue_keys(self, t, dets, key_img, mem=DV_MEM_HOST, stride_bytes=0, boxes3d=None):
+        """inst_track_enqueue with the objects' masks cut on the device from the frame's key image: mask of a detection = key_img[rect] == track_id.  dets: dicts with track_id
+        and rect (mask / points are ignored); key_img: uint32 [h, w] numpy array or a device / pinned pointer (int) with mem and stride_bytes."""
+        from .dynsim import BOX3D_DTYPE
+        arr = self._det_array(dets)
+        ptr, stride_bytes, mem = self._key_image(key_img, mem, stride_bytes)
+        b3 = np.ascontiguousarray(boxes3d, BOX3D_DTYPE) if boxes3d is not None else np.zeros(0, BOX3D_DTYPE)
+        self._inst_keep = [arr, b3]
+        self._check(self.lib.dv_inst_track_enqueue_keys(self.h, float(t), C.addressof(arr) if len(dets) else None, len(dets), ptr, stride_bytes, mem, b3.ctypes.data if len(b3) else None, len(b3)))
+
+    def track_unmask_static_keys(self, dets, static_ids, key_img, mem=DV_MEM_HOST, stride_bytes=0):
+        """track_unmask_static from the frame's key image: the pixels with key == track_id inside the rectangles of the static detections leave the merged mask"""
+        ids = np.ascontiguousarray(static_ids, np.uint32)
+        arr = self._det_array(dets)
+        ptr, stride_bytes, mem = self._key_image(key_img, mem, stride_bytes)
+        self._check(self.lib.dv_track_unmask_static_keys(self.h, C.addressof(arr) if len(dets) else None, len(dets), ids.ctypes.data if len(ids) else None, len(ids), ptr, stride_bytes, mem))
+
+    def viode_frame_enqueue(self, seg0, seg1, dyn_keys, mem=DV_MEM_HOST, stride=0):
+        """thread T1's stage of one frame: label images (uint8 [h, w, 3] B G R numpy arrays, or device / pinned pointers with mem and stride) -> library-owned device buffers"""
+        keys = np.ascontiguousarray(dyn_keys, np.uint32)
+        ptrs = []
+        for sg in (seg0, seg1):
+            if isinstance(sg, np.ndarray):
+                assert sg.dtype == np.uint8 and sg.ndim == 3 and sg.strides[1] == 3 and sg.strides[2] == 1
+                ptrs.append(sg.ctypes.data); mem, stride = DV_MEM_HOST, sg.strides[0]
+            else:
+                ptrs.append(None if sg is None else int(sg))
+        self._viode_keep = (seg0, seg1, keys)
+        self._check(self.lib.dv_viode_frame_enqueue(self.h, ptrs[0], ptrs[1], self.cfg.width, self.cfg.height, int(stride), int(mem), keys.ctypes.data, len(keys)))
+
+    def viode_frame_collect(self, min_inst_size=8, cap=64):
+        """-> (dets [dict(track_id, class_id, rect, mask=None, points=None)], inverse merged mask, key image left, key image right or None) — the three as DEVICE POINTERS
+        (int) into the library's buffers of that frame"""
+        arr = (dv_inst_det * max(cap, 1))()
+        n, inv, k0, k1 = C.c_int(0), C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)
+        self._check(self.lib.dv_viode_frame_collect(self.h, int(min_inst_size), C.addressof(arr), int(cap), C.byref(n), C.byref(inv), C.byref(k0), C.byref(k1)))
+        dets = [dict(track_id=int(a.track_id), class_id=int(a.class_id), rect=(int(a.x), int(a.y), int(a.w), int(a.h)), mask=None, points=None) for a in arr[: n.value]]
+        return dets, inv.value, k0.value, k1.value
+
     def inst_set_right_keys(self, key_img, mem=DV_MEM_HOST):
         """VIODE: the key image of seg1 (viode_mask(...)[2]: uint32 [h, w] numpy array, or a device pointer with mem=DV_MEM_DEVICE) of the frame the next inst_track_enqueue
         processes: TrackRightByPad's segmentation-key test (front_end/instance_feature.cpp:263-268)"""

@@ -2,7 +2,10 @@
 // (system/main.cpp:334-421 Run, :59-171 ImageProcess with Dataloader::LoadStereo utils/io/dataloader.cpp:62-88, :178-330 FeatureTrack, :394-404 the estimator
 // thread, Estimator::Output -> SaveBodyTrajectory utils/io/output.cpp:189-227), on the C++ runner of the library (dv_runner, csrc/runner.hip).
 //
-//   dvins_node <config.yaml> <sequence dir> [output dir] [--seq NAME] [--kitti-calib DIR] [--max-frames N] [--device D] [--marg-form info|eigen]
+//   dvins_node <config.yaml> <sequence dir> [output dir] [--seq NAME] [--kitti-calib DIR] [--max-frames N] [--device D] [--marg-form info|eigen] [--live-masks]
+//
+//   --live-masks   VIODE runs in dynamic mode: the label images themselves are kept (pinned) and thread T1's stage — masks, key images, instances — runs per frame on the
+//                  device inside the loop (dv_runner_set_viode), as a live stream would be fed, instead of the pre-pass below.  Same trajectory file, byte for byte.
 //
 //   <sequence dir>/left/*.{pgm,png}  <sequence dir>/right/*.{pgm,png}   stereo pairs, sorted by name like Dataloader's std::sort (8-bit gray, or RGB which is
 //                                                                        reduced with cvtColor's BGR2GRAY fixed-point weights)
@@ -152,7 +155,7 @@ std::string stem(const std::string& path) {
 
 int main(int argc, char** argv) {
     try {
-        std::vector<std::string> pos; std::string seq_name, kitti_calib; int max_frames = 1 << 30, device = 0, marg_form = DV_MARG_INFO, undistort = -1 /* -1: as the file says */;
+        std::vector<std::string> pos; std::string seq_name, kitti_calib; int max_frames = 1 << 30, device = 0, marg_form = DV_MARG_INFO, undistort = -1 /* -1: as the file says */; bool live_masks = false;
         if (argc >= 3 && std::string(argv[1]) == "--decode") {      // dvins_node --decode <image>...: size and a checksum of the decoded gray image (CPU; tests/test_node.py)
             for (int i = 2; i < argc; ++i) {
                 const Gray g = read_image(argv[i]);
@@ -168,6 +171,7 @@ int main(int argc, char** argv) {
             else if (a == "--kitti-calib" && i + 1 < argc) kitti_calib = argv[++i];
             else if (a == "--max-frames" && i + 1 < argc) max_frames = std::atoi(argv[++i]);
             else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
+            else if (a == "--live-masks") live_masks = true;
             else if (a == "--undistort") {          // overrides the file's undistort_input (cfg::is_undistort_input, utils/camera_model.cpp:479-504)
                 const std::string v = i + 1 < argc ? argv[++i] : "";
                 if (v != "0" && v != "1") { std::fprintf(stderr, "dvins_node: --undistort takes 0 or 1, not '%s'\n", v.c_str()); return 2; }
@@ -181,7 +185,7 @@ int main(int argc, char** argv) {
             }
             else pos.push_back(a);
         }
-        if (pos.size() < 2) { std::fprintf(stderr, "usage: dvins_node <config.yaml> <sequence dir> [output dir] [--seq NAME] [--kitti-calib DIR] [--max-frames N] [--device D] [--marg-form info|eigen] [--undistort 0|1]\n"); return 2; }
+        if (pos.size() < 2) { std::fprintf(stderr, "usage: dvins_node <config.yaml> <sequence dir> [output dir] [--seq NAME] [--kitti-calib DIR] [--max-frames N] [--device D] [--marg-form info|eigen] [--undistort 0|1] [--live-masks]\n"); return 2; }
         const std::string cfg_path = pos[0], seq_dir = pos[1], out_dir = pos.size() > 2 ? pos[2] : ".";
         if (seq_name.empty()) seq_name = stem(seq_dir);
         Config cfg = ReadConfig(cfg_path, device, seq_name, kitti_calib);
@@ -196,6 +200,8 @@ int main(int argc, char** argv) {
         // lie on them (the reference remaps the merged mask too, basic/semantic_image.cpp:84-92).  No shipped file combines the two: refused rather than tracked misaligned.
         const bool undistort_on = undistort < 0 ? cfg.undistort_input != 0 : undistort != 0;
         if (undistort_on && viode) throw std::runtime_error("dvins_node: undistort_input with VIODE segmentation masks is not supported (the masks and key images would have to be remapped with the frames)");
+        const bool live = live_masks && run_dynamic;
+        if (live_masks && !live) std::fprintf(stderr, "dvins_node: --live-masks applies to dataset_type viode with slam_type dynamic: ignored\n");
         cfg.est.dynamic = run_dynamic ? 1 : 0; cfg.est.use_line = 0;
         if (run_dynamic) cfg.est.use_det3d = 0;          // (no 3-D detector output in a VIODE directory; viode.yaml ships use_det3d: 0)
 
@@ -242,9 +248,11 @@ int main(int argc, char** argv) {
         const int W = cfg.front.width, H = cfg.front.height;
         const size_t px = (size_t)W * H;
         const bool want_masks = viode, want_keys = run_dynamic;
-        const size_t arena_bytes = (size_t)n * px * (2 + (want_masks ? 1 : 0) + (want_keys ? 4 : 0));
+        const size_t arena_bytes = live ? (size_t)n * px * (2 + 3 + 3)          // --live-masks: the two label images (B G R) in place of mask and key image
+                                        : (size_t)n * px * (2 + (want_masks ? 1 : 0) + (want_keys ? 4 : 0));
         Pinned arena(arena_bytes);
         const int mem = arena.p ? DV_MEM_PINNED : DV_MEM_HOST;
+        if (live && !arena.p) throw std::runtime_error("dvins_node: --live-masks needs the pinned arena (the inverse mask stays on the device and travels with device-addressable frames)");
         if (!arena.p) std::fprintf(stderr, "dvins_node: %zu MB of pinned memory are not available: pageable buffers (DV_MEM_HOST)\n", arena_bytes >> 20);
         std::vector<const uint8_t*> lp(n), rp(n);
         for (int k = 0; k < n; ++k) {
@@ -255,7 +263,8 @@ int main(int argc, char** argv) {
             } else { lp[k] = L[k].d.data(); rp[k] = R[k].d.data(); }
         }
         uint8_t* mask_arena = arena.p ? arena.p + (size_t)n * 2 * px : nullptr;
-        uint32_t* key_arena = (arena.p && want_keys) ? reinterpret_cast<uint32_t*>(arena.p + (size_t)n * (2 + (want_masks ? 1 : 0)) * px) : nullptr;
+        std::vector<const uint8_t*> seg0_ptr, seg1_ptr;                   // --live-masks: the label images per frame, inside the arena
+        uint32_t* key_arena = (arena.p && want_keys && !live) ? reinterpret_cast<uint32_t*>(arena.p + (size_t)n * (2 + (want_masks ? 1 : 0)) * px) : nullptr;
         dv_seq_input in{};
         in.left = lp.data(); in.right = rp.data(); in.times = times.data(); in.n_frames = n; in.mem = mem; in.stride = 0; in.ba_stride = cfg.every_frame ? 1 : 2;
         in.imu_t = imu_t.data(); in.imu_acc = imu_a.data(); in.imu_gyr = imu_g.data(); in.n_imu = (int)imu_t.size();
@@ -272,7 +281,14 @@ int main(int argc, char** argv) {
             const std::vector<uint32_t>& keys = cfg.viode_dynamic_keys; const int nk = (int)keys.size();
             inv_mask.resize(n); right_keys.resize(n); dets.resize(n); det_masks.resize(n); mask_ptr.resize(n); keys_ptr.resize(n); det_ptr.resize(n); n_dets.assign(n, 0);
             std::vector<uint8_t> merge((size_t)W * H); std::vector<uint32_t> kimg((size_t)W * H); std::vector<int32_t> boxes(4 * (size_t)nk);
-            for (int k = 0; k < n; ++k) {
+            for (int k = 0; k < n && live; ++k) {          // T1's stage runs per frame inside the loop: only the label images are kept
+                const Gray a = read_image(s0[k], true), b = read_image(s1[k], true);
+                if (a.w != W || a.h != H || b.w != W || b.h != H) throw std::runtime_error("dvins_node: " + (a.w != W || a.h != H ? s0[k] : s1[k]) + " is not image_width x image_height of the config");
+                uint8_t* d0 = arena.p + (size_t)n * 2 * px + (size_t)k * 6 * px;
+                std::memcpy(d0, a.bgr.data(), 3 * px); std::memcpy(d0 + 3 * px, b.bgr.data(), 3 * px);
+                seg0_ptr.push_back(d0); seg1_ptr.push_back(d0 + 3 * px);
+            }
+            for (int k = 0; k < n && !live; ++k) {
                 const Gray seg = read_image(s0[k], true);
                 if (seg.w != W || seg.h != H) throw std::runtime_error("dvins_node: " + s0[k] + " is not image_width x image_height of the config");
                 uint8_t* inv_k = mask_arena ? mask_arena + (size_t)k * px : (inv_mask[k].resize(px), inv_mask[k].data());
@@ -307,8 +323,13 @@ int main(int argc, char** argv) {
 
         dv_runner* runner = dv_runner_create(&ctx, &in, 1, 0, 1);
         if (!runner) throw std::runtime_error(std::string("dvins_node: ") + dv_last_error(nullptr));
-        dv_seq_dynamic dyn{};
-        if (run_dynamic) {
+        dv_seq_dynamic dyn{}; dv_seq_viode vio{};
+        if (live) {
+            vio.seg0 = seg0_ptr.data(); vio.seg1 = seg1_ptr.data(); vio.mem = mem; vio.stride = 0;
+            vio.dyn_keys = cfg.viode_dynamic_keys.data(); vio.nkeys = (int)cfg.viode_dynamic_keys.size(); vio.min_inst_size = kMinInstSize;
+            vio.static_as_background = cfg.static_inst_as_background ? 1 : 0; vio.disp = nullptr; vio.baseline = cfg.baseline;
+            if (dv_runner_set_viode(runner, 0, &vio)) throw std::runtime_error(std::string("dvins_node: ") + dv_runner_error(runner));
+        } else if (run_dynamic) {
             dyn.inv_mask = mask_ptr.data(); dyn.mask_mem = mem; dyn.mode = DV_MODE_SEMANTIC;
             dyn.dets = det_ptr.data(); dyn.n_dets = n_dets.data(); dyn.boxes3d = nullptr; dyn.n_boxes3d = nullptr; dyn.disp = nullptr; dyn.baseline = cfg.baseline;
             dyn.right_keys = keys_ptr.data(); dyn.right_keys_mem = mem;

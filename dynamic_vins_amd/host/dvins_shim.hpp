@@ -587,6 +587,27 @@ public:
     void UnmaskStaticInstances(const std::vector<dv_inst_det>& dets, const std::vector<uint32_t>& static_ids) {
         detail::check(ctx_, dv_track_unmask_static(ctx_, dets.empty() ? nullptr : dets.data(), (int)dets.size(), static_ids.empty() ? nullptr : static_ids.data(), (int)static_ids.size()), "UnmaskStaticInstances");
     }
+    // the key-image forms (label images instead of masks: VIODE::SetViodeMaskAndRoi's ROI masks, utils/dataset/viode_utils.cpp:177-218, cut on the device): the mask of a
+    // detection is key_image == track_id over its rectangle, dv_inst_det::mask / points are ignored.  key_image: dv_viode_mask's, or dv_viode_frame_collect's device pointer
+    void UnmaskStaticInstances(const std::vector<dv_inst_det>& dets, const std::vector<uint32_t>& static_ids, const uint32_t* key_image, int stride_bytes = 0, int mem = DV_MEM_HOST) {
+        detail::check(ctx_, dv_track_unmask_static_keys(ctx_, dets.empty() ? nullptr : dets.data(), (int)dets.size(), static_ids.empty() ? nullptr : static_ids.data(), (int)static_ids.size(), key_image, stride_bytes, mem), "UnmaskStaticInstances");
+    }
+    void InstsTrack(double time, const std::vector<dv_inst_det>& dets, const uint32_t* key_image, int stride_bytes = 0, int mem = DV_MEM_HOST, const std::vector<dv_box3d>& boxes3d = {}) {
+        detail::check(ctx_, dv_inst_track_enqueue_keys(ctx_, time, dets.empty() ? nullptr : dets.data(), (int)dets.size(), key_image, stride_bytes, mem, boxes3d.empty() ? nullptr : boxes3d.data(), (int)boxes3d.size()), "InstsTrack");
+        pending_ = true;
+    }
+    // thread T1's stage of one frame (ImageProcessor::Run, image_process/image_process.cpp:161-178) on the device: label images in; detections and the DEVICE pointers of
+    // the inverse merged mask and the two key images out (dv_viode_frame_enqueue / _collect) — for TrackSemanticImage, the overloads above and SetRightKeys(keys1, 0, true)
+    struct ViodeFrame { std::vector<dv_inst_det> dets; const uint8_t* inv_mask = nullptr; const uint32_t* keys0 = nullptr; const uint32_t* keys1 = nullptr; };
+    void ViodeFrameEnqueue(const uint8_t* seg0_bgr, const uint8_t* seg1_bgr, int w, int h, int stride, const std::vector<uint32_t>& dyn_keys, int mem = DV_MEM_HOST) {
+        detail::check(ctx_, dv_viode_frame_enqueue(ctx_, seg0_bgr, seg1_bgr, w, h, stride, mem, dyn_keys.data(), (int)dyn_keys.size()), "ViodeFrameEnqueue");
+    }
+    ViodeFrame ViodeFrameCollect(int min_inst_size = 8) {
+        ViodeFrame f; f.dets.resize(64); int n = 0;
+        detail::check(ctx_, dv_viode_frame_collect(ctx_, min_inst_size, f.dets.data(), 64, &n, &f.inv_mask, &f.keys0, &f.keys1), "ViodeFrameCollect");
+        f.dets.resize(n);
+        return f;
+    }
     void InstsTrack(double time, const std::vector<dv_inst_det>& dets, const std::vector<dv_box3d>& boxes3d = {}) {
         detail::check(ctx_, dv_inst_track_enqueue(ctx_, time, dets.empty() ? nullptr : dets.data(), (int)dets.size(), boxes3d.empty() ? nullptr : boxes3d.data(), (int)boxes3d.size()), "InstsTrack");
         pending_ = true;

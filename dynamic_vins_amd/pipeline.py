@@ -215,8 +215,11 @@ class DynamicPipeline(Pipeline):
 
     def __init__(self, seq: DynamicSequence, max_cnt=250, min_dist=25, max_iters=10, device=0, use_imu=1, max_dynamic_cnt=50, min_dynamic_dist=5, use_det3d=1,
                  static_inst_threshold=1.0, mask_morphology_size=0, segments=None, est_kw=None, extra_from_disparity=True, ba_stride=1,
-                 static_as_background=False):
+                 static_as_background=False, live_masks=False):
         from .frontend import DV_MODE_SEMANTIC
+        # live_masks: `seq` carries label images (a viode.ViodeSequence: seg0, seg1, dyn_keys) and thread T1's stage runs per frame on the device (viode_frame_enqueue /
+        # _collect + the key-image entries) instead of reading the sequence's pre-computed masks, detections and key images; same results, bit for bit
+        self.live_masks, self._live_enq = bool(live_masks), None
         self.extra_from_disparity = extra_from_disparity      # False: the detections' own `points` are handed through (the caller ran the extra-point pipeline)
         self.seq, self.host = seq, None
         c = make_cam(*sim.cam_tuple(seq.cam))
@@ -245,7 +248,30 @@ class DynamicPipeline(Pipeline):
         best = [s for s in self.static_snaps if s[0] <= k - DV_STATIC_REPORT_LAG]
         return best[-1][1] if best else np.zeros(0, np.uint32)
 
+    def _enqueue_live(self, k):
+        from . import viode
+        s, ctx = self.seq, self.ctx
+        l, r = s.frames[k]
+        if self._live_enq != k:
+            ctx.viode_frame_enqueue(s.seg0[k], s.seg1[k], s.dyn_keys)
+        self._live_enq = None
+        dets, inv, k0, k1 = ctx.viode_frame_collect(viode.MIN_INST_SIZE)
+        if self.static_as_background and len(dets):
+            ctx.track_unmask_static_keys(dets, self.static_ids_for(k), k0, DV_MEM_DEVICE)
+        ctx.track_stereo_enqueue(l.data_ptr(), r.data_ptr(), s.times[k], inv, self.mode, DV_MEM_DEVICE)
+        if self.extra_from_disparity and len(getattr(s, "disp_dev", [])):
+            ctx.inst_set_disparity(s.disp_dev[k].data_ptr(), s.baseline, DV_MEM_DEVICE)
+        if k1:
+            ctx.inst_set_right_keys(k1, DV_MEM_DEVICE)
+        ctx.inst_track_enqueue_keys(s.times[k], dets, k0, DV_MEM_DEVICE)
+        self.enqueued = True
+        if k + 1 < len(s.frames):          # T1's stage of the next frame behind this frame's tracking: its boxes are there when the host turns to it
+            ctx.viode_frame_enqueue(s.seg0[k + 1], s.seg1[k + 1], s.dyn_keys)
+            self._live_enq = k + 1
+
     def _enqueue(self, k):
+        if self.live_masks:
+            return self._enqueue_live(k)
         l, r = self.seq.frames[k]
         if self.static_as_background and len(self.seq.dets[k]):
             self.ctx.track_unmask_static(self.seq.dets[k], self.static_ids_for(k))

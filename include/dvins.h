@@ -100,6 +100,13 @@ struct dv_inst_det;
  * For the NEXT dv_track_stereo_enqueue (which must carry a mask): dets = the frame's detections (rect + ROI mask, host memory, valid until that call), static_ids =
  * the estimator's list.  Detections whose track_id is not in the list are left alone; n_static 0 cancels.  The caller's mask is not written to. */
 int dv_track_unmask_static(dv_ctx* ctx, const struct dv_inst_det* dets, int n_dets, const uint32_t* static_ids, int n_static);
+/* The same step of FeatureTrack (system/main.cpp:217-245) from the frame's KEY IMAGE instead of host ROI masks: the ROI mask of detection d is, by definition,
+ * key_image[y + d.y][x + d.x] == d.track_id over its rectangle (what VIODE::SetViodeMaskAndRoi cuts, utils/dataset/viode_utils.cpp:177-218), compared on the device;
+ * dv_inst_det::mask is ignored.  key_image: w x h uint32 (dv_viode_mask's / dv_viode_frame_collect's), rows of stride_bytes (0 = 4 w), mem = DV_MEM_HOST (staged once by
+ * the enqueue; valid until that call returns), DV_MEM_DEVICE or DV_MEM_PINNED (read in place; valid until the frame is collected).  Every rectangle is checked against the
+ * image before a job is staged.  Applies to the NEXT dv_track_stereo_enqueue, as dv_track_unmask_static does, and EVERY return of that call, 0 or -1, drops the staged
+ * jobs (so does dv_batch_track_enqueue for the members handed in: such a member keeps its own launches in that round). */
+int dv_track_unmask_static_keys(dv_ctx* ctx, const struct dv_inst_det* dets, int n_dets, const uint32_t* static_ids, int n_static, const uint32_t* key_image, int stride_bytes, int mem);
 
 /* ---- front end: operator-level entries ---- */
 /* cv::calcOpticalFlowPyrLK(img_a,img_b,pts_a,pts_b,status,err,Size(21,21),max_level,
@@ -145,6 +152,22 @@ int dv_pyr_down(dv_ctx* ctx, const uint8_t* src, int w, int h, int stride, uint8
  * each key's pixels, -1 if absent (InstanceSimple).  Host buffers, tightly packed outputs. */
 int dv_viode_mask(dv_ctx* ctx, const uint8_t* seg_bgr, int w, int h, int stride, const uint32_t* dyn_keys, int nkeys,
                   uint8_t* merge_mask, uint8_t* inv_merge_mask, uint32_t* key_image, int32_t* boxes);
+/* Thread T1's stage of ONE frame of a VIODE-style stream (label image in, instances out) without a host round trip of pixels: ImageProcessor::Run
+ * (image_process/image_process.cpp:161-178) -> VIODE::SetViodeMaskAndRoi (utils/dataset/viode_utils.cpp:21-218), as FeatureTrack consumes it (system/main.cpp:196-250).
+ * _enqueue runs dv_viode_mask's kernel on the LEFT label image and, if given, on the RIGHT one (whose key image TrackRightByPad tests, front_end/instance_feature.cpp:263-268)
+ * on the ctx's stream, into device buffers the LIBRARY owns, and records an event.  seg*_bgr: 8-bit B G R, size of the config, rows of `stride` bytes (0 = 3 w), mem =
+ * DV_MEM_HOST (staged; valid until the frame is collected), DV_MEM_DEVICE or DV_MEM_PINNED (read in place).  dyn_keys[nkeys], 1 <= nkeys <= 64, host memory.
+ * _collect waits for that event and builds the frame's detections by the rule dvins_node and dynamic_vins_amd/viode.py detections() share: one per key present, ASCENDING
+ * key, rect = cv::Rect(min_pt, max_pt) (max row / column excluded), rectangles under min_inst_size pixels on a side dropped, track_id = key, class 0, mask = points = NULL.
+ * It hands back the device pointers of that frame's inverse merged mask (w x h bytes, tightly packed: give it to dv_track_stereo_enqueue with DV_MEM_DEVICE beside frames
+ * of row stride w) and of its two key images (w x h uint32, tightly packed; keys1 NULL without a right image): for dv_inst_track_enqueue_keys,
+ * dv_track_unmask_static_keys and dv_inst_set_right_keys.  The buffers exist twice and alternate: those of frame k stay intact while frame k + 1 is enqueued and until
+ * frame k + 2 is; the caller never frees them.  One frame may be in flight: _enqueue twice without _collect is refused.
+ * The ONLY device -> host traffic per frame is nkeys x 16 bytes of boxes (into pinned memory): the host needs them because the object tracker's job tables are sized
+ * from the rectangles.  dv_viode_mask itself is unchanged. */
+struct dv_inst_det;
+int dv_viode_frame_enqueue(dv_ctx* ctx, const uint8_t* seg0_bgr, const uint8_t* seg1_bgr_or_null, int w, int h, int stride, int mem, const uint32_t* dyn_keys, int nkeys);
+int dv_viode_frame_collect(dv_ctx* ctx, int min_inst_size, struct dv_inst_det* dets, int cap, int* n_dets, const uint8_t** inv_mask_dev, const uint32_t** keys0_dev, const uint32_t** keys1_dev);
 /* cv::cvtColor(BGR2GRAY) on 8-bit images: (B 1868 + G 9617 + R 4899 + 8192) >> 14; gray is w x h, tightly packed */
 int dv_bgr2gray(dv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, uint8_t* gray, int mem);
 /* cv::remap(src, dst, map1, map2, INTER_LINEAR) — BORDER_CONSTANT 0 — with the fixed-point maps cv::initUndistortRectifyMap(..., CV_16SC2, ...)
@@ -616,6 +639,24 @@ int dv_runner_set_mask(dv_runner* runner, int seq, const uint8_t* const* inv_mas
  * tracking(k+1), dv_est_process_dynamic_attach(k), then ONE dv_batch_enqueue for the group, then collect tracking(k+1).  Every member's results are bit-identical to
  * its own run with group_size 0 and "tracker_thread" 0. */
 int dv_runner_set_dynamic(dv_runner* runner, int seq, const dv_seq_dynamic* dyn);
+/* Dynamic mode of a sequence fed with LABEL IMAGES, one frame at a time: thread T1's stage (ImageProcessor::Run, image_process/image_process.cpp:161-178;
+ * VIODE::SetViodeMaskAndRoi, utils/dataset/viode_utils.cpp:21-218) runs per frame inside the loop (dv_viode_frame_enqueue / _collect) instead of as a pre-pass whose
+ * masks, detections and key images dv_seq_dynamic carries.  The sequence then runs the dynamic loop of dv_runner_set_dynamic — one-thread order or T2 beside T3
+ * ("tracker_thread") — with the key-image entries: dv_track_unmask_static_keys (the static report with the same lag rule, DV_STATIC_REPORT_LAG, choice T1),
+ * dv_track_stereo_enqueue with the device-resident inverse mask, dv_inst_set_right_keys, dv_inst_track_enqueue_keys (FeatureTrack, system/main.cpp:196-250).  The stage of
+ * frame k + 1 is enqueued right behind the tracking of frame k, so its boxes have arrived when the host turns to frame k + 1.  Results are bit-identical to
+ * dv_runner_set_dynamic fed the pre-computed masks, detections (ROI masks cut from the key image) and right key images of the same label images.
+ * Before the first dv_runner_run; the frames must be DV_MEM_DEVICE or DV_MEM_PINNED with row stride = width (the inverse mask stays on the device and travels with them).
+ * Refused with "dv_runner_set_viode: a sequence of a dv_batch group is not supported ..." for a member of a group (group_size > 1: the group's shared unmask launch reads
+ * host masks); the runner stays usable. */
+typedef struct dv_seq_viode {
+    const uint8_t* const* seg0; const uint8_t* const* seg1;      /* [n_frames] label images of the left / right camera (B G R); seg1 may be NULL (no key test in the right image) */
+    int32_t mem /* DV_MEM_* of the label images */, stride /* bytes per row, 0 = 3 * width */;
+    const uint32_t* dyn_keys; int32_t nkeys /* 1..64 */, min_inst_size /* rectangles below it are not handed to the object tracker (dvins_node: 8) */;
+    int32_t static_as_background, reserved;      /* as dv_seq_dynamic::static_as_background */
+    const float* const* disp; int32_t disp_mem, disp_stride; double baseline;      /* as in dv_seq_dynamic; disp may be NULL */
+} dv_seq_viode;
+int dv_runner_set_viode(dv_runner* runner, int seq, const dv_seq_viode* viode);
 /* what the object branch of a dynamic sequence was fed so far: detections, object feature rows, frames with at least one object, fewest detections in a frame */
 int dv_runner_dynamic_stats(dv_runner* runner, int seq, long long* detections, long long* object_features, long long* frames_with_objects, int* min_detections);
 dv_runner* dv_runner_create(dv_ctx* const* ctxs, const dv_seq_input* seqs, int n_seq, int group_size, int threads);      /* group_size <= 1: no batching */
@@ -690,6 +731,13 @@ int dv_inst_reset(dv_ctx* ctx);
  * of the frame last passed to dv_track_stereo_enqueue (call it right after, same frame; `t` = that frame's time).  boxes3d = SemanticImage::boxes3d
  * (only read when use_det3d). */
 int dv_inst_track_enqueue(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_dets, const dv_box3d* boxes3d, int n_boxes3d);
+/* The same call with the objects' masks cut ON THE DEVICE from the frame's key image (VIODE::SetViodeMaskAndRoi's ROI masks, utils/dataset/viode_utils.cpp:177-218;
+ * AddViodeInstances, front_end/dynamic_tracker.cpp:585-605): the mask of detection d is key_image[y + d.y][x + d.x] == d.track_id ? 255 : 0 over its rectangle;
+ * dv_inst_det::mask and dv_inst_det::points are ignored.  key_image: w x h uint32, rows of stride_bytes (0 = 4 w), mem = DV_MEM_HOST (staged once per frame, as
+ * dv_inst_set_right_keys stages; valid until the frame is collected), DV_MEM_DEVICE or DV_MEM_PINNED (read in place).  One launch for all visible objects writes their
+ * masks where dv_inst_track_enqueue uploads them (padding bytes zero); everything behind — ROI crop, erosion, corner detection, LK, extra-point sampling — runs unchanged
+ * on those bytes, so the rows equal those of dv_inst_track_enqueue given the masks cut on the host. */
+int dv_inst_track_enqueue_keys(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_dets, const uint32_t* key_image, int stride_bytes, int mem, const dv_box3d* boxes3d, int n_boxes3d);
 /* SemanticImage::disp (CV_32F disparity of the left image, basic/semantic_image.h:30-65) of the frame about to be handed to dv_inst_track_enqueue.  With it the library
  * runs the reference's extra-point pipeline for every visible object ON THE DEVICE, one launch for all objects on a side stream (the reference: a second thread):
  * InstFeat::DetectExtraPoints (front_end/instance_feature.cpp:413-461: step = max(sqrt(0.8 rows cols / 1000), 2), mask > 0, disparity > 0 and not NaN,
