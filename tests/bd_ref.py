@@ -2,7 +2,7 @@
 dv_line_solve) and the oracle's solver loop (dvo_obj_solve, dvo_line_solve) are held to by tests/test_bd_reference.py and tests/test_bd_reference_gpu.py.
 
 A problem is a list of residual blocks, each on ONE variable block.  Residuals and Jacobians come from the oracle's per-factor entries (G.o_box_enclose,
-G.o_box_dims, G.o_box_orientation, G.o_line: the ones tests/test_obj_factors.py pins, documented non-derivative Jacobians included); everything after that is
+G.o_box_dims, G.o_box_orientation, G.o_line: the ones tests/test_objfactor_reference*.py pin against a float64 restatement, documented non-derivative Jacobians included); everything after that is
 written here from the Ceres 1.14 rule set (trust_region_minimizer.cc, dogleg_strategy.cc, corrector.cc), not from the kernel's or the oracle's
 loop, and with other arithmetic: no normal equations.  With J the stacked Jacobian on the local parameters (6 per object pose, 3 per object dims, 4 per line; a block
 without a residual is dropped, as Ceres drops it), S = 1 / (1 + |J column|) fixed at iteration 0 and D = sqrt(clip(diag((J S)^T (J S)), 1e-6, 1e32)):

@@ -9,7 +9,8 @@ Quaternions are stored x y z w as in the parameter blocks (para_pose: p, qx qy q
 
 Every closed form is evaluated on `A` values: a float64 array that carries, beside its value, the SAME expression evaluated on absolute values (sums of
 magnitudes for sums and differences, products of magnitudes for products): the size of the rounding a float64 evaluation of that expression can carry, entry
-by entry, and exactly 0 where the expression is structurally zero.  The tests hold |device - reference| <= K eps magnitude.
+by entry, and exactly 0 where the expression is structurally zero.  The tests hold |device - reference| <= K eps magnitude.  The elementary functions (sin, cos,
+asin, atan, atan2, sqrt: tests/objfactor_ref.py) carry |f(x)| + |f'(x)| m_x.
 
 Three closed forms of the IMU factor are not the derivative of the residual once the gyroscope bias has moved from its linearisation point
 (theta = dq_dbg (Bg_i - lin_bg) != 0), all in the rotation rows:
@@ -19,6 +20,8 @@ Three closed forms of the IMU factor are not the derivative of the residual once
                      |cq|^2 times the derivative: exact at theta = 0, second-order gap beyond, and EXACTLY that factor (asserted);
 and one of the projection factors: Q7, kind 2 writes d r / d lambda with pts_i instead of pts_i_td (projection_one_frame_two_cam_factor.cpp:125).
 The closed forms are what the device must match; tests/test_factor_reference.py pins down where and by how much they leave the derivative."""
+import contextlib
+
 import numpy as np
 
 EPS = np.finfo(np.float64).eps
@@ -28,6 +31,7 @@ SQRT_INFO = 460.0 / 1.5          # kFocalLength / 1.5 * I2 (estimator.cpp:685-68
 # ---------------------------------------------------------------- values that carry the magnitude of their own expression
 class A:
     __slots__ = ("v", "m")
+    first_order = False          # see first_order() below; off, the products are products of magnitudes
 
     def __init__(self, v, m=None):
         self.v = np.asarray(v, np.float64)
@@ -55,6 +59,8 @@ class A:
 
     def __mul__(self, o):
         o = A.of(o)
+        if A.first_order:
+            return A(self.v * o.v, np.abs(self.v) * o.m + self.m * np.abs(o.v))
         return A(self.v * o.v, self.m * o.m)
 
     __rmul__ = __mul__
@@ -70,6 +76,8 @@ class A:
 
     def __matmul__(self, o):
         o = A.of(o)
+        if A.first_order:
+            return A(self.v @ o.v, np.abs(self.v) @ o.m + self.m @ np.abs(o.v))
         return A(self.v @ o.v, self.m @ o.m)
 
     def __rmatmul__(self, o):
@@ -81,6 +89,18 @@ class A:
     @property
     def T(self):
         return A(self.v.T, self.m.T)
+
+
+@contextlib.contextmanager
+def first_order():
+    """Inside, a product carries |a| m_b + m_a |b| instead of m_a m_b (each m holds its own |value|, so the product's own rounding is in it).  The product of
+    magnitudes is the expression on absolute values only while the operands are polynomials of the inputs; past a quotient or a function call the magnitudes are
+    error bounds, and multiplying two of them squares their slack at every step (1e12 eps on a benign line Jacobian, 1e130 at the end of the orientation chain)."""
+    old, A.first_order = A.first_order, True
+    try:
+        yield
+    finally:
+        A.first_order = old
 
 
 def stack(rows):
@@ -101,6 +121,42 @@ def zeros(*shape):
 
 def eye3():
     return A(np.eye(3))
+
+
+# elementary functions on A: the magnitude of f(x) is |f(x)| + |f'(x)| m_x (the function's own rounding plus what the rounding of its argument becomes)
+def _elem(x, f, df):
+    x = A.of(x)
+    v = f(x.v)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return A(v, np.abs(v) + np.where(x.m > 0, np.abs(df(x.v)) * x.m, 0.0))
+
+
+def sin(x):
+    return _elem(x, np.sin, np.cos)
+
+
+def cos(x):
+    return _elem(x, np.cos, np.sin)
+
+
+def asin(x):
+    return _elem(x, np.arcsin, lambda v: 1.0 / np.sqrt(1.0 - v * v))
+
+
+def atan(x):
+    return _elem(x, np.arctan, lambda v: 1.0 / (1.0 + v * v))
+
+
+def sqrt(x):
+    return _elem(x, np.sqrt, lambda v: 0.5 / np.sqrt(v))
+
+
+def atan2(y, x):
+    y, x = A.of(y), A.of(x)
+    v = np.arctan2(y.v, x.v)
+    n2 = x.v * x.v + y.v * y.v
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return A(v, np.abs(v) + np.where((x.m > 0) | (y.m > 0), (np.abs(x.v) * y.m + np.abs(y.v) * x.m) / n2, 0.0))
 
 
 def skew(v):
