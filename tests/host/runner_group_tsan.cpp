@@ -4,7 +4,7 @@
 // attach(k) | ONE dv_batch_enqueue | collect tracking(k+1) — between the team's barriers, beside raw members whose tracking thread 0 enqueues in shared launches.
 // The stub's outputs are functions of what every call was handed, so every layout must leave, per sequence, the logs of that sequence's own one-thread loop
 // (group_size 0, tracker_thread 0); TSan reports what the bit-identity checks of tests/test_runner_dynamic_group.py cannot see.
-//   runner_group_tsan layouts | fail        exit 0 = logs identical / failure reported without a hang; TSan's own exit code (66) on a report
+//   runner_group_tsan layouts | fail [--calls | --calls-full]       (--calls: per run, context and domain the digest of the stub's call trace)        exit 0 = logs identical / failure reported without a hang; TSan's own exit code (66) on a report
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +17,8 @@
 extern "C" dv_ctx* dvstub_ctx(int w, int h, int dynamic);
 extern "C" long long dvstub_violations();
 extern "C" void dvstub_new_run();
+extern "C" void dvstub_trace(int level);
+extern "C" void dvstub_trace_report(const char* label);
 
 namespace {
 struct Seq {
@@ -35,14 +37,16 @@ void make_seq(Seq& q, int frames, int id) {
 }
 struct Log { std::vector<double> frames; std::vector<unsigned long long> rows; long long iterations = 0; };
 // the mix of a group of four: member 3 of every four is a raw sequence, member 1 feeds its static report back into its tracking, member 2 sends every 2nd frame to the back end
+// (mix 1: member 2 feeds its static report back too — every 2nd frame to the back end AND the snapshot lookup)
 bool is_dynamic(int i) { return i % 4 != 3; }
-int run_layout(int n, int frames, int group, int threads, int teams, int batch_front, int tracker_thread, const std::vector<int>& cuts, std::vector<Log>& out, bool expect_fail = false) {
+std::string g_label;          // the call trace's name of the next run
+int run_layout(int n, int frames, int group, int threads, int teams, int batch_front, int tracker_thread, const std::vector<int>& cuts, std::vector<Log>& out, bool expect_fail = false, int mix = 0) {
     std::vector<Seq> seqs(n); std::vector<dv_ctx*> ctxs; std::vector<dv_seq_input> in;
     dvstub_new_run();
     for (int i = 0; i < n; ++i) {
         make_seq(seqs[i], frames, i);
         if (i % 4 == 1) seqs[i].dyn.static_as_background = 1;
-        if (i % 4 == 2) seqs[i].in.ba_stride = 2;
+        if (i % 4 == 2) { seqs[i].in.ba_stride = 2; if (mix == 1) seqs[i].dyn.static_as_background = 1; }
         ctxs.push_back(dvstub_ctx(64, 48, is_dynamic(i))); in.push_back(seqs[i].in);
     }
     dv_runner* R = dv_runner_create(ctxs.data(), in.data(), n, group, threads);
@@ -62,6 +66,7 @@ int run_layout(int n, int frames, int group, int threads, int teams, int batch_f
     dv_batch* b[8]; int nb = 0;
     if (dv_runner_get_batches(R, b, 8, &nb) || nb != (group > 1 ? (n + group - 1) / group : 0)) { std::fprintf(stderr, "dv_runner_get_batches: %d groups\n", nb); dv_runner_destroy(R); return 2; }
     dv_runner_destroy(R);
+    dvstub_trace_report(g_label.c_str());
     return 0;
 }
 bool same(const std::vector<Log>& a, const std::vector<Log>& b) {
@@ -76,19 +81,27 @@ int main(int argc, char** argv) {
     std::thread watchdog([] { std::this_thread::sleep_for(std::chrono::seconds(240)); std::fprintf(stderr, "runner_group_tsan: HANG (watchdog)\n"); std::_Exit(9); });
     watchdog.detach();
     int bad = 0;
+    for (int a = 1; a < argc; ++a) { if (!std::strcmp(argv[a], "--calls")) dvstub_trace(1); else if (!std::strcmp(argv[a], "--calls-full")) dvstub_trace(2); }          // the stub's call trace: digests / records per run (not for `fail`)
     if (mode == "layouts") {
         const int n = 8, frames = 36;
         std::vector<Log> ref, got;
+        g_label = "group reference";
         if (run_layout(n, frames, 0, 1, 0, 1, 0, { frames }, ref)) return 2;                                  // every sequence's own one-thread loop: the reference
         struct L { int group, threads, teams, batch_front, tracker; std::vector<int> cuts; const char* name; };
         const L layouts[] = { { 4, 1, 0, 1, 1, { frames }, "two groups on one thread" }, { 4, 2, 0, 1, 1, { frames }, "one thread per group" }, { 4, 2, 0, 0, 0, { 20, 16 }, "one thread per group, own tracking launches, two calls" },
                               { 4, 4, 1, 1, 1, { frames }, "teams of two" }, { 4, 8, 1, 1, 0, { 7, 1, 13, 15 }, "teams of four, four calls" }, { 8, 4, 1, 1, 1, { 1, 1, 1, 33 }, "one group, team of four, one-frame calls" },
                               { 3, 3, 0, 1, 1, { frames }, "groups of three (the last one of two)" } };
-        for (const L& l : layouts) {
-            if (run_layout(n, frames, l.group, l.threads, l.teams, l.batch_front, l.tracker, l.cuts, got)) return 2;
-            const bool ok = same(ref, got);
-            if (!ok) bad++, std::fprintf(stderr, "MISMATCH: %s\n", l.name);
-            std::printf("layout '%s': %s\n", l.name, ok ? "same logs" : "DIFFERENT");
+        for (int mix = 0; mix <= 1; ++mix) {
+            const std::string tag = mix ? "ba_stride 2 with static feedback: " : "";
+            if (mix) { g_label = tag + "reference"; if (run_layout(n, frames, 0, 1, 0, 1, 0, { frames }, ref, false, mix)) return 2; }
+            for (const L& l : layouts) {
+                if (mix && l.group == 3) continue;
+                g_label = tag + l.name;
+                if (run_layout(n, frames, l.group, l.threads, l.teams, l.batch_front, l.tracker, l.cuts, got, false, mix)) return 2;
+                const bool ok = same(ref, got);
+                if (!ok) bad++, std::fprintf(stderr, "MISMATCH: %s%s\n", tag.c_str(), l.name);
+                std::printf("%slayout '%s': %s\n", tag.c_str(), l.name, ok ? "same logs" : "DIFFERENT");
+            }
         }
     } else if (mode == "fail") {          // DVSTUB_FAIL=<ctx>:<frame> names a DYNAMIC member: the run must return an error, not hang, in every layout
         std::vector<Log> got;

@@ -1,7 +1,7 @@
 // runner_viode_host.cpp — stand-alone host program for the label-image path (dv_runner_set_viode): the detection-building rule (csrc/viode_host.h) and the runner's
 // scheduling of thread T1's per-frame stage (csrc/runner.hip compiled as plain C++) on the stand-in C ABI (stub_abi.cpp + stub_viode.cpp).  Built twice by viode.mk:
 // AddressSanitizer + UBSan, and ThreadSanitizer.  No GPU, no HIP runtime.
-//   runner_viode_host        exit 0 = the rule holds, every layout leaves the one-thread logs, a grouped sequence is refused and the runner goes on
+//   runner_viode_host [--calls | --calls-full]       (--calls: per run, context and domain the digest of the stub's call trace)        exit 0 = the rule holds, every layout leaves the one-thread logs, a grouped sequence is refused and the runner goes on
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +16,8 @@ extern "C" dv_ctx* dvstub_ctx(int w, int h, int dynamic);
 extern "C" long long dvstub_violations();
 extern "C" long long dvstub_viode_violations();
 extern "C" void dvstub_new_run();
+extern "C" void dvstub_trace(int level);
+extern "C" void dvstub_trace_report(const char* label);
 
 namespace {
 int g_bad = 0;
@@ -56,6 +58,7 @@ void make_seq(Seq& q, int frames, int id, int static_bg, int ba_stride, bool rig
     q.vio.static_as_background = static_bg;
 }
 struct Log { std::vector<double> frames; std::vector<unsigned long long> rows; long long iterations = 0, dets = 0; };
+std::string g_label;          // the call trace's name of the next run
 int run_layout(int n, int frames, int threads, int tracker_thread, const std::vector<int>& cuts, int static_bg, int ba_stride, std::vector<Log>& out) {
     std::vector<Seq> seqs(n); std::vector<dv_ctx*> ctxs; std::vector<dv_seq_input> in;
     dvstub_new_run();
@@ -73,6 +76,7 @@ int run_layout(int n, int frames, int threads, int tracker_thread, const std::ve
         dv_runner_dynamic_stats(R, i, &out[i].dets, nullptr, nullptr, nullptr);
     }
     dv_runner_destroy(R);
+    dvstub_trace_report(g_label.c_str());
     return 0;
 }
 bool same(const std::vector<Log>& a, const std::vector<Log>& b) {
@@ -82,19 +86,23 @@ bool same(const std::vector<Log>& a, const std::vector<Log>& b) {
 }
 }
 
-int main() {
+int main(int argc, char** argv) {
     std::thread watchdog([] { std::this_thread::sleep_for(std::chrono::seconds(240)); std::fprintf(stderr, "runner_viode_host: HANG (watchdog)\n"); std::_Exit(9); });
     watchdog.detach();
     rule_checks();
+    for (int a = 1; a < argc; ++a) { if (!std::strcmp(argv[a], "--calls")) dvstub_trace(1); else if (!std::strcmp(argv[a], "--calls-full")) dvstub_trace(2); }          // the stub's call trace: digests / records per run (not for `fail`)
     const int n = 3, frames = 32;
     struct L { int threads, tracker; std::vector<int> cuts; const char* name; };
     const L layouts[] = { { 1, 1, { frames }, "T2 beside T3" }, { 3, 1, { frames }, "T2 beside T3, one estimator thread per sequence" }, { 1, 1, { 7, 1, 13, 11 }, "T2 beside T3, four calls" },
                           { 1, 0, { 5, 27 }, "one-thread loop, two calls" }, { 3, 0, { 11, 21 }, "one-thread loops on three threads" } };
     for (int static_bg = 0; static_bg <= 1; ++static_bg) for (int stride = 1; stride <= 2; ++stride) {
         std::vector<Log> ref, got;
+        const std::string tag = "static feedback " + std::to_string(static_bg) + ", ba_stride " + std::to_string(stride) + ": ";
+        g_label = tag + "reference";
         if (run_layout(n, frames, 1, 0, { frames }, static_bg, stride, ref)) return 2;          // the one-thread loop, uncut
         expect(!ref.empty() && ref[0].dets > 0, "the object branch was fed");
         for (const L& l : layouts) {
+            g_label = tag + l.name;
             if (run_layout(n, frames, l.threads, l.tracker, l.cuts, static_bg, stride, got)) return 2;
             const bool ok = same(ref, got);
             if (!ok) ++g_bad;
@@ -111,6 +119,7 @@ int main() {
             expect(dv_runner_set_viode(R, 0, &seqs[0].vio) == -1 && std::strstr(dv_runner_error(R), "dv_runner_set_viode: a sequence of a dv_batch group is not supported") != nullptr, "grouped sequence refused with the documented message");
             expect(dv_runner_run(R, 12, nullptr) == 0, "the runner stays usable");
             dv_runner_destroy(R);
+            dvstub_trace_report("refused label-image member: the group goes on raw");
         }
     }
     if (dvstub_violations() || dvstub_viode_violations()) { std::fprintf(stderr, "stub: %lld + %lld call-sequence violations\n", dvstub_violations(), dvstub_viode_violations()); ++g_bad; }

@@ -4,11 +4,13 @@
 // detections are built by the library's own rule (csrc/viode_host.h) from boxes that are a function of the frame.
 #include <cstdint>
 #include <mutex>
+#include <string>
 #include <unordered_map>
 #include "dv_ctx.h"
 #include "viode_host.h"
 
 extern "C" long long dvstub_violations();
+void dvstub_record(dv_ctx* c, int domain, const char* fmt, ...);          // stub_abi.cpp: the call trace (domain 0 = tracker)
 
 namespace {
 struct VStub { int scratch = 0; bool pending = false; int frame = 0, collected = 0; const uint8_t* seg0 = nullptr; const uint8_t* seg1 = nullptr; uint32_t keys[64]; int nkeys = 0; };
@@ -21,8 +23,10 @@ int violation(dv_ctx* c, const char* what) { dv_set_error(c, what); std::lock_gu
 
 extern "C" {
 long long dvstub_viode_violations() { std::lock_guard<std::mutex> lk(v_mu); return g_bad; }
-int dv_viode_frame_enqueue(dv_ctx* c, const uint8_t* seg0, const uint8_t* seg1, int w, int h, int, int mem, const uint32_t* keys, int nkeys) {
+int dv_viode_frame_enqueue(dv_ctx* c, const uint8_t* seg0, const uint8_t* seg1, int w, int h, int stride, int mem, const uint32_t* keys, int nkeys) {
     VStub& s = V(c); s.scratch++;
+    { std::string ks; for (int k = 0; keys && k < nkeys && k < 64; ++k) ks += (k ? " " : "") + std::to_string(keys[k]);
+      dvstub_record(c, 0, "dv_viode_frame_enqueue w=%d h=%d stride=%d mem=%d nkeys=%d keys=[%s] seg0=%d seg1=%d", w, h, stride, mem, nkeys, ks.c_str(), seg0 != nullptr, seg1 != nullptr); }
     if (!seg0 || !keys || nkeys < 1 || nkeys > 64 || w != c->cfg.width || h != c->cfg.height || mem < 0 || mem > 2) return violation(c, "dv_viode_frame_enqueue: bad argument");
     if (s.pending) return violation(c, "dv_viode_frame_enqueue: previous frame not collected");
     s.pending = true; s.seg0 = seg0; s.seg1 = seg1; s.nkeys = nkeys; for (int k = 0; k < nkeys; ++k) s.keys[k] = keys[k];
@@ -30,6 +34,7 @@ int dv_viode_frame_enqueue(dv_ctx* c, const uint8_t* seg0, const uint8_t* seg1, 
 }
 int dv_viode_frame_collect(dv_ctx* c, int min_inst_size, dv_inst_det* dets, int cap, int* n_dets, const uint8_t** inv, const uint32_t** k0, const uint32_t** k1) {
     VStub& s = V(c); s.scratch++;
+    dvstub_record(c, 0, "dv_viode_frame_collect min_inst_size=%d cap=%d dets=%d n_dets=%d inv=%d k0=%d k1=%d", min_inst_size, cap, dets != nullptr, n_dets != nullptr, inv != nullptr, k0 != nullptr, k1 != nullptr);
     if (!s.pending) return violation(c, "dv_viode_frame_collect: nothing enqueued");
     s.pending = false;
     int32_t boxes[256];
@@ -48,15 +53,18 @@ int dv_viode_frame_collect(dv_ctx* c, int min_inst_size, dv_inst_det* dets, int 
     return 0;
 }
 // the key forms land in the tracker domain's state machine of stub_abi.cpp through the entries it has: the ids / detections travel into the same hashes
-int dv_track_unmask_static_keys(dv_ctx* c, const dv_inst_det* dets, int n_dets, const uint32_t* ids, int n_static, const uint32_t* key_image, int, int mem) {
+int dv_track_unmask_static_keys(dv_ctx* c, const dv_inst_det* dets, int n_dets, const uint32_t* ids, int n_static, const uint32_t* key_image, int stride, int mem) {
     VStub& s = V(c); s.scratch++;
+    { std::string is; for (int i = 0; i < n_static; ++i) is += (i ? " " : "") + std::to_string(ids[i]);
+      dvstub_record(c, 0, "dv_track_unmask_static_keys n_dets=%d n_static=%d ids=[%s] stride=%d mem=%d dets=%d keys=%d", n_dets, n_static, is.c_str(), stride, mem, dets != nullptr, key_image != nullptr); }
     if (n_static > 0 && n_dets > 0 && (!key_image || mem < 0 || mem > 2)) return violation(c, "dv_track_unmask_static_keys: bad key image");
     std::vector<uint32_t> hit;
     for (int i = 0; i < n_static; ++i) for (int k = 0; k < n_dets; ++k) if (dets[k].track_id == ids[i]) hit.push_back(ids[i]);
     return dv_track_unmask_static(c, dets, n_dets, hit.data(), (int)hit.size());
 }
-int dv_inst_track_enqueue_keys(dv_ctx* c, double t, const dv_inst_det* dets, int n_dets, const uint32_t* key_image, int, int mem, const dv_box3d* b, int nb) {
+int dv_inst_track_enqueue_keys(dv_ctx* c, double t, const dv_inst_det* dets, int n_dets, const uint32_t* key_image, int stride, int mem, const dv_box3d* b, int nb) {
     VStub& s = V(c); s.scratch++;
+    dvstub_record(c, 0, "dv_inst_track_enqueue_keys t=%.17g n_dets=%d stride=%d mem=%d n_boxes=%d dets=%d keys=%d boxes=%d", t, n_dets, stride, mem, nb, dets != nullptr, key_image != nullptr, b != nullptr);
     if (!key_image || mem < 0 || mem > 2) return violation(c, "dv_inst_track_enqueue_keys: bad key image");
     for (int k = 0; k < n_dets; ++k) if (dets[k].mask || dets[k].w <= 0 || dets[k].h <= 0) return violation(c, "dv_inst_track_enqueue_keys: a detection of the frame stage carries a mask or an empty rectangle");
     return dv_inst_track_enqueue(c, t, dets, n_dets, b, nb);
