@@ -122,6 +122,10 @@ SIGNATURES = {
     "dv_track_unmask_static_keys": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "dv_viode_frame_enqueue": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "dv_viode_frame_collect": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "dv_inst_stack_frame_enqueue": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "dv_inst_stack_frame_collect": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "dv_inst_track_enqueue_planes": (C.c_int, [_ctx, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "dv_track_unmask_static_planes": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dv_inst_set_disparity": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_double]),
     "dv_inst_set_right_keys": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int]),
     "dv_pinned_alloc": (C.c_void_p, [C.c_size_t]),
@@ -157,6 +161,7 @@ SIGNATURES = {
     "dv_runner_batch_timing": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "dv_runner_set_dynamic": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "dv_runner_set_viode": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "dv_runner_set_inst_stack": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "dv_runner_set_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "dv_runner_dynamic_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "dv_runner_set": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),

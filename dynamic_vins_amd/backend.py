@@ -595,6 +595,12 @@ class dv_seq_viode(C.Structure):
                 ("static_as_background", C.c_int32), ("reserved", C.c_int32), ("disp", C.c_void_p), ("disp_mem", C.c_int32), ("disp_stride", C.c_int32), ("baseline", C.c_double)]
 
 
+class dv_seq_stack(C.Structure):
+    _fields_ = [("stack", C.c_void_p), ("n_planes", C.c_void_p), ("kind", C.c_int32), ("mem", C.c_int32), ("row_stride", C.c_int32), ("min_inst_size", C.c_int32),
+                ("plane_stride", C.c_int64), ("threshold", C.c_float), ("static_as_background", C.c_int32), ("track_id", C.c_void_p), ("class_id", C.c_void_p),
+                ("boxes3d", C.c_void_p), ("n_boxes3d", C.c_void_p), ("disp", C.c_void_p), ("disp_mem", C.c_int32), ("disp_stride", C.c_int32), ("baseline", C.c_double)]
+
+
 class Runner:
     """dv_runner: the per-frame host loop of pipeline.Pipeline in C++ inside the library, for one or many sequences (include/dvins.h).  `pipes` are Pipeline
     objects (each owns its Context + Estimator and a SyntheticSequence whose frames are resident in HBM); the runner takes over driving them."""
@@ -638,7 +644,12 @@ class Runner:
         if not self.h:
             raise DvinsError((self.lib.dv_last_error(None) or b"dv_runner_create failed").decode())
         for i, p in enumerate(pipes):
-            if getattr(p, "live_masks", False):     # a DynamicPipeline over a VIODE-style sequence, fed with its label images frame by frame
+            if getattr(p, "mask_stack", False):     # a DynamicPipeline fed with the detector's mask stacks frame by frame
+                st = p.stack_input()
+                self.set_inst_stack(i, st["stacks"][first_frame:], st["track_ids"][first_frame:], st["class_ids"][first_frame:], min_inst_size=st["min_inst_size"],
+                                    static_as_background=getattr(p, "static_as_background", False),
+                                    disp=p.seq.disp_dev[first_frame:] if getattr(p, "extra_from_disparity", False) and len(getattr(p.seq, "disp_dev", [])) else None, baseline=p.seq.baseline)
+            elif getattr(p, "live_masks", False):     # a DynamicPipeline over a VIODE-style sequence, fed with its label images frame by frame
                 self._set_viode(i, p, first_frame)
             elif getattr(p, "mode", 0) != 0:          # a DynamicPipeline: hand the per-frame perception outputs of its sequence to the runner's dynamic loop
                 self._set_dynamic(i, p, first_frame)
@@ -706,6 +717,37 @@ class Runner:
         v.disp, v.disp_mem, v.disp_stride, v.baseline = (C.cast(disps, C.c_void_p) if use_disp else None), DV_MEM_DEVICE, 0, float(q.baseline)
         self._keep += [seg0, seg1, p0, p1, keys, disps, v]
         if self.lib.dv_runner_set_viode(self.h, i, C.byref(v)) != 0:
+            raise DvinsError(self.lib.dv_runner_error(self.h).decode())
+
+    def set_inst_stack(self, i, stacks, track_ids, class_ids=None, min_inst_size=8, static_as_background=False, disp=None, baseline=0.0, threshold=0.0, boxes3d=None):
+        """dv_runner_set_inst_stack: sequence i runs the dynamic loop on the detector's mask stacks.  stacks: per frame a contiguous [n, h, w] torch tensor on the device
+        (uint8 / bool -> DV_STACK_U8, float32 -> DV_STACK_F32 with `threshold`); track_ids / class_ids: per frame one int per plane, the upstream tracker's answer
+        (-1 drops the plane); disp: per frame a device float32 tensor or None; boxes3d: per frame a BOX3D_DTYPE array or None"""
+        import torch
+        from .dynsim import BOX3D_DTYPE
+        from .frontend import DV_MEM_DEVICE, DV_STACK_F32, DV_STACK_U8
+        nf = len(stacks)
+        assert all(t.is_cuda and t.is_contiguous() and t.dim() == 3 and t.dtype == stacks[0].dtype for t in stacks)
+        sp = (C.c_void_p * nf)(*[t.data_ptr() for t in stacks])
+        npl = np.array([t.shape[0] for t in stacks], np.int32)
+        tid = [np.ascontiguousarray(a, np.int32) for a in track_ids]
+        cls = [np.ascontiguousarray(a, np.int32) for a in class_ids] if class_ids is not None else None
+        assert all(len(a) == n for a, n in zip(tid, npl)) and (cls is None or all(len(a) == n for a, n in zip(cls, npl)))
+        tp = (C.c_void_p * nf)(*[a.ctypes.data for a in tid]); cp = (C.c_void_p * nf)(*[a.ctypes.data for a in cls]) if cls is not None else None
+        q = dv_seq_stack()
+        q.stack, q.n_planes = C.cast(sp, C.c_void_p), npl.ctypes.data
+        q.kind, q.mem, q.row_stride, q.plane_stride = (DV_STACK_F32 if stacks[0].dtype == torch.float32 else DV_STACK_U8), DV_MEM_DEVICE, 0, 0
+        q.min_inst_size, q.threshold, q.static_as_background = int(min_inst_size), float(threshold), 1 if static_as_background else 0
+        q.track_id, q.class_id = C.cast(tp, C.c_void_p), (C.cast(cp, C.c_void_p) if cp is not None else None)
+        b3 = bp = nb = None
+        if boxes3d is not None:
+            b3 = [np.ascontiguousarray(b, BOX3D_DTYPE) for b in boxes3d]
+            bp = (C.c_void_p * nf)(*[(b.ctypes.data if len(b) else None) for b in b3]); nb = np.array([len(b) for b in b3], np.int32)
+            q.boxes3d, q.n_boxes3d = C.cast(bp, C.c_void_p), nb.ctypes.data
+        dp = (C.c_void_p * nf)(*[d.data_ptr() for d in disp]) if disp is not None else None
+        q.disp, q.disp_mem, q.disp_stride, q.baseline = (C.cast(dp, C.c_void_p) if dp is not None else None), DV_MEM_DEVICE, 0, float(baseline)
+        self._keep += [stacks, sp, npl, tid, cls, tp, cp, b3, bp, nb, disp, dp, q]
+        if self.lib.dv_runner_set_inst_stack(self.h, i, C.byref(q)) != 0:
             raise DvinsError(self.lib.dv_runner_error(self.h).decode())
 
     def dynamic_stats(self, i):

@@ -174,6 +174,11 @@ void dv_est_destroy_internal(dv_estimator* e);
 struct dv_inst_tracker;
 void dv_inst_destroy_internal(dv_inst_tracker* t);
 int dv_inst_wait_before_next_frame(dv_ctx* ctx, hipStream_t s, bool consume = true);
+// A dv_mask_stack as the kernels read it (dvins_api.hip).  st: a descriptor dv_stack_check passed, strides filled in.  Device / pinned stacks are read in place.  A host
+// stack is taken from the copy the frame's dv_inst_stack_frame_enqueue staged when st equals that stack's descriptor and the frame has been collected (one staging per
+// frame); any other host stack is staged into own_buf, tightly packed, on s
+int dv_stack_resolve(dv_ctx* ctx, const dv_mask_stack& st, struct DevBuf& own_buf, hipStream_t s, DvStackSrc* out);
+void dv_stack_frame_done(dv_ctx* ctx);      // dv_track_stereo_collect: the shared staging ends with the frame
 
 // One window sharded by landmark over several GPUs (be_shard.hip): the transport of the exchange vectors
 struct DvDist {
@@ -218,6 +223,12 @@ struct dv_ctx {
     // dv_viode_frame_enqueue / _collect: thread T1's per-frame stage (label images -> inverse merged mask, key images, boxes) on the ctx's stream.  Two buffer sets
     // used alternately: set[cur] belongs to the frame enqueued last; the key images of the frame before stay intact while its objects are tracked
     struct ViodeFrame* viode = nullptr;      // (defined in dvins_api.hip, released by dv_destroy)
+    // dv_inst_stack_frame_enqueue / _collect: the same stage from a detector's mask stack (merged mask, inverse, boxes; a DV_MEM_HOST stack staged once per frame)
+    struct InstStackFrame* istack = nullptr;      // (defined in dvins_api.hip, released by dv_destroy)
+    // dv_track_unmask_static_planes: the same rectangles, the per-pixel test being "the detection's plane has the pixel".  Dropped on EVERY return of the next
+    // dv_track_stereo_enqueue / dv_batch_track_enqueue; a host stack the frame's stage did not stage is staged into unmask_stack_buf by that enqueue
+    struct UnmaskPlaneJob { int x, y, w, h, plane; };
+    std::vector<UnmaskPlaneJob> unmask_planes; dv_mask_stack unmask_stack{}; DevBuf unmask_stack_buf;
     DevBuf undist_buf[2]; bool undist[2] = { false, false }; int undist_w = 0, undist_h = 0;      // cfg::is_undistort_input: fixed-point maps per camera (map1 | map2)
     bool cam_switched = false; dv_cam cam_orig[2]{};      // dv_undistort_setup: cfg.cam0 / cam1 hold (newK, 0); the cameras the ctx was created with, restored when the maps are removed
     DevBuf out_buf; dv_feat* out_dev = nullptr; int* nout_dev = nullptr;

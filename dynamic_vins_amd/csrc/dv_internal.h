@@ -130,6 +130,17 @@ void dv_launch_unmask_keys(uint8_t* inv_mask, int pitch, int W, int H, int x0, i
 // c < w, 0 for w <= c < dpitch (the padding carries a defined value), r < h.  kpitch in ELEMENTS; the rectangle lies inside the key image (checked by the caller)
 struct DvKeyRoiJob { const uint32_t* key; uint8_t* dst; int kpitch, x0, y0, w, h, dpitch; uint32_t id; int pad_; };
 void dv_launch_key_roi_mask_multi(const DvKeyRoiJob* jobs_dev, int n_jobs, int dpitch_max, int h_max, hipStream_t s);
+// the detector's mask stack (inst_stack.hip; include/dvins.h dv_mask_stack): a device-addressable view of it, strides in BYTES
+struct DvStackSrc { const uint8_t* base; long long plane_stride; int row_stride, n_planes, kind; float thr; };
+// one pass over the stack: merge / inv (w x h bytes, tightly packed) and boxes[n_planes][4] = row_min, row_max, col_min, col_max (the caller initialises them to max, -1, max, -1)
+void dv_launch_inst_stack(const DvStackSrc& S, int w, int h, uint8_t* merge, uint8_t* inv, int32_t* boxes, hipStream_t s);
+void dv_launch_stack_finish_remap(const uint8_t* src, int spitch, int w, int h, uint8_t* merge, uint8_t* inv, hipStream_t s);      // merge = src made tight, inv = ~src
+// the ROI masks of all visible objects of a frame from their planes in ONE launch (dv_inst_track_enqueue_planes): dst(r, c) = plane has (y0 + r, x0 + c) ? 255 : 0 for c < w,
+// 0 for w <= c < dpitch, r < h.  dst 4-byte aligned, dpitch a multiple of 4; the rectangle lies inside the plane (checked by the caller)
+struct DvPlaneRoiJob { const uint8_t* plane; uint8_t* dst; int row_stride, x0, y0, w, h, dpitch, kind; float thr; };
+void dv_launch_plane_roi_mask_multi(const DvPlaneRoiJob* jobs_dev, int n_jobs, int dpitch_max, int h_max, hipStream_t s);
+// the plane form of dv_launch_unmask (dv_track_unmask_static_planes): inv_mask(y0 + r, x0 + c) = 255 where the plane has that pixel
+void dv_launch_unmask_plane(uint8_t* inv_mask, int pitch, int W, int H, int x0, int y0, int w, int h, const uint8_t* plane, int row_stride, int kind, float thr, hipStream_t s);
 hipError_t dv_copy_async(void* dst, const void* src, size_t bytes, hipStream_t s);      // copy.hip: device <-> PINNED host (or device <-> device) as a kernel on s — no copy engine in the per-frame path
 int  dv_launch_gftt_select(const GfttSelectArgs& a, hipStream_t s);
 void dv_launch_compact(const DvTrackState& tr, const uint8_t* in_mask, int mask_pitch, int sort_by_cnt, int* n_cand,

@@ -8,6 +8,7 @@
 // The per-frame orchestration of the tracker (one sequence, or a dv_batch group in shared launches) is front_track.hip.
 #include "dv_ctx.h"
 #include "viode_host.h"
+#include "inst_stack_host.h"
 
 static std::string g_last_error;
 static std::mutex g_err_mutex;
@@ -180,6 +181,58 @@ static void dv_viode_frame_release(dv_ctx* ctx) {
     delete V; ctx->viode = nullptr;
 }
 
+// dv_inst_stack_frame_enqueue / _collect: the same stage from a detector's mask stack.  Two buffer sets used alternately, as above: set[cur] belongs to the frame enqueued
+// last.  A DV_MEM_HOST stack is staged into its set (tightly packed) and `from` remembers its descriptor: the *_planes entries of the frame find the copy there.
+struct InstStackFrame {
+    struct Set { DevBuf merge, inv, staged; dv_mask_stack from{}; bool has_staged = false; } set[2];
+    int cur = 1;
+    DevBuf small /* boxes (1024 B) */, scratch /* DV_STACK_REMAP_MERGED: the merged mask before the remap | the remapped one, pitched */;
+    uint8_t* pinned = nullptr;      // box initialiser (1024 B) | the frame's boxes (1024 B)
+    hipEvent_t ev = nullptr; bool pending = false; int n_planes = 0;
+};
+static void dv_inst_stack_frame_release(dv_ctx* ctx) {
+    InstStackFrame* V = ctx->istack;
+    if (!V) return;
+    for (InstStackFrame::Set& q : V->set) { q.merge.release(); q.inv.release(); q.staged.release(); }
+    V->small.release(); V->scratch.release();
+    if (V->pinned) (void)hipHostFree(V->pinned);
+    if (V->ev) (void)hipEventDestroy(V->ev);
+    delete V; ctx->istack = nullptr;
+}
+static bool same_stack(const dv_mask_stack& a, const dv_mask_stack& b) {
+    return a.data == b.data && a.n_planes == b.n_planes && a.kind == b.kind && a.mem == b.mem && a.row_stride == b.row_stride && a.plane_stride == b.plane_stride;
+}
+// a host stack -> dst, tightly packed (rows of w * es bytes, planes of w * h * es), on s
+static int stage_host_stack(dv_ctx* ctx, const dv_mask_stack& st, int es, DevBuf& dst, hipStream_t s) {
+    const int w = ctx->cfg.width, h = ctx->cfg.height;
+    const size_t row = (size_t)w * es, plane = row * h;
+    DV_CHECK(dst.ensure(plane * st.n_planes));
+    if ((size_t)st.row_stride == row) DV_CHECK(hipMemcpy2DAsync(dst.p, plane, st.data, (size_t)st.plane_stride, plane, st.n_planes, hipMemcpyHostToDevice, s));
+    else for (int p = 0; p < st.n_planes; ++p)
+        DV_CHECK(hipMemcpy2DAsync((uint8_t*)dst.p + p * plane, row, (const uint8_t*)st.data + (size_t)p * st.plane_stride, (size_t)st.row_stride, row, h, hipMemcpyHostToDevice, s));
+    return 0;
+}
+// the frame whose background tracking has just been collected is over: the staged stack of a COLLECTED stage no longer stands in for a host stack of the same descriptor
+// (a caller who refills the buffer for the next frame without running the stage gets its new content staged, not the old copy).  A stage in flight belongs to the next frame
+void dv_stack_frame_done(dv_ctx* ctx) {
+    InstStackFrame* V = ctx->istack;
+    if (!V) return;
+    if (V->pending) V->set[V->cur ^ 1].has_staged = false;
+    else V->set[0].has_staged = V->set[1].has_staged = false;
+}
+int dv_stack_resolve(dv_ctx* ctx, const dv_mask_stack& st, DevBuf& own_buf, hipStream_t s, DvStackSrc* out) {
+    const int es = st.kind == DV_STACK_F32 ? 4 : 1, w = ctx->cfg.width, h = ctx->cfg.height;
+    if (st.mem != DV_MEM_HOST) { *out = DvStackSrc{ (const uint8_t*)st.data, (long long)st.plane_stride, st.row_stride, st.n_planes, st.kind, st.threshold }; return 0; }
+    const void* dev = nullptr;
+    if (ctx->istack && !ctx->istack->pending) {
+        const InstStackFrame::Set& Q = ctx->istack->set[ctx->istack->cur];
+        if (Q.has_staged && same_stack(Q.from, st)) dev = Q.staged.p;
+    }
+    if (!dev) { if (stage_host_stack(ctx, st, es, own_buf, s)) return -1; dev = own_buf.p; }
+    *out = DvStackSrc{ (const uint8_t*)dev, (long long)w * es * h, w * es, st.n_planes, st.kind, st.threshold };
+    return 0;
+}
+
 extern "C" {
 
 void* dv_pinned_alloc(size_t bytes) {
@@ -270,6 +323,7 @@ void dv_destroy(dv_ctx* ctx) {
     if (ctx->unmask_pinned) (void)hipHostFree(ctx->unmask_pinned);
     ctx->unmask_keys_buf.release();
     dv_viode_frame_release(ctx);
+    dv_inst_stack_frame_release(ctx); ctx->unmask_stack_buf.release();
     if (ctx->done) (void)hipEventDestroy(ctx->done);
     if (ctx->ev_pyr) (void)hipEventDestroy(ctx->ev_pyr);
     if (ctx->ev_bg_select) (void)hipEventDestroy(ctx->ev_bg_select);
@@ -604,6 +658,83 @@ int dv_viode_frame_collect(dv_ctx* ctx, int min_inst_size, dv_inst_det* dets, in
     if (inv_mask_dev) *inv_mask_dev = (const uint8_t*)Q.inv.p;
     if (keys0_dev) *keys0_dev = (const uint32_t*)Q.keys0.p;
     if (keys1_dev) *keys1_dev = V.has_right ? (const uint32_t*)Q.keys1.p : nullptr;
+    return 0;
+}
+
+// ImageProcessor::Run's detector branch for ONE frame (image_process/image_process.cpp:160-170: Detector2D::Launch's threshold + BuildBoxes2D + the mask half of
+// SetMaskAndRoi / SetBackgroundMask) as enqueue + collect: inst_stack_kernel over the stack into library-owned buffers; n_planes x 16 bytes of boxes are the frame's ONLY
+// device -> host traffic
+int dv_inst_stack_frame_enqueue(dv_ctx* ctx, const dv_mask_stack* stack, int w, int h, int flags) {
+    if (!ctx) return -1;
+    if (w != ctx->cfg.width || h != ctx->cfg.height) DV_FAIL("dv_inst_stack_frame_enqueue: image size differs from config");
+    DvStackLayout L;
+    if (const char* why = dv_stack_check(stack, w, h, &L)) DV_FAIL(std::string("dv_inst_stack_frame_enqueue: ") + why);
+    if (flags & ~DV_STACK_REMAP_MERGED) DV_FAIL("dv_inst_stack_frame_enqueue: unknown flag");
+    const bool remap = (flags & DV_STACK_REMAP_MERGED) != 0;
+    if (remap && !ctx->undist[0]) DV_FAIL("dv_inst_stack_frame_enqueue: DV_STACK_REMAP_MERGED needs installed undistortion maps (dv_undistort_setup / dv_set_undistort_maps)");
+    if (ctx->istack && ctx->istack->pending) DV_FAIL("dv_inst_stack_frame_enqueue: previous frame not collected");
+    DV_CHECK(hipSetDevice(ctx->cfg.device));
+    hipStream_t s = ctx->stream;
+    if (!ctx->istack) ctx->istack = new InstStackFrame();          // (a half-built one is completed by the next call or released by dv_destroy)
+    InstStackFrame& V = *ctx->istack;
+    if (!V.ev) DV_CHECK(hipEventCreateWithFlags(&V.ev, hipEventDisableTiming));
+    if (!V.pinned) {
+        void* p = nullptr;
+        DV_CHECK(hipHostMalloc(&p, 2048, hipHostMallocDefault));
+        V.pinned = (uint8_t*)p;
+        int32_t* init = (int32_t*)V.pinned;
+        for (int k = 0; k < 64; ++k) { init[4 * k] = 0x7fffffff; init[4 * k + 1] = -1; init[4 * k + 2] = 0x7fffffff; init[4 * k + 3] = -1; }
+    }
+    const size_t plane = ((size_t)w * h + 255) / 256 * 256;          // the masks are tightly packed: the inverse goes to dv_track_stereo_enqueue as a DV_MEM_DEVICE mask beside frames of stride w
+    const int rp = align_up(w, 16);
+    InstStackFrame::Set& Q = V.set[V.cur ^ 1];
+    DV_CHECK(Q.merge.ensure(plane)); DV_CHECK(Q.inv.ensure(plane)); DV_CHECK(V.small.ensure(1024));
+    if (remap) DV_CHECK(V.scratch.ensure(plane + (size_t)rp * h));
+    // The set about to be overwritten held the frame before the last.  Its masks are read on this stream alone.  Its STAGED host stack may still be read by that frame's
+    // objects on the object tracker's stream when the caller enqueues this stage before the dv_track_stereo_enqueue that would wait for them (stage k + 1 in front of
+    // tracking k): only then the stream waits for the object tracker.  Device / pinned stacks are never copied, so their stage runs beside the object stream.
+    if (Q.has_staged && dv_inst_wait_before_next_frame(ctx, s, false)) DV_FAIL("dv_inst_stack_frame_enqueue: hipStreamWaitEvent");
+    dv_mask_stack st = *stack; st.row_stride = L.row_stride; st.plane_stride = L.plane_stride;
+    DvStackSrc S{ (const uint8_t*)st.data, L.plane_stride, L.row_stride, st.n_planes, st.kind, st.threshold };
+    Q.has_staged = false;
+    if (st.mem == DV_MEM_HOST) {
+        if (stage_host_stack(ctx, st, L.es, Q.staged, s)) return -1;
+        S.base = (const uint8_t*)Q.staged.p; S.row_stride = w * L.es; S.plane_stride = (long long)w * L.es * h;
+    }
+    int32_t* d_box = (int32_t*)V.small.p;
+    DV_CHECK(dv_copy_async(d_box, V.pinned, 1024, s));          // the boxes start every frame at (max, -1, max, -1)
+    {
+        StageScope sc_t(ctx, "inst_stack_frame");
+        if (!remap) dv_launch_inst_stack(S, w, h, (uint8_t*)Q.merge.p, (uint8_t*)Q.inv.p, d_box, s);
+        else {          // SetBackgroundMask: merged -> cv::remap(left maps, INTER_LINEAR) -> inverted
+            uint8_t* raw = (uint8_t*)V.scratch.p; uint8_t* mapped = raw + plane;
+            dv_launch_inst_stack(S, w, h, raw, (uint8_t*)Q.inv.p, d_box, s);
+            const uint8_t* maps = (const uint8_t*)ctx->undist_buf[0].p;
+            dv_launch_remap(raw, nullptr, w, h, w, 1, 0, (const int16_t*)maps, (const uint16_t*)(maps + (size_t)4 * w * h), nullptr, nullptr, mapped, nullptr, rp, s);
+            dv_launch_stack_finish_remap(mapped, rp, w, h, (uint8_t*)Q.merge.p, (uint8_t*)Q.inv.p, s);
+        }
+    }
+    DV_CHECK(hipGetLastError());
+    DV_CHECK(dv_copy_async(V.pinned + 1024, d_box, 1024, s));
+    DV_CHECK(hipEventRecord(V.ev, s));
+    if (st.mem == DV_MEM_HOST) { Q.from = st; Q.has_staged = true; }
+    V.cur ^= 1; V.pending = true; V.n_planes = st.n_planes;
+    return 0;
+}
+
+int dv_inst_stack_frame_collect(dv_ctx* ctx, int min_inst_size, dv_inst_det* dets, int32_t* planes, int cap, int* n_dets, const uint8_t** inv_mask_dev, const uint8_t** merge_mask_dev) {
+    if (!ctx) return -1;
+    if (!ctx->istack || !ctx->istack->pending) DV_FAIL("dv_inst_stack_frame_collect: nothing enqueued");
+    if (!n_dets || cap < 0 || (cap > 0 && !dets)) DV_FAIL("dv_inst_stack_frame_collect: bad argument");
+    InstStackFrame& V = *ctx->istack;
+    DV_CHECK(hipEventSynchronize(V.ev));
+    V.pending = false;
+    const int n = dv_stack_build_dets((const int32_t*)(V.pinned + 1024), V.n_planes, min_inst_size, dets, planes, cap);
+    if (n < 0) DV_FAIL("dv_inst_stack_frame_collect: more detections than `cap`");
+    *n_dets = n;
+    const InstStackFrame::Set& Q = V.set[V.cur];
+    if (inv_mask_dev) *inv_mask_dev = (const uint8_t*)Q.inv.p;
+    if (merge_mask_dev) *merge_mask_dev = (const uint8_t*)Q.merge.p;
     return 0;
 }
 

@@ -4,6 +4,7 @@
 // Both entries take what the stages are given from ONE description of the frame (front_plan), mode and mask included: the single entry launches it by value with the
 // single-sequence kernels, the group entry scatters it into the job tables of the _multi kernels — raw, semantic and naive members alike.
 #include "dv_ctx.h"
+#include "inst_stack_host.h"
 
 // What the stages of one frame of one context are given, in the job types of the table kernels
 struct FrontPlan {
@@ -135,7 +136,7 @@ int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gr
     if (!ctx) return -1;
     HostScope hs(ctx, "h_front_enqueue");
     // what dv_track_unmask_static_keys staged belongs to THIS call: applied below, or dropped with whichever return ends the call
-    struct KeyJobsGuard { dv_ctx* c; ~KeyJobsGuard() { c->unmask_keys.clear(); c->unmask_key_img = nullptr; } } key_jobs_guard{ ctx };
+    struct KeyJobsGuard { dv_ctx* c; ~KeyJobsGuard() { c->unmask_keys.clear(); c->unmask_key_img = nullptr; c->unmask_planes.clear(); c->unmask_stack = dv_mask_stack{}; } } key_jobs_guard{ ctx };
     if (!gray0) DV_FAIL("dv_track_stereo: gray0 is null");
     if (w != ctx->cfg.width || h != ctx->cfg.height) DV_FAIL("dv_track_stereo: image size differs from config (reference: std::terminate, main.cpp:95-99)");
     if (ctx->pending) DV_FAIL("dv_track_stereo_enqueue: previous frame not collected");
@@ -163,15 +164,19 @@ int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gr
         if (P.cuda_prev) { dv_launch_cuda_pyramids(P.cpyr_prev, s); ctx->leftc_valid[cur ^ 1] = true; }
         DV_CHECK(hipGetLastError());
     }
+    // the unmasking forms below write the mask: a caller's device buffer is never written to, they work on a copy in mask_buf
+    auto own_mask = [&](const uint8_t*& mask_dev, int& mask_pitch) -> int {
+        if (mask_dev == (const uint8_t*)ctx->mask_buf.p) return 0;
+        const int mp = align_up(w, 16);
+        DV_CHECK(ctx->mask_buf.ensure((size_t)mp * h));
+        DV_CHECK(hipMemcpy2DAsync(ctx->mask_buf.p, mp, mask_dev, mask_pitch, w, h, hipMemcpyDeviceToDevice, s));
+        mask_dev = (const uint8_t*)ctx->mask_buf.p; mask_pitch = mp;
+        return 0;
+    };
     if (!ctx->unmask.empty()) {          // system/main.cpp:217-245: the static instances' pixels leave the merged mask (inv_merge_mask = 255 there) before anything reads it
         const uint8_t* mask_dev = P.mask; int mask_pitch = P.mask_pitch;
         if (!mask_dev) { ctx->unmask.clear(); DV_FAIL("dv_track_unmask_static: the frame carries no mask"); }
-        if (mask_dev != (const uint8_t*)ctx->mask_buf.p) {          // the caller's device buffer is not written to: work on a copy
-            const int mp = align_up(w, 16);
-            DV_CHECK(ctx->mask_buf.ensure((size_t)mp * h));
-            DV_CHECK(hipMemcpy2DAsync(ctx->mask_buf.p, mp, mask_dev, mask_pitch, w, h, hipMemcpyDeviceToDevice, s));
-            mask_dev = (const uint8_t*)ctx->mask_buf.p; mask_pitch = mp;
-        }
+        if (own_mask(mask_dev, mask_pitch)) return -1;
         for (const dv_ctx::UnmaskJob& j : ctx->unmask)
             dv_launch_unmask((uint8_t*)ctx->mask_buf.p, mask_pitch, w, h, j.x, j.y, j.w, j.h, (const uint8_t*)ctx->unmask_pinned + j.off, s);
         ctx->unmask.clear();
@@ -180,12 +185,7 @@ int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gr
     if (!ctx->unmask_keys.empty()) {     // the key-image form of the same step (dv_track_unmask_static_keys): the per-pixel test is key == id
         const uint8_t* mask_dev = P.mask; int mask_pitch = P.mask_pitch;
         if (!mask_dev) DV_FAIL("dv_track_unmask_static_keys: the frame carries no mask");
-        if (mask_dev != (const uint8_t*)ctx->mask_buf.p) {          // the caller's device buffer is not written to: work on a copy
-            const int mp = align_up(w, 16);
-            DV_CHECK(ctx->mask_buf.ensure((size_t)mp * h));
-            DV_CHECK(hipMemcpy2DAsync(ctx->mask_buf.p, mp, mask_dev, mask_pitch, w, h, hipMemcpyDeviceToDevice, s));
-            mask_dev = (const uint8_t*)ctx->mask_buf.p; mask_pitch = mp;
-        }
+        if (own_mask(mask_dev, mask_pitch)) return -1;
         const uint32_t* kimg = ctx->unmask_key_img; int kpitch = ctx->unmask_key_stride / 4;
         if (ctx->unmask_key_mem == DV_MEM_HOST) {                   // staged once for the frame
             DV_CHECK(ctx->unmask_keys_buf.ensure((size_t)4 * w * h));
@@ -194,6 +194,16 @@ int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gr
         }
         for (const dv_ctx::UnmaskKeyJob& j : ctx->unmask_keys)
             dv_launch_unmask_keys((uint8_t*)ctx->mask_buf.p, mask_pitch, w, h, j.x, j.y, j.w, j.h, kimg, kpitch, j.id, s);
+        if (front_plan_mask(ctx, mode, mask_dev, mask_pitch, P)) return -1;
+    }
+    if (!ctx->unmask_planes.empty()) {   // the mask-stack form (dv_track_unmask_static_planes): the per-pixel test is "the detection's plane has the pixel"
+        const uint8_t* mask_dev = P.mask; int mask_pitch = P.mask_pitch;
+        if (!mask_dev) DV_FAIL("dv_track_unmask_static_planes: the frame carries no mask");
+        if (own_mask(mask_dev, mask_pitch)) return -1;
+        DvStackSrc S{};
+        if (dv_stack_resolve(ctx, ctx->unmask_stack, ctx->unmask_stack_buf, s, &S)) return -1;
+        for (const dv_ctx::UnmaskPlaneJob& j : ctx->unmask_planes)
+            dv_launch_unmask_plane((uint8_t*)ctx->mask_buf.p, mask_pitch, w, h, j.x, j.y, j.w, j.h, S.base + (size_t)j.plane * S.plane_stride, S.row_stride, S.kind, S.thr, s);
         if (front_plan_mask(ctx, mode, mask_dev, mask_pitch, P)) return -1;
     }
     if (P.has_erode) { const DvErodeJob& k = P.erode; dv_launch_erode(k.src, k.w, k.h, k.spitch, k.k, k.tmp, k.tpitch, k.dst, k.dpitch, s); }
@@ -290,11 +300,33 @@ int dv_track_unmask_static_keys(dv_ctx* ctx, const dv_inst_det* dets, int n_dets
     return 0;
 }
 
+// the mask-stack form: the same rectangle jobs, the ROI mask of detection i being "plane planes[i] has the pixel" (include/dvins.h, dv_mask_stack).  The stack is read in
+// place by the next dv_track_stereo_enqueue (device / pinned), taken from the copy the frame's stage staged, or staged there once (any other host stack)
+int dv_track_unmask_static_planes(dv_ctx* ctx, const dv_inst_det* dets, const int32_t* planes, int n_dets, const uint32_t* static_ids, int n_static, const dv_mask_stack* stack) {
+    if (!ctx) return -1;
+    ctx->unmask_planes.clear(); ctx->unmask_stack = dv_mask_stack{};
+    if (n_static <= 0 || n_dets <= 0) return 0;
+    if (!dets || !planes || !static_ids) DV_FAIL("dv_track_unmask_static_planes: null argument");
+    DvStackLayout L;
+    if (const char* why = dv_stack_check(stack, ctx->cfg.width, ctx->cfg.height, &L)) DV_FAIL(std::string("dv_track_unmask_static_planes: ") + why);
+    if (ctx->pending) DV_FAIL("dv_track_unmask_static_planes: call it before dv_track_stereo_enqueue of the frame it belongs to");
+    // every rectangle and plane index is checked before a job is staged: the kernel's reads are bounded by them
+    if (const char* why = dv_stack_check_dets(dets, planes, n_dets, stack->n_planes, ctx->cfg.width, ctx->cfg.height, static_ids, n_static)) DV_FAIL(std::string("dv_track_unmask_static_planes: ") + why);
+    for (int i = 0; i < n_dets; ++i) {
+        const dv_inst_det& d = dets[i];
+        if (std::find(static_ids, static_ids + n_static, d.track_id) == static_ids + n_static) continue;
+        ctx->unmask_planes.push_back({ d.x, d.y, d.w, d.h, planes[i] });
+    }
+    if (!ctx->unmask_planes.empty()) { ctx->unmask_stack = *stack; ctx->unmask_stack.row_stride = L.row_stride; ctx->unmask_stack.plane_stride = L.plane_stride; }
+    return 0;
+}
+
 int dv_track_stereo_collect(dv_ctx* ctx, dv_feat* out, int* n_out) {
     if (!ctx) return -1;
     if (!ctx->pending) DV_FAIL("dv_track_stereo_collect: nothing enqueued");
     { HostScope hs(ctx, "h_front_wait"); DV_CHECK(hipEventSynchronize(ctx->last_done ? ctx->last_done : ctx->done)); }
     ctx->pending = false;
+    dv_stack_frame_done(ctx);
     if (ctx->timing) dv_harvest_timers(ctx, ctx->stream);
     if (*ctx->err_pinned) {
         int f = *ctx->err_pinned;
@@ -376,7 +408,7 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
     // a refused / failed call — no job survives into a later frame
     struct UnmaskGuard {
         const std::vector<dv_ctx*>& mem; const dv_track_job* jobs; int n;
-        ~UnmaskGuard() { for (int i = 0; i < n; ++i) if (jobs[i].member >= 0 && jobs[i].member < (int)mem.size()) { mem[jobs[i].member]->unmask.clear(); mem[jobs[i].member]->unmask_keys.clear(); } }
+        ~UnmaskGuard() { for (int i = 0; i < n; ++i) if (jobs[i].member >= 0 && jobs[i].member < (int)mem.size()) { mem[jobs[i].member]->unmask.clear(); mem[jobs[i].member]->unmask_keys.clear(); mem[jobs[i].member]->unmask_planes.clear(); mem[jobs[i].member]->unmask_stack = dv_mask_stack{}; } }
     } unmask_guard{ mem, jobs, n };
     for (int i = 0; i < n; ++i) {
         const dv_track_job& j = jobs[i];
@@ -384,7 +416,7 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
         for (int q = 0; q < i; ++q) if (jobs[q].member == j.member) DV_FAIL("dv_batch_track_enqueue: a member appears twice");
         const dv_ctx* c = mem[j.member];
         if (c->timing || !j.gray0 || (c->cfg.stereo && !j.gray1)) continue;
-        if (!c->unmask_keys.empty()) continue;          // dv_track_unmask_static_keys jobs: the member's own entry applies them (the round's unmask launch reads host masks)
+        if (!c->unmask_keys.empty() || !c->unmask_planes.empty()) continue;          // dv_track_unmask_static_keys / _planes jobs: the member's own entry applies them (the round's unmask launch reads host masks)
         if (j.mode == DV_MODE_SEMANTIC && j.mask) kind[i] = K_SEMANTIC;
         else if (c->inst) continue;
         else if (j.mode == DV_MODE_RAW && !j.mask) kind[i] = K_RAW;

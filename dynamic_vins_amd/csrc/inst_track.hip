@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <map>
 #include "dv_ctx.h"
+#include "inst_stack_host.h"
 
 #define INST_CAP 256          // device capacity per object (max_dynamic_cnt <= 200)
 
@@ -103,11 +104,12 @@ struct dv_inst_tracker {
     // extra points from the frame's disparity map (dv_inst_set_disparity; extra_points.hip): the reference's second thread = a side stream
     const float* disp_user = nullptr; int disp_stride = 0, disp_mem = 0; double disp_baseline = 0; bool disp_next = false, xp_frame = false, xp_inflight = false;
     const uint32_t* keys_user = nullptr; int keys_stride = 0, keys_mem = 0; bool keys_next = false; DevBuf keys_buf;
+    DevBuf stack_buf;          // dv_inst_track_enqueue_planes with a DV_MEM_HOST stack the frame's stage did not stage
     DevBuf keys0_buf;          // dv_inst_track_enqueue_keys with a DV_MEM_HOST key image: staged once per frame      // VIODE: seg1's key image of the next frame (dv_inst_set_right_keys)
     DevBuf disp_buf, xp_pool; hipStream_t xstream = nullptr; hipEvent_t ev_xin = nullptr, ev_xdone = nullptr;
     void* xp_pinned = nullptr; size_t xp_cap_slots = 0;          // per output slot: count (64 bytes) + 3 * DV_XP_CAP doubles, written by the kernel straight into pinned memory
     ~dv_inst_tracker() {
-        disp_buf.release(); xp_pool.release(); keys_buf.release(); keys0_buf.release();
+        disp_buf.release(); xp_pool.release(); keys_buf.release(); keys0_buf.release(); stack_buf.release();
         if (xstream) { (void)hipStreamSynchronize(xstream); (void)hipStreamDestroy(xstream); }
         if (ev_xin) (void)hipEventDestroy(ev_xin);
         if (ev_xdone) (void)hipEventDestroy(ev_xdone);
@@ -223,8 +225,10 @@ int dv_inst_reset(dv_ctx* ctx) {
 
 // the frame's object masks: the detections' own host masks (dv_inst_track_enqueue: ks == nullptr) or the comparison of the frame's key image with each detection's
 // track id, done on the device (dv_inst_track_enqueue_keys)
+// — or "plane planes[i] of the detector's mask stack has the pixel", also on the device (dv_inst_track_enqueue_planes: ps != nullptr; st passed dv_stack_check, strides filled in)
 struct InstKeySrc { const uint32_t* img; int stride_bytes, mem; };
-static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_dets, const dv_box3d* boxes3d, int n_boxes3d, const InstKeySrc* ks) {
+struct InstPlaneSrc { const dv_mask_stack* st; const int32_t* planes; };
+static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_dets, const dv_box3d* boxes3d, int n_boxes3d, const InstKeySrc* ks, const InstPlaneSrc* ps = nullptr) {
     HostScope hs(ctx, "h_inst_enqueue");
     if (!ctx->inst) DV_FAIL("dv_inst_track: call dv_inst_config first");
     if (n_dets < 0 || (n_dets > 0 && !dets) || n_boxes3d < 0 || (n_boxes3d > 0 && !boxes3d)) DV_FAIL("dv_inst_track: bad argument");
@@ -249,7 +253,7 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
     for (int i = 0; i < n_dets; ++i) {
         const dv_inst_det& d = dets[i];
         if (d.w <= 0 || d.h <= 0 || d.x < 0 || d.y < 0 || d.x + d.w > W || d.y + d.h > H) DV_FAIL("dv_inst_track: detection rectangle outside the image");
-        if (!ks && !d.mask) DV_FAIL("dv_inst_track: detection without a mask");
+        if (!ks && !ps && !d.mask) DV_FAIL("dv_inst_track: detection without a mask");
         auto it = T.slots.find(d.track_id);
         if (it == T.slots.end()) {
             it = T.slots.emplace(d.track_id, Slot()).first; it->second.id = d.track_id;
@@ -258,7 +262,7 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
         Slot& S = it->second;
         if (S.visible) DV_FAIL("dv_inst_track: two detections with the same track id");
         S.visible = true; S.has_box2d = true; S.class_id = d.class_id; S.rx = d.x; S.ry = d.y; S.rw = d.w; S.rh = d.h;
-        if (ks) S.pts_copy.clear();          // (the key form ignores dv_inst_det::points)
+        if (ks || ps) S.pts_copy.clear();          // (the key and plane forms ignore dv_inst_det::points)
         else S.pts_copy.assign(d.points ? d.points : nullptr, d.points ? d.points + 3 * (size_t)std::max(d.n_points, 0) : nullptr);
         mask_bytes += (size_t)align_up(d.w, 16) * d.h;
     }
@@ -293,7 +297,7 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
         //  hipHostFree + hipHostMalloc resp. two stream synchronisations + hipFree + hipMalloc — 5 - 8 ms during which the estimator thread's HIP calls wait for the runtime's
         //  locks too; seen as one 6 ms frame somewhere in the first frames of the dynamic bench line's timed region in every second run)
         const size_t mask_floor = 2 * (size_t)align_up(W, 16) * H + 4096;
-        if (!ks && T.pinned_in_bytes < mask_bytes) {
+        if (!ks && !ps && T.pinned_in_bytes < mask_bytes) {
             if (T.pinned_in) (void)hipHostFree(T.pinned_in);
             T.pinned_in = nullptr; T.pinned_in_bytes = 0;
             const size_t want = std::max(mask_bytes * 2 + 4096, mask_floor);
@@ -337,7 +341,7 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
         {
             const size_t need = ((size_t)na * 2 * sizeof(RoiJob) + (size_t)na * DV_MAX_LEVELS * sizeof(DvPyrJob) + (size_t)na * sizeof(DvExtraJob) +
                                  (size_t)na * (sizeof(DvCompactJob) + sizeof(DvErodeJob) + sizeof(GfttTileArgs) + sizeof(GfttSelectArgs) + sizeof(DvFinalizeJob)) + 4096) +
-                                (ks ? (size_t)na * sizeof(DvKeyRoiJob) + 256 : 0);
+                                (ks ? (size_t)na * sizeof(DvKeyRoiJob) + 256 : 0) + (ps ? (size_t)na * sizeof(DvPlaneRoiJob) + 256 : 0);
             if (need > T.arena_cap) {
                 DV_CHECK(hipStreamSynchronize(s));
                 const size_t cap = need * 2;
@@ -360,7 +364,7 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
         auto up256 = [](size_t v) { return (v + 255) / 256 * 256; };
         const size_t cj_off = up256(xp_off + (size_t)na * sizeof(DvExtraJob)), ej_off = up256(cj_off + (size_t)na * sizeof(DvCompactJob)), gt_off = up256(ej_off + (size_t)na * sizeof(DvErodeJob)),
                      gs_off = up256(gt_off + (size_t)na * sizeof(GfttTileArgs)), fj_off = up256(gs_off + (size_t)na * sizeof(GfttSelectArgs)),
-                     kj_off = up256(fj_off + (size_t)na * sizeof(DvFinalizeJob)), arena_used = ks ? kj_off + (size_t)na * sizeof(DvKeyRoiJob) : fj_off + (size_t)na * sizeof(DvFinalizeJob);
+                     kj_off = up256(fj_off + (size_t)na * sizeof(DvFinalizeJob)), arena_used = ks ? kj_off + (size_t)na * sizeof(DvKeyRoiJob) : ps ? kj_off + (size_t)na * sizeof(DvPlaneRoiJob) : fj_off + (size_t)na * sizeof(DvFinalizeJob);
         DvCompactJob* h_cj = (DvCompactJob*)((uint8_t*)T.arena_pinned + cj_off); DvErodeJob* h_ej = (DvErodeJob*)((uint8_t*)T.arena_pinned + ej_off);
         GfttTileArgs* h_gt = (GfttTileArgs*)((uint8_t*)T.arena_pinned + gt_off); GfttSelectArgs* h_gs = (GfttSelectArgs*)((uint8_t*)T.arena_pinned + gs_off);
         DvFinalizeJob* h_fj = (DvFinalizeJob*)((uint8_t*)T.arena_pinned + fj_off);
@@ -372,6 +376,10 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
             DV_CHECK(hipMemcpy2DAsync(T.keys0_buf.p, (size_t)W * 4, ks->img, (size_t)ks->stride_bytes, (size_t)W * 4, H, hipMemcpyHostToDevice, s));
             kimg0 = (const uint32_t*)T.keys0_buf.p; kpitch0 = W;
         }
+        // the plane form: one job per object for plane_roi_mask_multi_kernel in the same place of the same upload; a host stack the frame's stage did not stage is staged once
+        DvPlaneRoiJob* h_pj = (DvPlaneRoiJob*)((uint8_t*)T.arena_pinned + kj_off);
+        DvStackSrc psrc{};
+        if (ps && na > 0 && dv_stack_resolve(ctx, *ps->st, T.stack_buf, s, &psrc)) return -1;
         int ero_W = 0, ero_H = 0, nj = 0;
         const double dt_fin = dt;
         T.xp_frame = T.disp_next; T.disp_next = false;
@@ -391,6 +399,10 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
             S.mask = (uint8_t*)T.mask_all.p + moff;
             if (ks) {
                 h_kj[nj] = DvKeyRoiJob{ kimg0, S.mask, kpitch0, S.rx, S.ry, w, h, mp, S.id, 0 };
+                key_P = std::max(key_P, mp); key_H = std::max(key_H, h);
+            } else if (ps) {
+                int plane = 0; for (int i = 0; i < n_dets; ++i) if (dets[i].track_id == S.id) plane = ps->planes[i];
+                h_pj[nj] = DvPlaneRoiJob{ psrc.base + (size_t)plane * psrc.plane_stride, S.mask, psrc.row_stride, S.rx, S.ry, w, h, mp, psrc.kind, psrc.thr };
                 key_P = std::max(key_P, mp); key_H = std::max(key_H, h);
             } else {
                 uint8_t* hm = (uint8_t*)T.pinned_in + moff;
@@ -447,9 +459,10 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
             }
         }
         if (na > 0) {
-            if (!ks) DV_CHECK(dv_copy_async(T.mask_all.p, T.pinned_in, moff, s));
+            if (!ks && !ps) DV_CHECK(dv_copy_async(T.mask_all.p, T.pinned_in, moff, s));
             DV_CHECK(dv_copy_async(T.arena.p, T.arena_pinned, arena_used, s));
             if (ks) dv_launch_key_roi_mask_multi((const DvKeyRoiJob*)((const uint8_t*)T.arena.p + kj_off), na, key_P, key_H, s);
+            if (ps) dv_launch_plane_roi_mask_multi((const DvPlaneRoiJob*)((const uint8_t*)T.arena.p + kj_off), na, key_P, key_H, s);
             if (T.xp_frame && n_xp > 0) {
                 // the reference starts a thread for this (dynamic_tracker.cpp:378): a side stream behind the mask + table uploads; the objects' tracking goes on meanwhile
                 DV_CHECK(hipEventRecord(T.ev_xin, s));
@@ -545,6 +558,19 @@ int dv_inst_track_enqueue_keys(dv_ctx* ctx, double t, const dv_inst_det* dets, i
     }
     const InstKeySrc ks{ key_image, stride_bytes, mem };
     return inst_track_enqueue_impl(ctx, t, dets, n_dets, boxes3d, n_boxes3d, &ks);
+}
+
+// the mask-stack form (include/dvins.h): mask of detection i = "plane planes[i] has the pixel" over its rectangle, cut on the device
+int dv_inst_track_enqueue_planes(dv_ctx* ctx, double t, const dv_inst_det* dets, const int32_t* planes, int n_dets, const dv_mask_stack* stack, const dv_box3d* boxes3d, int n_boxes3d) {
+    if (!ctx) return -1;
+    DvStackLayout L;
+    if (const char* why = dv_stack_check(stack, ctx->cfg.width, ctx->cfg.height, &L)) DV_FAIL(std::string("dv_inst_track_enqueue_planes: ") + why);
+    if (n_dets < 0 || (n_dets > 0 && (!dets || !planes))) DV_FAIL("dv_inst_track_enqueue_planes: bad argument");
+    // every rectangle and plane index before anything is staged: the kernel's reads are bounded by them
+    if (const char* why = dv_stack_check_dets(dets, planes, n_dets, stack->n_planes, ctx->cfg.width, ctx->cfg.height, nullptr, 0)) DV_FAIL(std::string("dv_inst_track_enqueue_planes: ") + why);
+    dv_mask_stack st = *stack; st.row_stride = L.row_stride; st.plane_stride = L.plane_stride;
+    const InstPlaneSrc ps{ &st, planes };
+    return inst_track_enqueue_impl(ctx, t, dets, n_dets, boxes3d, n_boxes3d, nullptr, &ps);
 }
 
 // VIODE: the keys of SemanticImage::seg1 of the frame the NEXT dv_inst_track_enqueue processes (include/dvins.h)

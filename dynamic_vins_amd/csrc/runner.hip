@@ -39,6 +39,11 @@
 #pragma weak dv_viode_frame_collect
 #pragma weak dv_track_unmask_static_keys
 #pragma weak dv_inst_track_enqueue_keys
+// ... and of a mask-stack sequence (dv_runner_set_inst_stack), likewise
+#pragma weak dv_inst_stack_frame_enqueue
+#pragma weak dv_inst_stack_frame_collect
+#pragma weak dv_track_unmask_static_planes
+#pragma weak dv_inst_track_enqueue_planes
 
 namespace {
 // choice T1: DV_STATIC_REPORT_LAG (DVINS_STATIC_LAG in the environment: experiments only — the Python pipeline and the parity harness read the same variable)
@@ -91,6 +96,9 @@ struct RSeq {
     // stage is enqueued and not collected yet (-1: none).  Touched by the thread that enqueues the tracking alone (T2, or the one-thread loop)
     bool live = false; dv_seq_viode vio{}; std::vector<dv_inst_det> live_dets; int live_n = 0, live_enq = -1;
     const uint8_t* live_inv = nullptr; const uint32_t* live_k0 = nullptr; const uint32_t* live_k1 = nullptr;
+    // dv_runner_set_inst_stack: the same stage from the detector's mask stack (live is set too).  live_planes[i] = the plane of live_dets[i]; live_st = the descriptor of the
+    // frame whose stage was collected last — what the *_planes entries of that frame take
+    bool live_stack = false; dv_seq_stack stk{}; std::vector<int32_t> live_planes; dv_mask_stack live_st{};
     // TrackImageNaive over the sequence (dv_runner_set_mask): per frame the inverse merged instance mask, and the tracking mode that takes it
     const uint8_t* const* raw_mask = nullptr; int raw_mode = DV_MODE_RAW;
 };
@@ -145,6 +153,7 @@ struct TrackInput {
     const dv_inst_det* dets = nullptr; int n_dets = 0; const dv_box3d* boxes = nullptr; int n_boxes = 0;
     const float* disp = nullptr; const uint32_t* right_keys = nullptr; int right_keys_mem = 0;
     const uint32_t* keys = nullptr; bool unmask = false;
+    const dv_mask_stack* stack = nullptr; const int32_t* planes = nullptr;      // a mask-stack frame: its calls take their plane forms
 };
 // raw sequence | sequence with dv_runner_set_mask | dynamic sequence | label-image sequence whose stage of frame k has been collected (viode_collect)
 TrackInput track_input(const RSeq& s, int k) {
@@ -156,6 +165,7 @@ TrackInput track_input(const RSeq& s, int k) {
     in.disp = d.disp ? d.disp[k] : nullptr;
     if (s.live) {
         in.mask = s.live_inv; in.keys = s.live_k0; in.right_keys = s.live_k1; in.right_keys_mem = DV_MEM_DEVICE;
+        if (s.live_stack) { in.stack = &s.live_st; in.planes = s.live_planes.data(); in.keys = nullptr; in.right_keys = nullptr; }
         in.dets = s.live_n ? s.live_dets.data() : nullptr; in.n_dets = s.live_n;
         in.unmask = s.static_unmask && s.live_n > 0;
     } else {
@@ -181,7 +191,8 @@ int seq_unmask(dv_runner* R, RSeq& s, int k, const TrackInput& in) {
     if (!in.unmask) return 0;
     uint32_t ids[256];          // (a snapshot holds at most the 256 ids dyn_passed asks for)
     const int n = static_ids(s, k, ids);
-    if (s.live) { if (dv_track_unmask_static_keys(s.ctx, in.dets, in.n_dets, n ? ids : nullptr, n, in.keys, 0, DV_MEM_DEVICE)) return fail(R, s, "dv_track_unmask_static_keys"); }
+    if (s.live_stack) { if (dv_track_unmask_static_planes(s.ctx, in.dets, in.planes, in.n_dets, n ? ids : nullptr, n, in.stack)) return fail(R, s, "dv_track_unmask_static_planes"); }
+    else if (s.live) { if (dv_track_unmask_static_keys(s.ctx, in.dets, in.n_dets, n ? ids : nullptr, n, in.keys, 0, DV_MEM_DEVICE)) return fail(R, s, "dv_track_unmask_static_keys"); }
     else if (dv_track_unmask_static(s.ctx, in.dets, in.n_dets, n ? ids : nullptr, n)) return fail(R, s, "dv_track_unmask_static");
     return 0;
 }
@@ -190,7 +201,8 @@ int seq_enqueued(dv_runner* R, RSeq& s, int k, const TrackInput& in) {
         const dv_seq_dynamic& d = s.dyn;
         if (in.disp && dv_inst_set_disparity(s.ctx, in.disp, d.disp_stride, d.disp_mem, d.baseline)) return fail(R, s, "dv_inst_set_disparity");
         if (in.right_keys && dv_inst_set_right_keys(s.ctx, in.right_keys, 0, in.right_keys_mem)) return fail(R, s, "dv_inst_set_right_keys");
-        if (s.live) { if (dv_inst_track_enqueue_keys(s.ctx, s.in.times[k], in.dets, in.n_dets, in.keys, 0, DV_MEM_DEVICE, in.boxes, in.n_boxes)) return fail(R, s, "dv_inst_track_enqueue_keys"); }
+        if (s.live_stack) { if (dv_inst_track_enqueue_planes(s.ctx, s.in.times[k], in.dets, in.planes, in.n_dets, in.stack, in.boxes, in.n_boxes)) return fail(R, s, "dv_inst_track_enqueue_planes"); }
+        else if (s.live) { if (dv_inst_track_enqueue_keys(s.ctx, s.in.times[k], in.dets, in.n_dets, in.keys, 0, DV_MEM_DEVICE, in.boxes, in.n_boxes)) return fail(R, s, "dv_inst_track_enqueue_keys"); }
         else if (dv_inst_track_enqueue(s.ctx, s.in.times[k], in.dets, in.n_dets, in.boxes, in.n_boxes)) return fail(R, s, "dv_inst_track_enqueue");
     }
     s.enqueued = true; s.started = true;
@@ -198,7 +210,20 @@ int seq_enqueued(dv_runner* R, RSeq& s, int k, const TrackInput& in) {
 }
 // a label-image sequence (dv_runner_set_viode): T1's stage of frame k is collected (enqueued first, if frame k - 1 did not do it), then FeatureTrack's calls in their
 // key-image forms, then T1's stage of frame k + 1 is enqueued behind them — its boxes arrive while the host is busy with frame k
+// (a mask-stack sequence, dv_runner_set_inst_stack: the same two steps on dv_inst_stack_frame_*; behind the collect the upstream tracker's answer goes onto the detections —
+// track id and class per plane, -1 = the plane is dropped: the reference's class filter, image_process/image_process.cpp:217-232)
+dv_mask_stack stack_of(const RSeq& s, int k) {
+    const dv_seq_stack& q = s.stk;
+    dv_mask_stack st{}; st.data = q.stack[k]; st.n_planes = q.n_planes[k]; st.kind = q.kind; st.mem = q.mem; st.row_stride = q.row_stride; st.plane_stride = q.plane_stride; st.threshold = q.threshold;
+    return st;
+}
 int viode_stage(dv_runner* R, RSeq& s, int k) {
+    if (s.live_stack) {
+        const dv_mask_stack st = stack_of(s, k);
+        if (dv_inst_stack_frame_enqueue(s.ctx, &st, s.w, s.h, 0)) return fail(R, s, "dv_inst_stack_frame_enqueue");
+        s.live_enq = k;
+        return 0;
+    }
     const dv_seq_viode& v = s.vio;
     if (dv_viode_frame_enqueue(s.ctx, v.seg0[k], v.seg1 ? v.seg1[k] : nullptr, s.w, s.h, v.stride, v.mem, v.dyn_keys, v.nkeys)) return fail(R, s, "dv_viode_frame_enqueue");
     s.live_enq = k;
@@ -207,6 +232,19 @@ int viode_stage(dv_runner* R, RSeq& s, int k) {
 int viode_collect(dv_runner* R, RSeq& s, int k) {
     if (s.live_enq != k && viode_stage(R, s, k)) return -1;
     s.live_enq = -1;
+    if (s.live_stack) {
+        if (dv_inst_stack_frame_collect(s.ctx, s.stk.min_inst_size, s.live_dets.data(), s.live_planes.data(), (int)s.live_dets.size(), &s.live_n, &s.live_inv, nullptr)) return fail(R, s, "dv_inst_stack_frame_collect");
+        s.live_st = stack_of(s, k);
+        int n = 0;
+        for (int i = 0; i < s.live_n; ++i) {
+            const int p = s.live_planes[i], tid = s.stk.track_id[k][p], cls = s.stk.class_id ? s.stk.class_id[k][p] : 0;
+            if (tid < 0 || cls < 0) continue;
+            dv_inst_det d = s.live_dets[i]; d.track_id = (uint32_t)tid; d.class_id = cls;
+            s.live_dets[n] = d; s.live_planes[n] = p; ++n;
+        }
+        s.live_n = n;
+        return 0;
+    }
     if (dv_viode_frame_collect(s.ctx, s.vio.min_inst_size, s.live_dets.data(), (int)s.live_dets.size(), &s.live_n, &s.live_inv, &s.live_k0, &s.live_k1)) return fail(R, s, "dv_viode_frame_collect");
     return 0;
 }
@@ -614,7 +652,7 @@ int dv_runner_set_dynamic(dv_runner* R, int seq, const dv_seq_dynamic* dyn) {
     if (seq_started(s)) return set_err(R, "dv_runner_set_dynamic: the sequence has already started");
     if (!s.ctx->inst) return set_err(R, "dv_runner_set_dynamic: call dv_inst_config on the sequence's context first");
     if (dyn->inv_mask && dyn->mask_mem != s.in.mem) return set_err(R, "dv_runner_set_dynamic: mask_mem must equal the frames' mem (dv_track_stereo_enqueue takes frames and mask from one memory kind)");
-    s.dynamic = true; s.live = false; s.dyn = *dyn; s.static_unmask = dyn->static_as_background != 0;
+    s.dynamic = true; s.live = false; s.live_stack = false; s.dyn = *dyn; s.static_unmask = dyn->static_as_background != 0;
     for (auto& b : s.db) b.reserve();
     for (auto& b : s.ring) b.reserve();
     return 0;
@@ -635,7 +673,30 @@ int dv_runner_set_viode(dv_runner* R, int seq, const dv_seq_viode* v) {
     dv_seq_dynamic d{};          // what the stage does not produce per frame travels as in a dynamic sequence (track_input)
     d.mode = DV_MODE_SEMANTIC; d.disp = v->disp; d.disp_mem = v->disp_mem; d.disp_stride = v->disp_stride; d.baseline = v->baseline; d.static_as_background = v->static_as_background;
     if (dv_runner_set_dynamic(R, seq, &d)) return -1;
-    s.live = true; s.vio = *v; s.live_enq = -1; s.live_dets.assign(64, dv_inst_det{});
+    s.live = true; s.live_stack = false; s.vio = *v; s.live_enq = -1; s.live_dets.assign(64, dv_inst_det{});
+    return 0;
+}
+// A mask-stack sequence: the same loop with the detector branch of T1's stage inside it
+int dv_runner_set_inst_stack(dv_runner* R, int seq, const dv_seq_stack* q) {
+    RSeq* sp = seq_at(R, seq);
+    if (!sp || !q) return -1;
+    RSeq& s = *sp;
+    if (s.grouped) return set_err(R, "dv_runner_set_inst_stack: a sequence of a dv_batch group is not supported (the group's shared unmask launch reads host masks)");
+    if (seq_started(s)) return set_err(R, "dv_runner_set_inst_stack: the sequence has already started");
+    if (!dv_inst_stack_frame_enqueue || !dv_inst_stack_frame_collect || !dv_track_unmask_static_planes || !dv_inst_track_enqueue_planes) return set_err(R, "dv_runner_set_inst_stack: the mask-stack entries are not linked into this build");
+    if (!s.ctx->inst) return set_err(R, "dv_runner_set_inst_stack: call dv_inst_config on the sequence's context first");
+    if (!q->stack || !q->n_planes || !q->track_id) return set_err(R, "dv_runner_set_inst_stack: per frame a stack, its number of planes and the planes' track ids are needed");
+    if (q->kind != DV_STACK_U8 && q->kind != DV_STACK_F32) return set_err(R, "dv_runner_set_inst_stack: unknown element kind");
+    if (q->mem != DV_MEM_HOST && q->mem != DV_MEM_DEVICE && q->mem != DV_MEM_PINNED) return set_err(R, "dv_runner_set_inst_stack: unknown memory kind of the stacks");
+    for (int k = 0; k < s.in.n_frames; ++k)
+        if (!q->stack[k] || !q->track_id[k] || q->n_planes[k] < 1 || q->n_planes[k] > DV_STACK_MAX_PLANES) return set_err(R, "dv_runner_set_inst_stack: every frame needs a stack of 1..64 planes and their track ids (a frame without instances: one empty plane)");
+    if (s.in.mem != DV_MEM_DEVICE && s.in.mem != DV_MEM_PINNED) return set_err(R, "dv_runner_set_inst_stack: the frames must be DV_MEM_DEVICE or DV_MEM_PINNED (the inverse mask stays on the device and travels with them)");
+    if (s.stride != s.w) return set_err(R, "dv_runner_set_inst_stack: the frames' row stride must equal the width (the inverse mask is tightly packed)");
+    dv_seq_dynamic d{};          // what the stage does not produce per frame travels as in a dynamic sequence (track_input)
+    d.mode = DV_MODE_SEMANTIC; d.boxes3d = q->boxes3d; d.n_boxes3d = q->n_boxes3d; d.disp = q->disp; d.disp_mem = q->disp_mem; d.disp_stride = q->disp_stride; d.baseline = q->baseline;
+    d.static_as_background = q->static_as_background;
+    if (dv_runner_set_dynamic(R, seq, &d)) return -1;
+    s.live = true; s.live_stack = true; s.stk = *q; s.live_enq = -1; s.live_dets.assign(64, dv_inst_det{}); s.live_planes.assign(64, 0);
     return 0;
 }
 // slam_type naive over a sequence (system/main.cpp:263-265 FeatureTrack -> TrackImageNaive): per frame the inverse merged instance mask (0 = object) the tracker takes,

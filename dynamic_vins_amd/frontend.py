@@ -14,6 +14,26 @@ class dv_inst_det(C.Structure):
                 ("mask", C.c_void_p), ("points", C.c_void_p), ("n_points", C.c_int32), ("pad_", C.c_int32)]
 
 
+class dv_mask_stack(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("n_planes", C.c_int32), ("kind", C.c_int32), ("mem", C.c_int32), ("row_stride", C.c_int32), ("plane_stride", C.c_int64),
+                ("threshold", C.c_float), ("reserved", C.c_int32)]
+
+
+DV_STACK_U8, DV_STACK_F32, DV_STACK_REMAP_MERGED = 0, 1, 1
+
+
+def mask_stack(stack, mem=DV_MEM_HOST, n_planes=0, kind=DV_STACK_U8, row_stride=0, plane_stride=0, threshold=0.0):
+    """dv_mask_stack of a detector's instance masks: a [n, h, w] numpy array (uint8 / bool -> DV_STACK_U8, float32 -> DV_STACK_F32; any strides with unit element stride;
+    host memory, kept alive by the caller) or a raw device / pinned pointer (int) with mem, n_planes, kind and the strides in bytes (0 = tight)"""
+    if isinstance(stack, dv_mask_stack):
+        return stack
+    if isinstance(stack, np.ndarray):
+        assert stack.ndim == 3 and stack.dtype in (np.uint8, np.bool_, np.float32) and stack.strides[2] == stack.itemsize
+        kind = DV_STACK_F32 if stack.dtype == np.float32 else DV_STACK_U8
+        return dv_mask_stack(stack.ctypes.data, stack.shape[0], kind, DV_MEM_HOST, stack.strides[1], stack.strides[0], float(threshold), 0)
+    return dv_mask_stack(int(stack), int(n_planes), int(kind), int(mem), int(row_stride), int(plane_stride), float(threshold), 0)
+
+
 FEAT_DTYPE = np.dtype([("id", np.uint32), ("track_cnt", np.int32), ("has_right", np.int32), ("pad_", np.int32),
                        ("left", np.float64, 7), ("right", np.float64, 7)])
 assert FEAT_DTYPE.itemsize == C.sizeof(dv_feat) == 128
@@ -201,6 +221,49 @@ class Context:
         self._check(self.lib.dv_viode_frame_collect(self.h, int(min_inst_size), C.addressof(arr), int(cap), C.byref(n), C.byref(inv), C.byref(k0), C.byref(k1)))
         dets = [dict(track_id=int(a.track_id), class_id=int(a.class_id), rect=(int(a.x), int(a.y), int(a.w), int(a.h)), mask=None, points=None) for a in arr[: n.value]]
         return dets, inv.value, k0.value, k1.value
+
+    def inst_stack_frame_enqueue(self, stack, remap_merged=False, **kw):
+        """thread T1's stage of one frame from a detector's mask stack (see mask_stack() for `stack` and the keywords) -> library-owned device buffers.
+        remap_merged: SemanticImage::SetBackgroundMask's remap of the merged mask (needs installed undistortion maps)"""
+        st = mask_stack(stack, **kw)
+        self._stack_keep = (stack, st)
+        self._check(self.lib.dv_inst_stack_frame_enqueue(self.h, C.addressof(st), self.cfg.width, self.cfg.height, DV_STACK_REMAP_MERGED if remap_merged else 0))
+
+    def inst_stack_frame_collect(self, min_inst_size=8, cap=64):
+        """-> (dets [dict(track_id = plane, class_id, rect, plane, mask=None, points=None)], inverse merged mask, merged mask) — the two masks as DEVICE POINTERS (int)
+        into the library's buffers of that frame.  The caller's multi-object tracker overwrites track_id / class_id; `plane` stays."""
+        arr = (dv_inst_det * max(cap, 1))()
+        planes = (C.c_int32 * max(cap, 1))()
+        n, inv, mrg = C.c_int(0), C.c_void_p(0), C.c_void_p(0)
+        self._check(self.lib.dv_inst_stack_frame_collect(self.h, int(min_inst_size), C.addressof(arr), C.addressof(planes), int(cap), C.byref(n), C.byref(inv), C.byref(mrg)))
+        dets = [dict(track_id=int(a.track_id), class_id=int(a.class_id), rect=(int(a.x), int(a.y), int(a.w), int(a.h)), plane=int(planes[i]), mask=None, points=None)
+                for i, a in enumerate(arr[: n.value])]
+        return dets, inv.value, mrg.value
+
+    @staticmethod
+    def _plane_array(dets):
+        planes = (C.c_int32 * max(len(dets), 1))()
+        for k, d in enumerate(dets):
+            planes[k] = int(d["plane"])
+        return planes
+
+    def inst_track_enqueue_planes(self, t, dets, stack, boxes3d=None, **kw):
+        """inst_track_enqueue with the objects' masks cut on the device from the detector's mask stack: mask of a detection = "plane d['plane'] has the pixel" over its
+        rectangle.  dets: dicts with track_id, rect and plane (mask / points are ignored)"""
+        from .dynsim import BOX3D_DTYPE
+        arr, planes, st = self._det_array(dets), self._plane_array(dets), mask_stack(stack, **kw)
+        b3 = np.ascontiguousarray(boxes3d, BOX3D_DTYPE) if boxes3d is not None else np.zeros(0, BOX3D_DTYPE)
+        self._inst_keep = [arr, planes, b3, stack, st]
+        self._check(self.lib.dv_inst_track_enqueue_planes(self.h, float(t), C.addressof(arr) if len(dets) else None, C.addressof(planes) if len(dets) else None, len(dets),
+                                                          C.addressof(st), b3.ctypes.data if len(b3) else None, len(b3)))
+
+    def track_unmask_static_planes(self, dets, static_ids, stack, **kw):
+        """track_unmask_static from the detector's mask stack: the pixels of plane d['plane'] inside the rectangles of the static detections leave the merged mask"""
+        ids = np.ascontiguousarray(static_ids, np.uint32)
+        arr, planes, st = self._det_array(dets), self._plane_array(dets), mask_stack(stack, **kw)
+        self._unmask_keep = [stack, st]
+        self._check(self.lib.dv_track_unmask_static_planes(self.h, C.addressof(arr) if len(dets) else None, C.addressof(planes) if len(dets) else None, len(dets),
+                                                           ids.ctypes.data if len(ids) else None, len(ids), C.addressof(st)))
 
     def inst_set_right_keys(self, key_img, mem=DV_MEM_HOST):
         """VIODE: the key image of seg1 (viode_mask(...)[2]: uint32 [h, w] numpy array, or a device pointer with mem=DV_MEM_DEVICE) of the frame the next inst_track_enqueue

@@ -608,6 +608,26 @@ public:
         f.dets.resize(n);
         return f;
     }
+    // the same stage from the detector's N x H x W instance-mask stack (Detector2D::Launch's output left on the device; BuildBoxes2D, det2d/detector2d.cpp:58-97, and the
+    // mask half of SemanticImage::SetMaskAndRoi / SetBackgroundMask, basic/semantic_image.cpp:20-93): dv_inst_stack_frame_enqueue / _collect, then the plane forms —
+    // planes[i] = the plane of dets[i]; the multi-object tracker writes dets[i].track_id / class_id in between.  remap_merged: SetBackgroundMask (slam_type naive)
+    struct StackFrame { std::vector<dv_inst_det> dets; std::vector<int32_t> planes; const uint8_t* inv_mask = nullptr; const uint8_t* merge_mask = nullptr; };
+    void StackFrameEnqueue(const dv_mask_stack& stack, int w, int h, bool remap_merged = false) {
+        detail::check(ctx_, dv_inst_stack_frame_enqueue(ctx_, &stack, w, h, remap_merged ? DV_STACK_REMAP_MERGED : 0), "StackFrameEnqueue");
+    }
+    StackFrame StackFrameCollect(int min_inst_size = 8) {
+        StackFrame f; f.dets.resize(64); f.planes.resize(64); int n = 0;
+        detail::check(ctx_, dv_inst_stack_frame_collect(ctx_, min_inst_size, f.dets.data(), f.planes.data(), 64, &n, &f.inv_mask, &f.merge_mask), "StackFrameCollect");
+        f.dets.resize(n); f.planes.resize(n);
+        return f;
+    }
+    void UnmaskStaticInstances(const std::vector<dv_inst_det>& dets, const std::vector<int32_t>& planes, const std::vector<uint32_t>& static_ids, const dv_mask_stack& stack) {
+        detail::check(ctx_, dv_track_unmask_static_planes(ctx_, dets.empty() ? nullptr : dets.data(), planes.empty() ? nullptr : planes.data(), (int)dets.size(), static_ids.empty() ? nullptr : static_ids.data(), (int)static_ids.size(), &stack), "UnmaskStaticInstances");
+    }
+    void InstsTrack(double time, const std::vector<dv_inst_det>& dets, const std::vector<int32_t>& planes, const dv_mask_stack& stack, const std::vector<dv_box3d>& boxes3d = {}) {
+        detail::check(ctx_, dv_inst_track_enqueue_planes(ctx_, time, dets.empty() ? nullptr : dets.data(), planes.empty() ? nullptr : planes.data(), (int)dets.size(), &stack, boxes3d.empty() ? nullptr : boxes3d.data(), (int)boxes3d.size()), "InstsTrack");
+        pending_ = true;
+    }
     void InstsTrack(double time, const std::vector<dv_inst_det>& dets, const std::vector<dv_box3d>& boxes3d = {}) {
         detail::check(ctx_, dv_inst_track_enqueue(ctx_, time, dets.empty() ? nullptr : dets.data(), (int)dets.size(), boxes3d.empty() ? nullptr : boxes3d.data(), (int)boxes3d.size()), "InstsTrack");
         pending_ = true;

@@ -215,11 +215,15 @@ class DynamicPipeline(Pipeline):
 
     def __init__(self, seq: DynamicSequence, max_cnt=250, min_dist=25, max_iters=10, device=0, use_imu=1, max_dynamic_cnt=50, min_dynamic_dist=5, use_det3d=1,
                  static_inst_threshold=1.0, mask_morphology_size=0, segments=None, est_kw=None, extra_from_disparity=True, ba_stride=1,
-                 static_as_background=False, live_masks=False):
+                 static_as_background=False, live_masks=False, mask_stack=False):
         from .frontend import DV_MODE_SEMANTIC
         # live_masks: `seq` carries label images (a viode.ViodeSequence: seg0, seg1, dyn_keys) and thread T1's stage runs per frame on the device (viode_frame_enqueue /
         # _collect + the key-image entries) instead of reading the sequence's pre-computed masks, detections and key images; same results, bit for bit
         self.live_masks, self._live_enq = bool(live_masks), None
+        # mask_stack: the detector branch of the same stage — per frame an N x H x W instance-mask stack on the device (stack_input(): seq.mask_stacks, or one plane per
+        # dynamic key cut from a label-image sequence) through inst_stack_frame_enqueue / _collect and the plane entries; bit for bit the pre-computed path's results
+        self.mask_stack, self._stack_in = bool(mask_stack), None
+        assert not (live_masks and mask_stack)
         self.extra_from_disparity = extra_from_disparity      # False: the detections' own `points` are handed through (the caller ran the extra-point pipeline)
         self.seq, self.host = seq, None
         c = make_cam(*sim.cam_tuple(seq.cam))
@@ -248,6 +252,48 @@ class DynamicPipeline(Pipeline):
         best = [s for s in self.static_snaps if s[0] <= k - DV_STATIC_REPORT_LAG]
         return best[-1][1] if best else np.zeros(0, np.uint32)
 
+    def stack_input(self):
+        """-> dict(stacks: per frame a uint8 [n, h, w] device tensor, track_ids / class_ids: per frame one int per plane, min_inst_size).  A sequence that carries
+        mask_stacks / stack_track_ids / stack_class_ids hands them over; a label-image sequence (seg0, dyn_keys) is turned into one plane per dynamic key, track id = key"""
+        if self._stack_in is None:
+            import torch
+            from . import viode
+            s = self.seq
+            if hasattr(s, "mask_stacks"):
+                self._stack_in = dict(stacks=s.mask_stacks, track_ids=s.stack_track_ids, class_ids=s.stack_class_ids, min_inst_size=getattr(s, "min_inst_size", viode.MIN_INST_SIZE))
+            else:
+                keys = [int(v) for v in s.dyn_keys]
+                dev = s.frames[0][0].device
+                stacks = []
+                for g in s.seg0:
+                    kimg = viode.pixel_to_key(g[..., 2], g[..., 1], g[..., 0])
+                    stacks.append(torch.from_numpy(np.stack([kimg == key for key in keys]).astype(np.uint8)).to(dev))
+                torch.cuda.synchronize()
+                self._stack_in = dict(stacks=stacks, track_ids=[np.array(keys, np.int32)] * len(stacks), class_ids=[np.zeros(len(keys), np.int32)] * len(stacks), min_inst_size=viode.MIN_INST_SIZE)
+        return self._stack_in
+
+    def _enqueue_stack(self, k):
+        from .frontend import DV_MEM_DEVICE as DEV
+        s, ctx, q = self.seq, self.ctx, self.stack_input()
+        l, r = s.frames[k]
+        kw = lambda j: dict(mem=DEV, n_planes=q["stacks"][j].shape[0])
+        if self._live_enq != k:
+            ctx.inst_stack_frame_enqueue(q["stacks"][k].data_ptr(), **kw(k))
+        self._live_enq = None
+        dets, inv, _ = ctx.inst_stack_frame_collect(q["min_inst_size"])
+        dets = [dict(d, track_id=int(q["track_ids"][k][d["plane"]]), class_id=int(q["class_ids"][k][d["plane"]])) for d in dets]
+        dets = [d for d in dets if d["track_id"] >= 0 and d["class_id"] >= 0]          # the upstream tracker's answer; -1 drops the plane
+        if self.static_as_background and len(dets):
+            ctx.track_unmask_static_planes(dets, self.static_ids_for(k), q["stacks"][k].data_ptr(), **kw(k))
+        ctx.track_stereo_enqueue(l.data_ptr(), r.data_ptr(), s.times[k], inv, self.mode, DEV)
+        if self.extra_from_disparity and len(getattr(s, "disp_dev", [])):
+            ctx.inst_set_disparity(s.disp_dev[k].data_ptr(), s.baseline, DEV)
+        ctx.inst_track_enqueue_planes(s.times[k], dets, q["stacks"][k].data_ptr(), **kw(k))
+        self.enqueued = True
+        if k + 1 < len(s.frames):          # T1's stage of the next frame behind this frame's tracking
+            ctx.inst_stack_frame_enqueue(q["stacks"][k + 1].data_ptr(), **kw(k + 1))
+            self._live_enq = k + 1
+
     def _enqueue_live(self, k):
         from . import viode
         s, ctx = self.seq, self.ctx
@@ -270,6 +316,8 @@ class DynamicPipeline(Pipeline):
             self._live_enq = k + 1
 
     def _enqueue(self, k):
+        if self.mask_stack:
+            return self._enqueue_stack(k)
         if self.live_masks:
             return self._enqueue_live(k)
         l, r = self.seq.frames[k]

@@ -168,6 +168,40 @@ int dv_viode_mask(dv_ctx* ctx, const uint8_t* seg_bgr, int w, int h, int stride,
 struct dv_inst_det;
 int dv_viode_frame_enqueue(dv_ctx* ctx, const uint8_t* seg0_bgr, const uint8_t* seg1_bgr_or_null, int w, int h, int stride, int mem, const uint32_t* dyn_keys, int nkeys);
 int dv_viode_frame_collect(dv_ctx* ctx, int min_inst_size, struct dv_inst_det* dets, int cap, int* n_dets, const uint8_t** inv_mask_dev, const uint32_t** keys0_dev, const uint32_t** keys1_dev);
+/* Thread T1's stage of ONE frame whose instances arrive as a detector's MASK STACK (ImageProcessor::Run's detector branch, image_process/image_process.cpp:160-170):
+ * N planes of the configured image size, one per instance, as the segmentation network leaves them on the device.  It covers Detector2D::Launch's
+ * `seg_label > kSoloMaskThr` (det2d/detector2d.cpp:441; DV_STACK_F32 only), BuildBoxes2D (det2d/detector2d.cpp:58-97) and the mask half of SemanticImage::SetMaskAndRoi /
+ * SetBackgroundMask (basic/semantic_image.cpp:20-93).
+ * A pixel BELONGS to a plane by the reference's rule mask_tensor.to(kInt8).abs().clamp(0, 1):
+ *   DV_STACK_U8   the thresholded bool / uint8 tensor.  Established with the CPU build, 2.10, of the reference's tensor library (csrc/inst_stack_host.h; scalar and vectorised paths agree over all 256 values): bytes 1..127 -> int8
+ *                 1..127 -> 1; bytes 129..255 -> int8 -127..-1 -> abs 127..1 -> 1; byte 128 -> int8 -128, whose abs WRAPS to -128, clamp(0, 1) -> 0.  So 1, 127, 129 and
+ *                 255 are object pixels and 128 is NOT: belongs = (byte != 0 && byte != 128).  Implemented bug for bug.
+ *   DV_STACK_F32  the detector's soft masks: element > threshold (strict, float compare: NaN is not an object pixel), then the same rule on the resulting 0 / 1.
+ * row_stride / plane_stride in BYTES (0 = tight: width * element size, row_stride * height); DV_STACK_F32 wants data and both strides multiples of 4.  mem = DV_MEM_HOST
+ * (staged by dv_inst_stack_frame_enqueue; valid until the frame is collected), DV_MEM_DEVICE or DV_MEM_PINNED (read in place; must stay valid until the frame's TRACKING is
+ * collected when the stack also goes to dv_inst_track_enqueue_planes / dv_track_unmask_static_planes). */
+#define DV_STACK_U8  0
+#define DV_STACK_F32 1
+#define DV_STACK_MAX_PLANES 64
+typedef struct dv_mask_stack {
+    const void* data; int32_t n_planes /* 1..64 */, kind /* DV_STACK_* */, mem /* DV_MEM_* */, row_stride; int64_t plane_stride; float threshold /* DV_STACK_F32 */; int32_t reserved;
+} dv_mask_stack;
+/* _enqueue: ONE kernel pass over the stack on the ctx's stream (every lane reads 4 consecutive pixels of every plane — a dword, or 16 bytes of floats — keeps the OR in
+ * registers and writes the two masks once) into device buffers the LIBRARY owns: the merged mask (255 where any plane has the pixel: sum(0).clamp(0, 1) * 255), its inverse,
+ * and per plane the box row_min, row_max, col_min, col_max of its pixels (BuildBoxes2D's min / max of nonzero()).  The buffers exist twice and alternate exactly as
+ * dv_viode_frame_*'s do: those of frame k stay intact while frame k + 1 is enqueued and until frame k + 2 is.  The ONLY device -> host traffic is n_planes x 16 bytes of
+ * boxes into pinned memory.  flags: DV_STACK_REMAP_MERGED = SemanticImage::SetBackgroundMask's extra step (slam_type naive, basic/semantic_image.cpp:85-92): the merged mask
+ * goes through cv::remap(left maps, INTER_LINEAR), BORDER_CONSTANT 0 — dv_remap's rule — before it is inverted, inv = ~remap(merged); it needs installed undistortion maps
+ * (dv_undistort_setup / dv_set_undistort_maps) and is refused without them.  SetMaskAndRoi (slam_type dynamic) does not remap, and neither does flags = 0.
+ * One frame may be in flight: _enqueue twice without _collect is refused.
+ * _collect waits for the stage and returns, per NON-EMPTY plane in ASCENDING plane order, a dv_inst_det: rect = cv::Rect(min_pt, max_pt) — max row / column excluded, as
+ * Box2D::rect is built at det2d/detector2d.cpp:89 —, rectangles under min_inst_size pixels on a side dropped, track_id = the plane index (Box2D::id = i), class 0,
+ * mask = points = NULL; planes[i] = the plane of dets[i].  The caller (its multi-object tracker stays upstream) overwrites track_id / class_id before the next step.  An EMPTY
+ * plane is where the reference would throw (the tensor library's max of an empty tensor, det2d/detector2d.cpp:64-66); here it yields no detection.  inv_mask_dev / merge_mask_dev (either may
+ * be NULL): the frame's inverse merged mask and merged mask, w x h bytes, tightly packed, device memory (with DV_STACK_REMAP_MERGED the merged mask is the remapped one). */
+#define DV_STACK_REMAP_MERGED 1
+int dv_inst_stack_frame_enqueue(dv_ctx* ctx, const dv_mask_stack* stack, int w, int h, int flags);
+int dv_inst_stack_frame_collect(dv_ctx* ctx, int min_inst_size, struct dv_inst_det* dets, int32_t* planes, int cap, int* n_dets, const uint8_t** inv_mask_dev, const uint8_t** merge_mask_dev);
 /* cv::cvtColor(BGR2GRAY) on 8-bit images: (B 1868 + G 9617 + R 4899 + 8192) >> 14; gray is w x h, tightly packed */
 int dv_bgr2gray(dv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, uint8_t* gray, int mem);
 /* cv::remap(src, dst, map1, map2, INTER_LINEAR) — BORDER_CONSTANT 0 — with the fixed-point maps cv::initUndistortRectifyMap(..., CV_16SC2, ...)
@@ -657,6 +691,24 @@ typedef struct dv_seq_viode {
     const float* const* disp; int32_t disp_mem, disp_stride; double baseline;      /* as in dv_seq_dynamic; disp may be NULL */
 } dv_seq_viode;
 int dv_runner_set_viode(dv_runner* runner, int seq, const dv_seq_viode* viode);
+/* Dynamic mode of a sequence fed with the detector's INSTANCE-MASK STACKS, one frame at a time (the detector branch of ImageProcessor::Run, image_process/image_process.cpp:160-170;
+ * the KITTI-tracking and ZED dynamic configurations): thread T1's stage runs per frame inside the loop (dv_inst_stack_frame_enqueue / _collect), and the sequence runs the
+ * dynamic loop of dv_runner_set_dynamic — one-thread order or T2 beside T3 ("tracker_thread") — on the plane entries: dv_track_unmask_static_planes (same lag rule,
+ * DV_STATIC_REPORT_LAG), dv_track_stereo_enqueue with the device-resident inverse mask, dv_inst_track_enqueue_planes.  The stage of frame k + 1 is enqueued right behind the
+ * tracking of frame k.  Per frame [n_frames]: the stack (layout, kind and mem shared by all frames: dv_mask_stack), its number of planes (1..64; a frame without instances
+ * hands one empty plane), and per plane the answer of the upstream multi-object tracker: track_id[k][p] / class_id[k][p] (class_id may be NULL: 0), -1 in either = the plane
+ * is dropped (the reference's class filter, image_process/image_process.cpp:217-232; its pixels stay in the merged mask, as there).  Results are bit-identical to
+ * dv_runner_set_dynamic fed the masks and detections pre-computed from the same stacks.  Before the first dv_runner_run; frames DV_MEM_DEVICE or DV_MEM_PINNED with row
+ * stride = width; device / pinned stacks must outlive the run.  Refused with "dv_runner_set_inst_stack: a sequence of a dv_batch group is not supported ..." for a member
+ * of a group; the runner stays usable. */
+typedef struct dv_seq_stack {
+    const void* const* stack; const int32_t* n_planes;
+    int32_t kind /* DV_STACK_* */, mem /* DV_MEM_* of the stacks */, row_stride /* bytes, 0 = tight */, min_inst_size; int64_t plane_stride /* bytes, 0 = tight */; float threshold; int32_t static_as_background;
+    const int32_t* const* track_id; const int32_t* const* class_id;
+    const dv_box3d* const* boxes3d; const int32_t* n_boxes3d;      /* may be NULL (no 3-D detector) */
+    const float* const* disp; int32_t disp_mem, disp_stride; double baseline;      /* as in dv_seq_dynamic; disp may be NULL */
+} dv_seq_stack;
+int dv_runner_set_inst_stack(dv_runner* runner, int seq, const dv_seq_stack* stack);
 /* what the object branch of a dynamic sequence was fed so far: detections, object feature rows, frames with at least one object, fewest detections in a frame */
 int dv_runner_dynamic_stats(dv_runner* runner, int seq, long long* detections, long long* object_features, long long* frames_with_objects, int* min_detections);
 dv_runner* dv_runner_create(dv_ctx* const* ctxs, const dv_seq_input* seqs, int n_seq, int group_size, int threads);      /* group_size <= 1: no batching */
@@ -738,6 +790,21 @@ int dv_inst_track_enqueue(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_
  * masks where dv_inst_track_enqueue uploads them (padding bytes zero); everything behind — ROI crop, erosion, corner detection, LK, extra-point sampling — runs unchanged
  * on those bytes, so the rows equal those of dv_inst_track_enqueue given the masks cut on the host. */
 int dv_inst_track_enqueue_keys(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_dets, const uint32_t* key_image, int stride_bytes, int mem, const dv_box3d* boxes3d, int n_boxes3d);
+/* The same call with the objects' masks cut ON THE DEVICE from the detector's mask stack (SemanticImage::SetMaskAndRoi's ROI masks, basic/semantic_image.cpp:20-66):
+ * the mask of detection i is 255 where plane planes[i] HAS the pixel by dv_mask_stack's rule (for DV_STACK_F32 the threshold is applied here too), over the detection's
+ * rectangle; dv_inst_det::mask and ::points are ignored, track_id / class_id are the caller's (its multi-object tracker's answer).  One launch for all visible objects writes
+ * their slices of the mask area (padding bytes zero); everything behind runs unchanged on those bytes, so the rows equal those of dv_inst_track_enqueue given the masks cut
+ * on the host.  Every rectangle and plane index is checked before anything is staged.  A DV_MEM_HOST stack whose descriptor equals the one the frame's
+ * dv_inst_stack_frame_enqueue staged is NOT copied again (one staging per frame, shared by the stage and the two *_planes entries) — from that stage's collect until the
+ * frame's dv_track_stereo_collect, which ends the sharing: a buffer refilled for a later frame is never answered from an old copy; any other host stack is staged by this
+ * call and must stay valid until the frame is collected.  Device / pinned stacks are read in place and must stay valid until dv_inst_track_collect. */
+struct dv_mask_stack;
+int dv_inst_track_enqueue_planes(dv_ctx* ctx, double t, const dv_inst_det* dets, const int32_t* planes, int n_dets, const struct dv_mask_stack* stack, const dv_box3d* boxes3d, int n_boxes3d);
+/* dv_track_unmask_static (FeatureTrack, system/main.cpp:217-245) with "plane planes[i] has the pixel" as the per-pixel test over the rectangles of the detections whose
+ * track_id is in static_ids.  Applied by the NEXT dv_track_stereo_enqueue (which must carry a mask) and dropped on EVERY return of that call, 0 or -1, as the key-image
+ * form is.  Every rectangle and plane index is validated before anything is staged.  The stack follows the rule above: a host stack the frame's stage staged is shared, any
+ * other is staged by that enqueue (valid until it returns); device / pinned stacks are read in place (valid until the frame is collected). */
+int dv_track_unmask_static_planes(dv_ctx* ctx, const dv_inst_det* dets, const int32_t* planes, int n_dets, const uint32_t* static_ids, int n_static, const struct dv_mask_stack* stack);
 /* SemanticImage::disp (CV_32F disparity of the left image, basic/semantic_image.h:30-65) of the frame about to be handed to dv_inst_track_enqueue.  With it the library
  * runs the reference's extra-point pipeline for every visible object ON THE DEVICE, one launch for all objects on a side stream (the reference: a second thread):
  * InstFeat::DetectExtraPoints (front_end/instance_feature.cpp:413-461: step = max(sqrt(0.8 rows cols / 1000), 2), mask > 0, disparity > 0 and not NaN,
