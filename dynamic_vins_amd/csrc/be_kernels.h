@@ -251,6 +251,7 @@ int  be_launch_solve_batch(const BeSolveArgs* tab_dev, int n_win, int max_n, int
 int be_eval_batch_blocks(int nlm, int nimu);      // workgroups of one window in the batched evaluation launch
 void be_launch_accept_gauge_batch(const BeSolveArgs* stab, const BeGaugeArgs* gtab, int n, hipStream_t s);
 void be_launch_reject_batch(const BeRejectArgs* tab, int n, int max_nlm, hipStream_t s);
+#define BE_MARG_FINISH_LDS (156 * 1024)      // dynamic LDS the finish kernels are allowed: what marg_plan checks be_marg_finish_smem against
 size_t be_marg_finish_smem(int D, int n);
 int be_launch_marg_batch(const BeMargArgs* tab, int n, int max_nlm, int any_imu, int max_D, size_t max_finish_bytes, hipStream_t s);
 void be_launch_shard_finalize(const BeSolveArgs& a, int spec, hipStream_t s);   // after the exchange of a reduce: rank-ordered sums -> Hd / Sc / gvec and the form coefficients qf

@@ -830,10 +830,10 @@ size_t be_marg_finish_smem(int D, int n) { return finish_smem(D, n); }
 int be_launch_marg_batch(const BeMargArgs* tab, int n, int max_nlm, int any_imu, int max_D, size_t max_finish_bytes, hipStream_t s) {
     static DevOnce once;
     if (once.run([] {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(be_marg_finish_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) return 1;
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(be_marg_finish_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BE_MARG_FINISH_LDS) != hipSuccess) return 1;
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(be_marg_lm_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) return 1;
             return 0; })) return -1;
-    if (max_finish_bytes > 156 * 1024 || lm_smem() > 96 * 1024) return -2;
+    if (max_finish_bytes > BE_MARG_FINISH_LDS || lm_smem() > 96 * 1024) return -2;
     if (max_nlm > 0 || any_imu) hipLaunchKernelGGL(be_marg_lm_batch_kernel, dim3(be_marg_chunks(max_nlm) + (any_imu ? 1 : 0), n), dim3(LM_THREADS), lm_smem(), s, tab);
     if (max_nlm > 0) {
         const int NB = (max_D + 1 + 15) / 16, tiles = NB * (NB + 1) / 2;
@@ -845,11 +845,11 @@ int be_launch_marg_batch(const BeMargArgs* tab, int n, int max_nlm, int any_imu,
 int be_launch_marg(const BeMargArgs& a, hipStream_t s) {
     static DevOnce once;
     if (once.run([] {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(be_marg_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) return 1;
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(be_marg_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BE_MARG_FINISH_LDS) != hipSuccess) return 1;
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(be_marg_lm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) return 1;
             return 0; })) return -1;
     const size_t bytes = finish_smem(a.D, a.D - a.m);
-    if (bytes > 156 * 1024 || lm_smem() > 96 * 1024) return -2;
+    if (bytes > BE_MARG_FINISH_LDS || lm_smem() > 96 * 1024) return -2;
     if (a.nlm > 0 || a.nimu > 0) hipLaunchKernelGGL(be_marg_lm_kernel, dim3(be_marg_chunks(a.nlm) + (a.nimu > 0 ? 1 : 0)), dim3(LM_THREADS), lm_smem(), s, a);
     if (a.nlm > 0) {
         const int NB = (a.D + 1 + 15) / 16, tiles = NB * (NB + 1) / 2;
@@ -864,6 +864,6 @@ int be_marg_prepare() {
     if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(be_gauge_kernel)) != hipSuccess) return -1;
     static DevOnce once;      // (the same attributes be_launch_marg sets on its first call)
     return once.run([] {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(be_marg_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) return 1;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(be_marg_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BE_MARG_FINISH_LDS) != hipSuccess) return 1;
         return hipFuncSetAttribute(reinterpret_cast<const void*>(be_marg_lm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess ? 1 : 0; }) ? -1 : 0;
 }

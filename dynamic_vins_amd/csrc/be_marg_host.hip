@@ -48,7 +48,14 @@ int marg_plan(dv_ctx* ctx, MargPlan& pl, int mode, const dv_ba_prior* prior, con
     if (td_in) { pl.td_dim = nd; dim_slot[nd] = BE_NF + 2; dim_comp[nd] = 0; ++nd; }
     pl.D = nd; pl.n = nd - pl.m;
     if (pl.n > BE_MAX_PRIOR || pl.n < 1 || nd > 256) DV_FAIL("dv_marginalize: bad kept size");
-    if (ctx->be.marg_form == DV_MARG_EIGEN && pl.n > 96) DV_FAIL("dv_marginalize: DV_MARG_EIGEN supports at most 96 kept dims (A' and its eigenvectors in LDS), this prior has " + std::to_string(pl.n));
+    // be_marg_finish holds the D x D system, A' and its workspace in LDS, in both forms: refused here, before anything is uploaded (6 dropped dims: n <= 89, 9: 88, 15: 85;
+    // be_marg_eig's own 96 lies above all of them)
+    if (be_marg_finish_smem(pl.D, pl.n) > BE_MARG_FINISH_LDS) {
+        int nmax = pl.n;
+        while (nmax > 1 && be_marg_finish_smem(pl.m + nmax, nmax) > BE_MARG_FINISH_LDS) --nmax;
+        DV_FAIL("dv_marginalize: at most " + std::to_string(nmax) + " kept dims beside " + std::to_string(pl.m) + " dropped ones (the system and A' share " + std::to_string(BE_MARG_FINISH_LDS / 1024) +
+                " KB of LDS), this prior has " + std::to_string(pl.n));
+    }
     if (has_prior) for (int b = 0; b < prior->nblocks; ++b) {
         const dv_ba_prior_block& pb = prior->blocks[b];
         const int d0 = pb.type == 0 ? pl.pose_dim[pb.idx] : pb.type == 1 ? pl.sb_dim[pb.idx] : pb.type == 2 ? pl.ex_dim[pb.idx] : pl.td_dim;
@@ -107,7 +114,7 @@ int marg_enqueue(dv_ctx* ctx, const MargPlan& pl, const BeState* x, double g_nor
         ea.A = outA; ea.b = outb; ea.scal = scal; ea.c0_out = c0_out; ea.spec = (double*)w.eig_spec.p; ea.n = pl.n;
         StageScope sc(ctx, "k_be_marg_eig", s);
         const int rc = be_launch_marg_eig(ea, s);
-        if (rc == -2) DV_FAIL("dv_marginalize: DV_MARG_EIGEN supports at most 96 kept dims");
+        if (rc == -2) DV_FAIL("dv_marginalize: be_marg_eig holds at most 96 kept dims (marg_plan refuses what be_marg_finish cannot hold: fewer)");
         if (rc) DV_FAIL("dv_marginalize: cannot set dynamic LDS size of be_marg_eig");
         DV_CHECK(hipGetLastError());
         w.eig_ran = true;

@@ -417,7 +417,8 @@ int dv_marginalize(dv_ctx* ctx, const dv_ba_problem* P, int mode, dv_ba_prior* o
  *   DV_MARG_INFO   A', b' as the Schur complement leaves them, c0 from a rank-revealing LDL^T that skips pivots <= 1e-8
  *   DV_MARG_EIGEN  A' eigen-decomposed on the device (be_marg_eig: parallel Jacobi), eigenvalues <= 1e-8 zeroed: A', b' projected onto the kept
  *                  eigenvectors and c0 summed over them in ascending order, as the reference's J0 = S^1/2 Q^T, r0 = S^-1/2 Q^T b' (:297-308).
- *                  At most 96 kept dims (the shipped configurations: <= 82); larger priors are refused.  A rank-deficient A_mm is still eliminated by the
+ *                  In BOTH forms the system being reduced and A' share the LDS of one workgroup: at most 89 kept dims beside 6 dropped ones, 88 beside 9, 85 beside 15
+ *                  (the shipped configurations: <= 82); larger priors are refused before anything is uploaded.  A rank-deficient A_mm is still eliminated by the
  *                  LDL^T of DV_MARG_INFO (its pivots are reported by dv_est_get_marg_health). */
 #define DV_MARG_INFO  0
 #define DV_MARG_EIGEN 1
