@@ -124,6 +124,10 @@ SIGNATURES = {
     "dv_viode_frame_collect": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "dv_inst_stack_frame_enqueue": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "dv_inst_stack_frame_collect": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "dv_solo_rect": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dv_solo_check": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "dv_solo_head_enqueue": (C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
+    "dv_solo_head_collect": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
     "dv_inst_track_enqueue_planes": (C.c_int, [_ctx, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "dv_track_unmask_static_planes": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dv_inst_set_disparity": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_double]),

@@ -34,6 +34,68 @@ def mask_stack(stack, mem=DV_MEM_HOST, n_planes=0, kind=DV_STACK_U8, row_stride=
     return dv_mask_stack(int(stack), int(n_planes), int(kind), int(mem), int(row_stride), int(plane_stride), float(threshold), 0)
 
 
+class dv_solo_outputs(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("channels", C.c_int32), ("n_classes", C.c_int32), ("mem", C.c_int32), ("kernel", C.c_void_p * 5), ("cate", C.c_void_p * 5),
+                ("grid", C.c_int32 * 5), ("fh", C.c_int32), ("fw", C.c_int32), ("reserved", C.c_int32), ("feature", C.c_void_p)]
+
+
+class dv_solo_params(C.Structure):
+    _fields_ = [("score_thr", C.c_float), ("mask_thr", C.c_float), ("update_thr", C.c_float), ("nms_sigma", C.c_float), ("nms_pre", C.c_int32), ("max_per_img", C.c_int32),
+                ("nms_kernel", C.c_int32), ("max_candidates", C.c_int32), ("num_grids", C.c_int32 * 5), ("strides", C.c_float * 5),
+                ("rect_x", C.c_int32), ("rect_y", C.c_int32), ("rect_w", C.c_int32), ("rect_h", C.c_int32), ("origin_w", C.c_int32), ("origin_h", C.c_int32)]
+
+
+DV_SOLO_NMS_GAUSSIAN, DV_SOLO_NMS_LINEAR = 0, 1
+
+
+def solo_rect(model_w, model_h, img_w, img_h):
+    """Pipeline::GetXYWHS (det2d/pipeline.cpp:23-48): the image's rectangle (x, y, w, h) inside the network input.  Host code: needs no GPU."""
+    lib = _abi.load()
+    v = [C.c_int(0) for _ in range(4)]
+    if lib.dv_solo_rect(int(model_w), int(model_h), int(img_w), int(img_h), *[C.byref(a) for a in v]) != 0:
+        raise DvinsError(lib.dv_last_error(None).decode())
+    return tuple(a.value for a in v)
+
+
+def solo_outputs(kernels, cates, feature, mem=DV_MEM_HOST, shapes=None):
+    """dv_solo_outputs of a SOLOv2 network's outputs.  Host: float32 C-contiguous numpy arrays, kernels[l] [channels, g, g], cates[l] [n_classes, g, g], feature
+    [channels, fh, fw] (kept alive by the caller).  Device / pinned: raw pointers (int) with shapes = (channels, n_classes, [g per level], fh, fw)."""
+    o = dv_solo_outputs()
+    if shapes is None:
+        for a in list(kernels) + list(cates) + [feature]:
+            assert isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous and a.ndim == 3
+        shapes = (feature.shape[0], cates[0].shape[0], [k.shape[1] for k in kernels], feature.shape[1], feature.shape[2])
+        ptr = lambda a: a.ctypes.data
+    else:
+        ptr = int
+    channels, n_classes, grids, fh, fw = shapes
+    o.n_levels, o.channels, o.n_classes, o.mem, o.fh, o.fw = len(kernels), int(channels), int(n_classes), int(mem), int(fh), int(fw)
+    for l in range(min(len(kernels), 5)):
+        o.kernel[l], o.cate[l], o.grid[l] = ptr(kernels[l]), ptr(cates[l]), int(grids[l])
+    o.feature = ptr(feature)
+    return o
+
+
+def solo_params(score_thr=0.1, mask_thr=0.5, update_thr=0.05, nms_pre=500, max_per_img=100, nms_kernel="gaussian", nms_sigma=2.0, num_grids=(40, 36, 24, 16, 12),
+                strides=(8, 8, 16, 32, 32), max_candidates=2048, rect=(0, 0, 0, 0), origin=(0, 0)):
+    """dv_solo_params; the defaults are the reference's tables (det2d/det2d_parameter.h:30-31) and its KITTI YAML"""
+    p = dv_solo_params()
+    p.score_thr, p.mask_thr, p.update_thr, p.nms_sigma = float(score_thr), float(mask_thr), float(update_thr), float(nms_sigma)
+    p.nms_pre, p.max_per_img, p.max_candidates = int(nms_pre), int(max_per_img), int(max_candidates)
+    p.nms_kernel = {"gaussian": DV_SOLO_NMS_GAUSSIAN, "linear": DV_SOLO_NMS_LINEAR}.get(nms_kernel, nms_kernel)
+    for l in range(min(len(num_grids), 5)):
+        p.num_grids[l], p.strides[l] = int(num_grids[l]), float(strides[l])
+    (p.rect_x, p.rect_y, p.rect_w, p.rect_h), (p.origin_w, p.origin_h) = [int(v) for v in rect], [int(v) for v in origin]
+    return p
+
+
+def solo_check(outputs, params):
+    """the refusals of solo_head_enqueue, without a device: raises DvinsError with the reason"""
+    lib = _abi.load()
+    if lib.dv_solo_check(C.addressof(outputs), C.addressof(params)) != 0:
+        raise DvinsError(lib.dv_last_error(None).decode())
+
+
 FEAT_DTYPE = np.dtype([("id", np.uint32), ("track_cnt", np.int32), ("has_right", np.int32), ("pad_", np.int32),
                        ("left", np.float64, 7), ("right", np.float64, 7)])
 assert FEAT_DTYPE.itemsize == C.sizeof(dv_feat) == 128
@@ -239,6 +301,23 @@ class Context:
         dets = [dict(track_id=int(a.track_id), class_id=int(a.class_id), rect=(int(a.x), int(a.y), int(a.w), int(a.h)), plane=int(planes[i]), mask=None, points=None)
                 for i, a in enumerate(arr[: n.value])]
         return dets, inv.value, mrg.value
+
+    def solo_head_enqueue(self, outputs, params):
+        """the detector's head of one frame (Solov2::GetSegTensor, det2d/solo_head.cpp:410-559) on the ctx's stream: outputs = solo_outputs(...), params = solo_params(...)"""
+        self._solo_keep = (outputs, params)
+        self._check(self.lib.dv_solo_head_enqueue(self.h, C.addressof(outputs), C.addressof(params)))
+
+    def solo_head_collect(self):
+        """-> (labels int32 [n], scores float32 [n], dv_mask_stack of the first min(n, 64) planes — DV_STACK_U8 in the library's device memory —, cells over score_thr)"""
+        labels, scores = np.zeros(128, np.int32), np.zeros(128, np.float32)
+        n, nc, st = C.c_int(0), C.c_int(0), dv_mask_stack()
+        self._check(self.lib.dv_solo_head_collect(self.h, labels.ctypes.data, scores.ctypes.data, 128, C.byref(n), C.byref(nc), C.addressof(st)))
+        return labels[: n.value].copy(), scores[: n.value].copy(), st, nc.value
+
+    def solo_head(self, outputs, params):
+        """solo_head_enqueue + solo_head_collect"""
+        self.solo_head_enqueue(outputs, params)
+        return self.solo_head_collect()
 
     @staticmethod
     def _plane_array(dets):

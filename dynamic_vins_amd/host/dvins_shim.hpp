@@ -659,6 +659,55 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// The detector's head (det2d/solo_head.h, det2d/detector2d.h) on the device: the network's output tensors stay where TensorRT left them and become the instance-mask
+// stack there (dv_solo_head_enqueue / _collect).  ImageInfo = det2d/pipeline.h's; SetImageInfo restates Pipeline::GetXYWHS.
+struct ImageInfo { int origin_h = 0, origin_w = 0, rect_x = 0, rect_y = 0, rect_w = 0, rect_h = 0; };
+inline ImageInfo SetImageInfo(int model_w, int model_h, int img_w, int img_h) {
+    ImageInfo i; i.origin_w = img_w; i.origin_h = img_h;
+    if (dv_solo_rect(model_w, model_h, img_w, img_h, &i.rect_x, &i.rect_y, &i.rect_w, &i.rect_h) != 0) throw std::runtime_error(std::string("SetImageInfo: ") + dv_last_error(nullptr));
+    return i;
+}
+struct SoloSeg { int n = 0, n_candidates = 0; std::vector<int32_t> cate_labels; std::vector<float> cate_scores; dv_mask_stack stack{}; };      // seg_label_out stays on the device: stack
+class Solov2 {
+public:
+    using Ptr = std::shared_ptr<Solov2>;
+    // det2d_para's head parameters (det2d/det2d_parameter.h:30-31,44-51); rect / origin are filled per call from the ImageInfo
+    explicit Solov2(dv_ctx* ctx, const dv_solo_params& para) : ctx_(ctx), para_(para) {}
+    // Solov2::GetSegTensor(outputs, img_info, seg_label_out, cate_labels_out, cate_scores_out) (det2d/solo_head.cpp:410-559): outputs = the eleven tensors in the
+    // reference's order (n_levels kernel maps, n_levels category maps, the mask feature), one memory kind.  Enqueue + Collect, or both at once
+    void GetSegTensorEnqueue(const dv_solo_outputs& outputs, const ImageInfo& img_info) {
+        dv_solo_params p = para_;
+        p.rect_x = img_info.rect_x; p.rect_y = img_info.rect_y; p.rect_w = img_info.rect_w; p.rect_h = img_info.rect_h; p.origin_w = img_info.origin_w; p.origin_h = img_info.origin_h;
+        detail::check(ctx_, dv_solo_head_enqueue(ctx_, &outputs, &p), "GetSegTensor");
+    }
+    SoloSeg GetSegTensorCollect() {
+        SoloSeg s; s.cate_labels.resize(DV_SOLO_MAX_PER_IMG); s.cate_scores.resize(DV_SOLO_MAX_PER_IMG);
+        detail::check(ctx_, dv_solo_head_collect(ctx_, s.cate_labels.data(), s.cate_scores.data(), DV_SOLO_MAX_PER_IMG, &s.n, &s.n_candidates, &s.stack), "GetSegTensor");
+        s.cate_labels.resize(s.n); s.cate_scores.resize(s.n);
+        return s;
+    }
+    SoloSeg GetSegTensor(const dv_solo_outputs& outputs, const ImageInfo& img_info) { GetSegTensorEnqueue(outputs, img_info); return GetSegTensorCollect(); }
+private:
+    dv_ctx* ctx_; dv_solo_params para_;
+};
+class Detector2D {
+public:
+    Detector2D(dv_ctx* ctx, const dv_solo_params& para, int model_w, int model_h, int img_w, int img_h) : solo_(ctx, para), info_(SetImageInfo(model_w, model_h, img_w, img_h)) {}
+    // Detector2D::ForwardTensor behind the network (det2d/detector2d.cpp:273-278): the head, then thread T1's stage on its stack — BuildBoxes2D's rectangles come back from
+    // insts.StackFrameCollect(); a frame without instances enqueues no stage (false).  The COCO -> KITTI naming of BuildBoxes2D stays with the caller: seg.cate_labels
+    bool ForwardHead(const dv_solo_outputs& outputs, InstsFeatManager& insts, SoloSeg* seg_out = nullptr) {
+        SoloSeg s = solo_.GetSegTensor(outputs, info_);
+        const bool any = s.stack.n_planes > 0;
+        if (any) insts.StackFrameEnqueue(s.stack, info_.origin_w, info_.origin_h);
+        if (seg_out) *seg_out = std::move(s);
+        return any;
+    }
+    const ImageInfo& image_info() const { return info_; }
+private:
+    Solov2 solo_; ImageInfo info_;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 class Estimator {
 public:
     using Ptr = std::shared_ptr<Estimator>;

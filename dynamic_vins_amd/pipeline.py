@@ -215,7 +215,7 @@ class DynamicPipeline(Pipeline):
 
     def __init__(self, seq: DynamicSequence, max_cnt=250, min_dist=25, max_iters=10, device=0, use_imu=1, max_dynamic_cnt=50, min_dynamic_dist=5, use_det3d=1,
                  static_inst_threshold=1.0, mask_morphology_size=0, segments=None, est_kw=None, extra_from_disparity=True, ba_stride=1,
-                 static_as_background=False, live_masks=False, mask_stack=False):
+                 static_as_background=False, live_masks=False, mask_stack=False, solo_head=None):
         from .frontend import DV_MODE_SEMANTIC
         # live_masks: `seq` carries label images (a viode.ViodeSequence: seg0, seg1, dyn_keys) and thread T1's stage runs per frame on the device (viode_frame_enqueue /
         # _collect + the key-image entries) instead of reading the sequence's pre-computed masks, detections and key images; same results, bit for bit
@@ -224,6 +224,15 @@ class DynamicPipeline(Pipeline):
         # dynamic key cut from a label-image sequence) through inst_stack_frame_enqueue / _collect and the plane entries; bit for bit the pre-computed path's results
         self.mask_stack, self._stack_in = bool(mask_stack), None
         assert not (live_masks and mask_stack)
+        # solo_head: the detector's head in front of that stack — a callable k -> (dv_solo_outputs, dv_solo_params, ids) supplies the network's eleven output tensors of
+        # frame k (frontend.solo_outputs / solo_params) and ids(labels, scores, stack) -> (track ids, class ids) per plane, the upstream multi-object tracker's answer
+        # (-1 drops a plane).  Context.solo_head_enqueue / _collect fill the stack, which goes down the mask-stack path unchanged; the head of frame k + 1 is enqueued
+        # behind the tracking of frame k.  Refused together with live_masks (and with mask_stack: the head IS the source of the stack)
+        if solo_head is not None and (live_masks or mask_stack):
+            raise ValueError("DynamicPipeline: solo_head cannot be combined with live_masks or mask_stack")
+        if solo_head is not None and not callable(solo_head):
+            raise ValueError("DynamicPipeline: solo_head must be a callable k -> (outputs, params, ids)")
+        self.solo_head, self._solo_enq, self._solo_ids, self._solo_blank = solo_head, None, None, None
         self.extra_from_disparity = extra_from_disparity      # False: the detections' own `points` are handed through (the caller ran the extra-point pipeline)
         self.seq, self.host = seq, None
         c = make_cam(*sim.cam_tuple(seq.cam))
@@ -294,6 +303,47 @@ class DynamicPipeline(Pipeline):
             ctx.inst_stack_frame_enqueue(q["stacks"][k + 1].data_ptr(), **kw(k + 1))
             self._live_enq = k + 1
 
+    def _solo_enqueue_head(self, k):
+        o, p, ids = self.solo_head(k)
+        self.ctx.solo_head_enqueue(o, p)
+        self._solo_enq, self._solo_ids = k, ids
+
+    def _enqueue_solo(self, k):
+        """the mask-stack path on the head's own stack (Detector2D::ForwardTensor behind the network, det2d/detector2d.cpp:273-278, then ImageProcessor::Run's detector branch)"""
+        from .frontend import DV_MEM_DEVICE as DEV
+        from . import viode
+        s, ctx = self.seq, self.ctx
+        l, r = s.frames[k]
+        if self._solo_enq != k:
+            self._solo_enqueue_head(k)
+        ids, self._solo_enq = self._solo_ids, None
+        labels, scores, st, _ = ctx.solo_head_collect()
+        dets = []
+        if st.n_planes:
+            ctx.inst_stack_frame_enqueue(st)
+            dets, inv, _ = ctx.inst_stack_frame_collect(getattr(s, "min_inst_size", viode.MIN_INST_SIZE))
+            tid, cid = ids(labels, scores, st)
+            dets = [dict(d, track_id=int(tid[d["plane"]]), class_id=int(cid[d["plane"]])) for d in dets]
+            dets = [d for d in dets if d["track_id"] >= 0 and d["class_id"] >= 0]
+            if self.static_as_background and len(dets):
+                ctx.track_unmask_static_planes(dets, self.static_ids_for(k), st)
+        else:          # a frame without instances: nothing is masked, no object is tracked
+            if self._solo_blank is None:
+                import torch
+                self._solo_blank = torch.full((s.h, s.w), 255, dtype=torch.uint8, device=l.device)
+                torch.cuda.synchronize()
+            inv = self._solo_blank.data_ptr()
+        ctx.track_stereo_enqueue(l.data_ptr(), r.data_ptr(), s.times[k], inv, self.mode, DEV)
+        if self.extra_from_disparity and len(getattr(s, "disp_dev", [])):
+            ctx.inst_set_disparity(s.disp_dev[k].data_ptr(), s.baseline, DEV)
+        if st.n_planes:
+            ctx.inst_track_enqueue_planes(s.times[k], dets, st)
+        else:
+            ctx.inst_track_enqueue(s.times[k], [], None)
+        self.enqueued = True
+        if k + 1 < len(s.frames):          # the head of the next frame behind this frame's tracking: its planes go to the other of the two sets
+            self._solo_enqueue_head(k + 1)
+
     def _enqueue_live(self, k):
         from . import viode
         s, ctx = self.seq, self.ctx
@@ -318,6 +368,8 @@ class DynamicPipeline(Pipeline):
     def _enqueue(self, k):
         if self.mask_stack:
             return self._enqueue_stack(k)
+        if self.solo_head is not None:
+            return self._enqueue_solo(k)
         if self.live_masks:
             return self._enqueue_live(k)
         l, r = self.seq.frames[k]

@@ -202,6 +202,60 @@ typedef struct dv_mask_stack {
 #define DV_STACK_REMAP_MERGED 1
 int dv_inst_stack_frame_enqueue(dv_ctx* ctx, const dv_mask_stack* stack, int w, int h, int flags);
 int dv_inst_stack_frame_collect(dv_ctx* ctx, int min_inst_size, struct dv_inst_det* dets, int32_t* planes, int cap, int* n_dets, const uint8_t** inv_mask_dev, const uint8_t** merge_mask_dev);
+/* The detector's HEAD for ONE frame: the SOLOv2 network's output tensors -> the instance-mask stack above, on the device.  It restates Solov2::GetSegTensor
+ * (det2d/solo_head.cpp:410-559) with Solov2::MatrixNMS (det2d/solo_head.cpp:31-71), the step Detector2D::ForwardTensor runs behind the network
+ * (det2d/detector2d.cpp:245-280), AS THE REFERENCE EVALUATES IT; the network itself (TensorRT) stays with the caller, and so does BuildBoxes2D's COCO -> KITTI naming.
+ * dv_solo_outputs: per level, in the order the reference concatenates them (outputs[0 .. n_levels - 1], then the category maps), the kernel map [channels, g, g], the
+ * category map [n_classes, g, g] and g; then the mask feature [channels, fh, fw].  float32, tightly packed, one memory kind (DV_MEM_DEVICE / DV_MEM_PINNED read in
+ * place and valid until the frame is collected; DV_MEM_HOST staged by the enqueue).  channels 1..256, n_classes 1..128, g 1..64, fh * fw <= 2^20.
+ * The rule, step by step:
+ *   candidates   the cells with cate > score_thr (strict) in nonzero() order: row-major over [cell, class], cells concatenated level by level (an ordered scan).
+ *                More than max_candidates of them: the frame FAILS (collect returns < 0 with a message, no planes) — never a silent truncation.
+ *   pixel floor  stride(cell) = strides[i] for the first i with cell < num_grids[0]^2 + .. + num_grids[i]^2, else 1, where `cell` is the index into the CONCATENATED
+ *                cells and i runs over n_levels entries.  The boundaries depend only on num_grids[], never on the levels' own g: the reference concatenates in the order
+ *                of kTensorQueueShapes (grids 12, 16, 24, 36, 40) and builds the boundaries from kSoloNumGrids (40, 36, 24, 16, 12), so with its own tables the first
+ *                1600 cells get stride 8 whatever level they came from (solo_head.cpp:24-28,454-465).  Kept as it is.
+ *   masks        seg = sigmoid(kernel . feature) (float32 in, float32 accumulate), mask = seg > mask_thr, sum_mask = the mask's pixels as float; kept when
+ *                sum_mask > stride; score = cate * (sum(seg * mask) / sum_mask).
+ *   sort         descending, the first nms_pre; equal scores in candidate order (the reference's argsort leaves ties open).
+ *   Matrix NMS   iou = inter / (sum_i + sum_j - inter) from the masks' inner products, upper triangle, same-label pairs only; compensation = the column maximum; decay =
+ *                the minimum over ALL rows i (not only i < j) of exp(-sigma iou^2) / exp(-sigma comp_i^2) (DV_SOLO_NMS_GAUSSIAN) or (1 - iou) / (1 - comp_i)
+ *                (DV_SOLO_NMS_LINEAR), NaN carried as the tensor library's min carries it.
+ *   second sort  kept when score * decay >= update_thr; descending, the first max_per_img; ties in the order of the first sort.
+ *   resampling   bilinear align_corners = true to (4 fh, 4 fw), crop [rect_y : rect_y + rect_h, rect_x : rect_x + rect_w], bilinear align_corners = true to
+ *                (origin_h, origin_w), plane = value > mask_thr.  Source coordinates and weights in float32 as upsample_bilinear2d forms them (scale = (in - 1) / (out - 1),
+ *                src = scale * dst, weights from the fractional part); the 4 x intermediate is never stored.
+ * No candidate, none over the pixel floor, none over update_thr: ZERO planes, not an error (the reference's three early returns).
+ * Limits: max_candidates <= 4096, nms_pre <= 512, max_per_img <= 128.  DV_STACK_MAX_PLANES is 64 while the reference's YAML asks for max_per_img 100: collect reports all
+ * n survivors (labels, scores, planes in memory) but the dv_mask_stack it fills names the first min(n, 64) planes — the highest scores.
+ * dv_solo_rect: Pipeline::GetXYWHS (det2d/pipeline.cpp:23-48), the image's rectangle inside the network input, with its round-up to even.  Host code, no ctx.
+ * dv_solo_check: the refusals of dv_solo_head_enqueue without a device (0, or < 0 with dv_last_error(NULL)).
+ * _enqueue: everything on the ctx's stream into buffers the LIBRARY owns; the output planes exist twice and alternate as dv_inst_stack_frame_*'s buffers do, so frame
+ * k + 1's head may be enqueued behind frame k's tracking.  One frame may be in flight.  Counts stay on the device between the kernels.
+ * _collect: waits, returns n (all survivors), *n_candidates, labels[min(n, cap)] / scores[min(n, cap)] (the frame's only device -> host traffic, through pinned memory) and
+ * fills *stack: DV_STACK_U8 (0 / 1), DV_MEM_DEVICE, rows of origin_w bytes padded to a multiple of 4 (padding zero), n_planes = min(n, 64) — 0 for a frame without
+ * instances, which dv_inst_stack_frame_enqueue refuses: skip the stage for such a frame. */
+#define DV_SOLO_MAX_LEVELS 5
+#define DV_SOLO_NMS_GAUSSIAN 0
+#define DV_SOLO_NMS_LINEAR 1
+#define DV_SOLO_MAX_CANDIDATES 4096
+#define DV_SOLO_MAX_NMS_PRE 512
+#define DV_SOLO_MAX_PER_IMG 128
+typedef struct dv_solo_outputs {
+    int32_t n_levels /* 1..5 */, channels, n_classes, mem /* DV_MEM_* */;
+    const float* kernel[DV_SOLO_MAX_LEVELS]; const float* cate[DV_SOLO_MAX_LEVELS]; int32_t grid[DV_SOLO_MAX_LEVELS];
+    int32_t fh, fw, reserved; const float* feature;
+} dv_solo_outputs;
+typedef struct dv_solo_params {
+    float score_thr, mask_thr, update_thr, nms_sigma;
+    int32_t nms_pre, max_per_img, nms_kernel /* DV_SOLO_NMS_* */, max_candidates;
+    int32_t num_grids[DV_SOLO_MAX_LEVELS]; float strides[DV_SOLO_MAX_LEVELS];
+    int32_t rect_x, rect_y, rect_w, rect_h, origin_w, origin_h;
+} dv_solo_params;
+int dv_solo_rect(int model_w, int model_h, int img_w, int img_h, int* rect_x, int* rect_y, int* rect_w, int* rect_h);
+int dv_solo_check(const dv_solo_outputs* out, const dv_solo_params* par);
+int dv_solo_head_enqueue(dv_ctx* ctx, const dv_solo_outputs* out, const dv_solo_params* par);
+int dv_solo_head_collect(dv_ctx* ctx, int32_t* labels, float* scores, int cap, int* n, int* n_candidates, dv_mask_stack* stack);
 /* cv::cvtColor(BGR2GRAY) on 8-bit images: (B 1868 + G 9617 + R 4899 + 8192) >> 14; gray is w x h, tightly packed */
 int dv_bgr2gray(dv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, uint8_t* gray, int mem);
 /* cv::remap(src, dst, map1, map2, INTER_LINEAR) — BORDER_CONSTANT 0 — with the fixed-point maps cv::initUndistortRectifyMap(..., CV_16SC2, ...)
