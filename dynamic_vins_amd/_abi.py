@@ -128,6 +128,13 @@ SIGNATURES = {
     "dv_solo_check": (C.c_int, [C.c_void_p, C.c_void_p]),
     "dv_solo_head_enqueue": (C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
     "dv_solo_head_collect": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
+    "dv_mot_check": (C.c_int, [C.c_void_p]),
+    "dv_mot_config": (C.c_int, [_ctx, C.c_void_p]),
+    "dv_mot_reset": (C.c_int, [_ctx]),
+    "dv_mot_update_enqueue": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "dv_mot_update_collect": (C.c_int, [_ctx, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dv_mot_get_tracks": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "dv_mot_assign": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dv_inst_track_enqueue_planes": (C.c_int, [_ctx, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "dv_track_unmask_static_planes": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dv_inst_set_disparity": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_double]),

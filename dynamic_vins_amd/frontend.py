@@ -89,6 +89,31 @@ def solo_params(score_thr=0.1, mask_thr=0.5, update_thr=0.05, nms_pre=500, max_p
     return p
 
 
+class dv_mot_params(C.Structure):
+    _fields_ = [("n_init", C.c_int32), ("max_age", C.c_int32), ("budget", C.c_int32), ("feat_dim", C.c_int32), ("max_tracks", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+# dv_mot_track: a row of Context.mot_tracks()
+MOT_TRACK_DTYPE = np.dtype([("x", np.float32, 7), ("p_diag", np.float32, 7), ("rect", np.float32, 4), ("state", np.int32), ("id", np.int32), ("hits", np.int32),
+                            ("time_since_update", np.int32), ("n_feats", np.int32), ("reserved", np.int32)])
+assert MOT_TRACK_DTYPE.itemsize == 96
+DV_MOT_MAX_TRACKS, DV_MOT_MAX_DETS = 128, 64
+
+
+def mot_params(n_init=3, max_age=5, budget=100, feat_dim=512, max_tracks=128):
+    """dv_mot_params; the defaults are the reference's tracking YAML (mot/mot_parameter.cpp)"""
+    p = dv_mot_params()
+    p.n_init, p.max_age, p.budget, p.feat_dim, p.max_tracks = int(n_init), int(max_age), int(budget), int(feat_dim), int(max_tracks)
+    return p
+
+
+def mot_check(params):
+    """the refusals of mot_config, without a device: raises DvinsError with the reason"""
+    lib = _abi.load()
+    if lib.dv_mot_check(C.addressof(params) if params is not None else None) != 0:
+        raise DvinsError(lib.dv_last_error(None).decode())
+
+
 def solo_check(outputs, params):
     """the refusals of solo_head_enqueue, without a device: raises DvinsError with the reason"""
     lib = _abi.load()
@@ -144,11 +169,15 @@ class Context:
         if not self.h:
             raise DvinsError(self.lib.dv_last_error(None).decode())
         self._out = np.zeros(_abi.DV_MAX_FEATS, FEAT_DTYPE)
+        self._mot_par, self._mot_n, self._mot_keep, self._mot_pin = None, 0, None, None
 
     def close(self):
         if getattr(self, "h", None):
             self.lib.dv_destroy(self.h)
             self.h = None
+            if getattr(self, "_mot_pin", None):
+                self.lib.dv_pinned_free(self._mot_pin)
+                self._mot_pin = None
 
     def __del__(self):
         try:
@@ -313,6 +342,75 @@ class Context:
         n, nc, st = C.c_int(0), C.c_int(0), dv_mask_stack()
         self._check(self.lib.dv_solo_head_collect(self.h, labels.ctypes.data, scores.ctypes.data, 128, C.byref(n), C.byref(nc), C.addressof(st)))
         return labels[: n.value].copy(), scores[: n.value].copy(), st, nc.value
+
+    # ---- the multi-object tracker (DeepSORT::update, mot/deep_sort.cpp:72-139): detections + embeddings -> track ids, table and galleries resident ----
+    def mot_config(self, params=None, **kw):
+        """allocates and resets the tracker; params = mot_params(...) or its keywords"""
+        self._mot_par = params if params is not None else mot_params(**kw)
+        self._check(self.lib.dv_mot_config(self.h, C.addressof(self._mot_par)))
+
+    def mot_reset(self):
+        self._check(self.lib.dv_mot_reset(self.h))
+
+    def mot_update_enqueue(self, rects, feats, n=None, mem=DV_MEM_HOST):
+        """one frame on the ctx's stream.  rects [n, 4] x, y, w, h and feats [n, feat_dim] (L2-normalised rows), float32.  mem = DV_MEM_HOST: host arrays, staged.
+        DV_MEM_DEVICE / DV_MEM_PINNED: feats is a pointer (int) read in place and n is required; rects is a pointer of either in-place kind, or a host array, which goes
+        through a small pinned buffer of the ctx (the rectangles come from inst_stack_frame_collect on the host, the embeddings from the ReID network on the device).
+        n = 0 is the reference's "tracker not called": nothing predicts or ages"""
+        if mem == DV_MEM_HOST:
+            rects = np.ascontiguousarray(rects, np.float32).reshape(-1, 4)
+            n = len(rects) if n is None else int(n)
+            if n:
+                if self._mot_par is None:
+                    raise DvinsError("mot_update_enqueue: mot_config first")
+                feats = np.ascontiguousarray(feats, np.float32)
+                if feats.shape != (n, self._mot_par.feat_dim):
+                    raise ValueError(f"feats must be [{n}, {self._mot_par.feat_dim}]")
+        else:
+            if n is None:
+                raise ValueError("mot_update_enqueue: n is required with device or pinned pointers")
+            n = int(n)
+            if n and not isinstance(feats, (int, np.integer)):
+                raise ValueError("mot_update_enqueue: feats must be a pointer (int) with device or pinned memory")
+            if n and not isinstance(rects, (int, np.integer)):
+                r = np.ascontiguousarray(rects, np.float32).reshape(-1, 4)
+                if len(r) != n or n > DV_MOT_MAX_DETS:
+                    raise ValueError(f"rects must be [{n}, 4], n <= {DV_MOT_MAX_DETS}")
+                if self._mot_pin is None:
+                    self._mot_pin = self.lib.dv_pinned_alloc(DV_MOT_MAX_DETS * 16)
+                    if not self._mot_pin:
+                        raise DvinsError("mot_update_enqueue: no pinned memory")
+                C.memmove(self._mot_pin, r.ctypes.data, n * 16)
+                rects = int(self._mot_pin)
+        self._mot_keep = (rects, feats)
+        self._check(self.lib.dv_mot_update_enqueue(self.h, _ptr(rects) if n else None, _ptr(feats) if n else None, n, mem))
+        self._mot_n = n
+
+    def mot_update_collect(self):
+        """-> (track_id int32 [n]: the Confirmed track updated with each detection, else -1; tracks in the table; Confirmed ones)"""
+        ids, nt, nc = np.full(max(self._mot_n, 1), -1, np.int32), C.c_int(0), C.c_int(0)
+        n, self._mot_n, self._mot_keep = self._mot_n, 0, None
+        self._check(self.lib.dv_mot_update_collect(self.h, ids.ctypes.data, C.byref(nt), C.byref(nc)))
+        return ids[:n].copy(), nt.value, nc.value
+
+    def mot_update(self, rects, feats, n=None, mem=DV_MEM_HOST):
+        """mot_update_enqueue + mot_update_collect"""
+        self.mot_update_enqueue(rects, feats, n, mem)
+        return self.mot_update_collect()
+
+    def mot_tracks(self):
+        """the track table in order (MOT_TRACK_DTYPE rows): for tests and the shim"""
+        out, n = np.zeros(DV_MOT_MAX_TRACKS, MOT_TRACK_DTYPE), C.c_int(0)
+        self._check(self.lib.dv_mot_get_tracks(self.h, out.ctypes.data, len(out), C.byref(n)))
+        return out[: n.value].copy()
+
+    def mot_assign(self, cost):
+        """the device Munkres alone (HungarianAlgorithm::Solve, mot/hungarian.cpp) on a [rows <= 128, cols <= 64] cost matrix -> column per row, or -1"""
+        cost = np.ascontiguousarray(cost, np.float32)
+        rows, cols = cost.shape
+        out = np.full(max(rows, 1), -1, np.int32)
+        self._check(self.lib.dv_mot_assign(self.h, cost.ctypes.data if cost.size else None, rows, cols, out.ctypes.data))
+        return out[:rows].copy()
 
     def solo_head(self, outputs, params):
         """solo_head_enqueue + solo_head_collect"""

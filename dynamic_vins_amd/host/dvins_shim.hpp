@@ -708,6 +708,71 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// The multi-object tracker (mot/deep_sort.h) on the device: dv_mot_update_enqueue / _collect.  The reference's update(detections, ori_img) extracts the embeddings from
+// cv::Mat crops itself; the shim has no crops, so the caller's ReID network runs first and hands its [n, feat_dim] float32 output (L2-normalised rows, mot/reid_net.cpp)
+// as a pointer: feat_mem = DV_MEM_HOST, or DV_MEM_DEVICE / DV_MEM_PINNED (read in place until the collect).  The rectangles come from the detections on the host
+// and travel through a small pinned buffer beside in-place embeddings.  track_id = -1: no Confirmed track was updated with the detection in this frame.
+class DeepSORT {
+public:
+    using Ptr = std::shared_ptr<DeepSORT>;
+    // mot_para's kTrackingNInit, kTrackingMaxAge, kBudget, kFeatDim (mot/mot_parameter.cpp) and the table's capacity
+    DeepSORT(dv_ctx* ctx, const dv_mot_params& para) : ctx_(ctx), para_(para) {
+        if (dv_mot_check(&para) != 0) throw std::runtime_error(std::string("DeepSORT: ") + dv_last_error(nullptr));
+        detail::check(ctx_, dv_mot_config(ctx_, &para), "DeepSORT");
+    }
+    DeepSORT(const DeepSORT&) = delete;
+    DeepSORT& operator=(const DeepSORT&) = delete;
+    ~DeepSORT() { if (pinned_) dv_pinned_free(pinned_); }
+    void reset() { detail::check(ctx_, dv_mot_reset(ctx_), "DeepSORT::reset"); }
+    // rects: x, y, width, height per detection (Box2D::rect)
+    void update_enqueue(const std::vector<std::array<float, 4>>& rects, const float* feats, int feat_mem = DV_MEM_DEVICE) {
+        const int n = (int)rects.size();
+        if (n > DV_STACK_MAX_PLANES) throw std::runtime_error("DeepSORT::update: more than 64 detections");
+        const float* r = n ? rects[0].data() : nullptr;
+        if (n && feat_mem != DV_MEM_HOST) {
+            if (!pinned_) pinned_ = static_cast<float*>(dv_pinned_alloc(DV_STACK_MAX_PLANES * 4 * sizeof(float)));
+            if (!pinned_) throw std::runtime_error("DeepSORT::update: no pinned memory");
+            std::memcpy(pinned_, r, (size_t)n * 4 * sizeof(float));
+            r = pinned_;
+        }
+        detail::check(ctx_, dv_mot_update_enqueue(ctx_, r, n ? feats : nullptr, n, feat_mem), "DeepSORT::update");
+        n_ = n;
+    }
+    std::vector<int32_t> update_collect() {
+        std::vector<int32_t> ids((size_t)std::max(n_, 1), -1);
+        detail::check(ctx_, dv_mot_update_collect(ctx_, ids.data(), &n_tracks_, &n_confirmed_), "DeepSORT::update");
+        ids.resize((size_t)n_); n_ = 0;
+        return ids;
+    }
+    std::vector<int32_t> update(const std::vector<std::array<float, 4>>& rects, const float* feats, int feat_mem = DV_MEM_DEVICE) { update_enqueue(rects, feats, feat_mem); return update_collect(); }
+    // InstsFeatManager::AddInstancesByTracking (front_end/dynamic_tracker.cpp:791-828) on the stack stage's detections: every detection gets its track id, those without a
+    // Confirmed track leave dets and planes (the reference builds instances from the tracker's answer only).  A frame without detections does not reach the tracker
+    void AddInstancesByTracking(std::vector<dv_inst_det>& dets, std::vector<int32_t>& planes, const float* feats, int feat_mem = DV_MEM_DEVICE) {
+        if (dets.empty()) return;
+        std::vector<std::array<float, 4>> rects(dets.size());
+        for (size_t i = 0; i < dets.size(); ++i) rects[i] = {(float)dets[i].x, (float)dets[i].y, (float)dets[i].w, (float)dets[i].h};
+        const std::vector<int32_t> ids = update(rects, feats, feat_mem);
+        size_t m = 0;
+        for (size_t i = 0; i < dets.size(); ++i) {
+            if (ids[i] < 0) continue;
+            dets[m] = dets[i]; dets[m].track_id = (uint32_t)ids[i];
+            if (i < planes.size()) planes[m] = planes[i];
+            ++m;
+        }
+        dets.resize(m); if (planes.size() > m) planes.resize(m);
+    }
+    std::vector<dv_mot_track> tracks() {
+        std::vector<dv_mot_track> t(DV_MOT_MAX_TRACKS); int n = 0;
+        detail::check(ctx_, dv_mot_get_tracks(ctx_, t.data(), (int)t.size(), &n), "DeepSORT::tracks");
+        t.resize((size_t)n);
+        return t;
+    }
+    int n_tracks() const { return n_tracks_; } int n_confirmed() const { return n_confirmed_; }
+private:
+    dv_ctx* ctx_; dv_mot_params para_; float* pinned_ = nullptr; int n_ = 0, n_tracks_ = 0, n_confirmed_ = 0;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 class Estimator {
 public:
     using Ptr = std::shared_ptr<Estimator>;

@@ -215,7 +215,7 @@ class DynamicPipeline(Pipeline):
 
     def __init__(self, seq: DynamicSequence, max_cnt=250, min_dist=25, max_iters=10, device=0, use_imu=1, max_dynamic_cnt=50, min_dynamic_dist=5, use_det3d=1,
                  static_inst_threshold=1.0, mask_morphology_size=0, segments=None, est_kw=None, extra_from_disparity=True, ba_stride=1,
-                 static_as_background=False, live_masks=False, mask_stack=False, solo_head=None):
+                 static_as_background=False, live_masks=False, mask_stack=False, solo_head=None, mot=None):
         from .frontend import DV_MODE_SEMANTIC
         # live_masks: `seq` carries label images (a viode.ViodeSequence: seg0, seg1, dyn_keys) and thread T1's stage runs per frame on the device (viode_frame_enqueue /
         # _collect + the key-image entries) instead of reading the sequence's pre-computed masks, detections and key images; same results, bit for bit
@@ -233,12 +233,25 @@ class DynamicPipeline(Pipeline):
         if solo_head is not None and not callable(solo_head):
             raise ValueError("DynamicPipeline: solo_head must be a callable k -> (outputs, params, ids)")
         self.solo_head, self._solo_enq, self._solo_ids, self._solo_blank = solo_head, None, None, None
+        # mot: the multi-object tracker on the device (DeepSORT::update, mot/deep_sort.cpp:72-139) behind the stack stage — (feats, params): feats(k, dets, stack) ->
+        # the caller's ReID network on the frame's crops, an [n, feat_dim] float32 device tensor (or a device pointer) with L2-normalised rows, one per detection the
+        # stack stage reports after the class filter, in that order; params = the keywords of frontend.mot_params.  Track ids then come from Context.mot_update_* in place
+        # of the sequence's / of ids(), which may return class ids alone; a detection without a Confirmed track (-1) is dropped, as AddInstancesByTracking leaves it out.
+        # Only where detections come from a stack: refused with pre-computed masks and with live_masks
+        if mot is not None:
+            if live_masks or not (mask_stack or solo_head is not None):
+                raise ValueError("DynamicPipeline: mot needs mask_stack=True or solo_head; it cannot be combined with pre-computed masks or live_masks")
+            if not (isinstance(mot, (tuple, list)) and len(mot) == 2 and callable(mot[0]) and isinstance(mot[1], dict)):
+                raise ValueError("DynamicPipeline: mot must be (callable (k, dets, stack) -> feats, dict of mot_params keywords)")
+        self.mot, self._mot_keep = mot, None
         self.extra_from_disparity = extra_from_disparity      # False: the detections' own `points` are handed through (the caller ran the extra-point pipeline)
         self.seq, self.host = seq, None
         c = make_cam(*sim.cam_tuple(seq.cam))
         self.cam_c, self.cam1_c = c, make_cam(*sim.cam_tuple(seq.cam1))
         self.ctx = Context(width=seq.w, height=seq.h, max_cnt=max_cnt, min_dist=min_dist, cam0=c, cam1=self.cam1_c, device=device, mask_morphology_size=mask_morphology_size)
         self.ctx.inst_config(max_dynamic_cnt, min_dynamic_dist, use_det3d)
+        if self.mot is not None:
+            self.ctx.mot_config(**self.mot[1])
         self.est_kw = dict(use_imu=use_imu, stereo=1, max_iters=max_iters, ric=seq.rig["est_ric"], tic=seq.rig["est_tic"], dynamic=1, use_det3d=use_det3d,
                            static_inst_threshold=static_inst_threshold, use_line=int(segments is not None), **seq.noise)
         self.est_kw.update(est_kw or {})
@@ -281,6 +294,22 @@ class DynamicPipeline(Pipeline):
                 self._stack_in = dict(stacks=stacks, track_ids=[np.array(keys, np.int32)] * len(stacks), class_ids=[np.zeros(len(keys), np.int32)] * len(stacks), min_inst_size=viode.MIN_INST_SIZE)
         return self._stack_in
 
+    def _mot_ids(self, k, dets, stack):
+        """dets (class filter applied) -> the same with track_id from the device tracker, those without a Confirmed track dropped.  A frame without detections does not
+        reach the tracker (front_end/dynamic_tracker.cpp:795-796)"""
+        from .frontend import DV_MEM_DEVICE as DEV
+        if not len(dets):
+            return dets
+        feats = self.mot[0](k, dets, stack)
+        if hasattr(feats, "data_ptr"):
+            import torch
+            if feats.dtype != torch.float32 or tuple(feats.shape) != (len(dets), int(self.mot[1].get("feat_dim", 512))) or not feats.is_contiguous():
+                raise ValueError("DynamicPipeline: mot feats must be a contiguous float32 [n, feat_dim] tensor")
+            torch.cuda.current_stream().synchronize()      # the caller's network ran on the tensor library's stream
+            self._mot_keep, feats = feats, feats.data_ptr()
+        ids, _, _ = self.ctx.mot_update(np.array([d["rect"] for d in dets], np.float32), int(feats), n=len(dets), mem=DEV)
+        return [dict(d, track_id=int(i)) for d, i in zip(dets, ids) if i >= 0]
+
     def _enqueue_stack(self, k):
         from .frontend import DV_MEM_DEVICE as DEV
         s, ctx, q = self.seq, self.ctx, self.stack_input()
@@ -291,6 +320,8 @@ class DynamicPipeline(Pipeline):
         self._live_enq = None
         dets, inv, _ = ctx.inst_stack_frame_collect(q["min_inst_size"])
         dets = [dict(d, track_id=int(q["track_ids"][k][d["plane"]]), class_id=int(q["class_ids"][k][d["plane"]])) for d in dets]
+        if self.mot is not None:          # the class filter first (image_process.cpp:217-232), then the device tracker's ids
+            dets = self._mot_ids(k, [d for d in dets if d["class_id"] >= 0], q["stacks"][k])
         dets = [d for d in dets if d["track_id"] >= 0 and d["class_id"] >= 0]          # the upstream tracker's answer; -1 drops the plane
         if self.static_as_background and len(dets):
             ctx.track_unmask_static_planes(dets, self.static_ids_for(k), q["stacks"][k].data_ptr(), **kw(k))
@@ -322,8 +353,13 @@ class DynamicPipeline(Pipeline):
         if st.n_planes:
             ctx.inst_stack_frame_enqueue(st)
             dets, inv, _ = ctx.inst_stack_frame_collect(getattr(s, "min_inst_size", viode.MIN_INST_SIZE))
-            tid, cid = ids(labels, scores, st)
-            dets = [dict(d, track_id=int(tid[d["plane"]]), class_id=int(cid[d["plane"]])) for d in dets]
+            if self.mot is not None:          # ids() may return the class ids alone
+                res = ids(labels, scores, st)
+                cid = res[1] if isinstance(res, tuple) else res
+                dets = self._mot_ids(k, [d for d in (dict(d, class_id=int(cid[d["plane"]])) for d in dets) if d["class_id"] >= 0], st)
+            else:
+                tid, cid = ids(labels, scores, st)
+                dets = [dict(d, track_id=int(tid[d["plane"]]), class_id=int(cid[d["plane"]])) for d in dets]
             dets = [d for d in dets if d["track_id"] >= 0 and d["class_id"] >= 0]
             if self.static_as_background and len(dets):
                 ctx.track_unmask_static_planes(dets, self.static_ids_for(k), st)

@@ -256,6 +256,62 @@ int dv_solo_rect(int model_w, int model_h, int img_w, int img_h, int* rect_x, in
 int dv_solo_check(const dv_solo_outputs* out, const dv_solo_params* par);
 int dv_solo_head_enqueue(dv_ctx* ctx, const dv_solo_outputs* out, const dv_solo_params* par);
 int dv_solo_head_collect(dv_ctx* ctx, int32_t* labels, float* scores, int cap, int* n, int* n_candidates, dv_mask_stack* stack);
+/* The MULTI-OBJECT TRACKER between the detector and the object tracker: a frame's detection rectangles and appearance embeddings -> a track id per detection, as
+ * InstsFeatManager::AddInstancesByTracking (front_end/dynamic_tracker.cpp:791-828) gets them from DeepSORT::update (mot/deep_sort.cpp:72-139).  Track table and appearance
+ * galleries stay in HBM between frames.  The ReID network (mot/reid_net.cpp, mot/extractor.cpp) stays with the caller: feats is its output, [n, feat_dim] float32 rows
+ * already L2-normalised as ReIdNetImpl::forward leaves them (never renormalised here).  rects_xywh: [n, 4] float32 x, y, width, height (Box2D::rect).
+ * The filter is cv::KalmanFilter(7, 4, 0), CV_32F (mot/kalman_tracker.cpp:31-51): state [cx, cy, s = area, r = w / h, vcx, vcy, vs], constant-velocity transition,
+ * H = the 4 x 7 identity, Q = 1e-2 I, R = 1e-1 I, P0 = I; rect(): w = sqrt(s r), h = s / w, x = cx - w / 2, y = cy - h / 2 (:20-28).  predict / correct are restated from
+ * OpenCV 3.4 video/src/kalman.cpp (unpinned): x' = A x, P' = A P A^T + Q; S = H P' H^T + R, K = (S^-1 H P')^T, x = x' + K (z - H x'), P = P' - K H P'.  Evaluated in
+ * float32; the 4 x 4 solve is Gaussian elimination with partial pivoting where OpenCV takes DECOMP_SVD (DESIGN.md has the measured distance to a float64 evaluation).
+ * A frame with n = 0 does not reach the reference's tracker at all (dynamic_tracker.cpp:795-796): accepted, it predicts and ages NOTHING.  Otherwise, step by step:
+ *   predict      every track: ++time_since_update, the filter's predict (kalman_tracker.cpp:63-67, tracker_manager.h:40-44).
+ *   remove_nan   tracks whose rect() has a NaN component are erased, order kept (tracker_manager.h:46-52).
+ *   stage 1      rows = the Confirmed tracks in table order, columns = all detections.  iou_dist = 1 - RectIou (deep_sort.cpp:27-35: cv::Rect2f arithmetic, the overlap
+ *                empty when its width or height is <= 0, 0 when the union is < DBL_EPSILON); feat = min over the track's stored embeddings g of 1 - g . f
+ *                (feature_metric.h:59-61); cost = feat, INVALID_DIST = 1000 where iou_dist > 0.8f or feat > 0.2f (deep_sort.cpp:99).  HungarianAlgorithm::Solve on the costs
+ *                widened to double (tracker_manager.cpp:20-50); an assigned pair with cost > 100 is dropped.
+ *   stage 2      rows = the tracks stage 1 left unmatched, in their order, then the Tentative tracks in table order (tracker_manager.h:89-97); columns = the detections
+ *                still unmatched, ascending.  cost = iou_dist, 1000 where > 0.7f (deep_sort.cpp:105-119).  Same solve, same drop.  A Confirmed track whose appearance gate
+ *                failed can be matched here.
+ *   miss         every track still unmatched: Tentative -> Deleted, else Deleted when time_since_update > max_age (kalman_tracker.cpp:90-96).
+ *   update       every matched track, stage-1 pairs by row, then stage-2 pairs by row: time_since_update = 0, ++hits, Tentative with hits > n_init -> Confirmed with the next
+ *                id of a counter that starts at 1 (ONE PER TRACKER here; one process-wide static in the reference), then correct with z = [x + w/2, y + h/2, w h, w / h].
+ *   birth        a new Tentative track (hits 0, id -1) per detection the reference leaves in unmatched_dets, ascending (tracker_manager.h:110-117).  That list is KEPT AS THE
+ *                REFERENCE COMPUTES IT: tracker_manager.cpp:62-68 subtracts the assigned COLUMN INDICES from the detection ids, which are the same numbers in stage 1 and
+ *                not in stage 2 once stage 1 has matched something.  So after stage 2 a detection d of its columns is born unless some pair was assigned column INDEX d: a
+ *                detection matched in stage 2 may ALSO start a track, and an unmatched one may start none.
+ *   gallery      for every matched pair, births included, the embedding goes into the track's ring of `budget` rows by FeatureBundle::add (feature_bundle.h:40-46): if
+ *                next == budget then full = true, next = 0; stored at next++.  A distance reads `next` rows, all `budget` once full.  Rows past that count are excluded BY
+ *                INDEX, never multiplied in: they are uninitialised (dv_mot_config fills the allocation with NaN so that a slip shows).
+ *   remove_deleted, order kept; removal never moves gallery rows (a track owns a gallery slot; freed slots are taken lowest first).
+ *   answer       visible_tracks_info (tracker_manager.h:136-156): track_id[j] = the id of the Confirmed track updated with detection j in this frame, else -1 — the value
+ *                the plane entries drop a detection by.
+ * The assignment is the one the reference's Munkres (mot/hungarian.cpp, Buehren's steps) returns, ties included: same scan orders, same fabs(x) < DBL_EPSILON zero test.
+ * A NaN appearance or IoU distance counts as gated (1000) in both stages: Munkres on a NaN need not end.
+ * A frame after which the table would hold more than max_tracks tracks FAILS in _collect with a message and leaves the tracker as it was before the frame.
+ * dv_mot_check: the refusals of dv_mot_config without a device.  dv_mot_config: allocates (galleries max_tracks x budget x feat_dim float32, once) and resets; a second
+ * call reconfigures.  dv_mot_reset: no tracks, id counter back to 1.
+ * _enqueue: on the ctx's stream — behind dv_inst_stack_frame_collect, in front of dv_inst_track_enqueue_planes.  mem = DV_MEM_HOST (both staged) or DV_MEM_DEVICE /
+ * DV_MEM_PINNED (both read in place until the collect; each pointer may be of either in-place kind: rectangles in pinned memory beside embeddings in device memory).  One frame may be in flight; n > 64 is refused.  No host round trip between _enqueue and _collect: counts stay on the
+ * device; the frame's only device -> host traffic is n ids and a few counters through pinned memory.
+ * dv_mot_get_tracks: the table in order (for tests and the shim).  dv_mot_assign: the operator form of the device Munkres alone on a row-major float cost matrix (host
+ * memory, finite, >= 0, rows <= 128, cols <= 64): assignment[row] = column or -1, nothing dropped. */
+#define DV_MOT_MAX_TRACKS 128
+#define DV_MOT_MAX_BUDGET 100
+#define DV_MOT_MAX_FEAT_DIM 512
+typedef struct dv_mot_params { int32_t n_init, max_age, budget, feat_dim, max_tracks, reserved[3]; } dv_mot_params;
+typedef struct dv_mot_track {
+    float x[7], p_diag[7], rect[4];      /* state, diagonal of the covariance, rect() = x, y, w, h */
+    int32_t state /* 0 Tentative, 1 Confirmed */, id, hits, time_since_update, n_feats /* stored embeddings */, reserved;
+} dv_mot_track;
+int dv_mot_check(const dv_mot_params* par);
+int dv_mot_config(dv_ctx* ctx, const dv_mot_params* par);
+int dv_mot_reset(dv_ctx* ctx);
+int dv_mot_update_enqueue(dv_ctx* ctx, const float* rects_xywh, const float* feats, int n, int mem);
+int dv_mot_update_collect(dv_ctx* ctx, int32_t* track_id, int* n_tracks, int* n_confirmed);
+int dv_mot_get_tracks(dv_ctx* ctx, dv_mot_track* out, int cap, int* n);
+int dv_mot_assign(dv_ctx* ctx, const float* cost, int rows, int cols, int32_t* assignment);
 /* cv::cvtColor(BGR2GRAY) on 8-bit images: (B 1868 + G 9617 + R 4899 + 8192) >> 14; gray is w x h, tightly packed */
 int dv_bgr2gray(dv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, uint8_t* gray, int mem);
 /* cv::remap(src, dst, map1, map2, INTER_LINEAR) — BORDER_CONSTANT 0 — with the fixed-point maps cv::initUndistortRectifyMap(..., CV_16SC2, ...)
