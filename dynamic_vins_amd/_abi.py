@@ -135,6 +135,13 @@ SIGNATURES = {
     "dv_mot_update_collect": (C.c_int, [_ctx, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dv_mot_get_tracks": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "dv_mot_assign": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dv_reid_check": (C.c_int, [C.c_size_t, C.c_int, C.c_int]),
+    "dv_reid_load": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
+    "dv_reid_extract_enqueue": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "dv_reid_extract_collect": (C.c_int, [_ctx, C.POINTER(C.c_void_p)]),
+    "dv_reid_get_feats": (C.c_int, [_ctx, C.c_void_p, C.c_int]),
+    "dv_reid_input": (C.c_int, [_ctx, C.c_void_p]),
+    "dv_reid_layer": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "dv_inst_track_enqueue_planes": (C.c_int, [_ctx, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "dv_track_unmask_static_planes": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dv_inst_set_disparity": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_double]),

@@ -181,6 +181,7 @@ int dv_stack_resolve(dv_ctx* ctx, const dv_mask_stack& st, struct DevBuf& own_bu
 void dv_stack_frame_done(dv_ctx* ctx);      // dv_track_stereo_collect: the shared staging ends with the frame
 void dv_solo_head_release(dv_ctx* ctx);     // solo_head.hip: the head's buffers (dv_destroy)
 void dv_mot_release(dv_ctx* ctx);           // mot.hip: the tracker's table and galleries (dv_destroy)
+void dv_reid_release(dv_ctx* ctx);          // reid.hip: the extractor's weights and activations (dv_destroy)
 
 // One window sharded by landmark over several GPUs (be_shard.hip): the transport of the exchange vectors
 struct DvDist {
@@ -231,6 +232,8 @@ struct dv_ctx {
     struct SoloHeadFrame* solo = nullptr;
     // dv_mot_*: the multi-object tracker behind that stage (detections + embeddings -> track ids; mot.hip, released by dv_mot_release)
     struct MotTracker* mot = nullptr;
+    // dv_reid_*: the ReID extractor in front of it (colour image + rectangles -> embeddings; reid.hip, released by dv_reid_release)
+    struct ReidNet* reid = nullptr;
     // dv_track_unmask_static_planes: the same rectangles, the per-pixel test being "the detection's plane has the pixel".  Dropped on EVERY return of the next
     // dv_track_stereo_enqueue / dv_batch_track_enqueue; a host stack the frame's stage did not stage is staged into unmask_stack_buf by that enqueue
     struct UnmaskPlaneJob { int x, y, w, h, plane; };

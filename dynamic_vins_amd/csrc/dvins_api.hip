@@ -326,6 +326,7 @@ void dv_destroy(dv_ctx* ctx) {
     dv_inst_stack_frame_release(ctx); ctx->unmask_stack_buf.release();
     dv_solo_head_release(ctx);
     dv_mot_release(ctx);
+    dv_reid_release(ctx);
     if (ctx->done) (void)hipEventDestroy(ctx->done);
     if (ctx->ev_pyr) (void)hipEventDestroy(ctx->ev_pyr);
     if (ctx->ev_bg_select) (void)hipEventDestroy(ctx->ev_bg_select);

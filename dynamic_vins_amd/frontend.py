@@ -114,6 +114,16 @@ def mot_check(params):
         raise DvinsError(lib.dv_last_error(None).decode())
 
 
+DV_REID_N_FLOATS, DV_REID_FEAT_DIM, DV_REID_MAX_CROPS = 11178496, 512, 64
+
+
+def reid_check(n_floats, in_w=64, in_h=128):
+    """the refusals of Context.reid_load, without a device: raises DvinsError with the reason"""
+    lib = _abi.load()
+    if lib.dv_reid_check(int(n_floats), int(in_w), int(in_h)) != 0:
+        raise DvinsError(lib.dv_last_error(None).decode())
+
+
 def solo_check(outputs, params):
     """the refusals of solo_head_enqueue, without a device: raises DvinsError with the reason"""
     lib = _abi.load()
@@ -170,6 +180,7 @@ class Context:
             raise DvinsError(self.lib.dv_last_error(None).decode())
         self._out = np.zeros(_abi.DV_MAX_FEATS, FEAT_DTYPE)
         self._mot_par, self._mot_n, self._mot_keep, self._mot_pin = None, 0, None, None
+        self._reid_size, self._reid_n, self._reid_keep, self._reid_pin = None, 0, None, None
 
     def close(self):
         if getattr(self, "h", None):
@@ -178,6 +189,9 @@ class Context:
             if getattr(self, "_mot_pin", None):
                 self.lib.dv_pinned_free(self._mot_pin)
                 self._mot_pin = None
+            if getattr(self, "_reid_pin", None):
+                self.lib.dv_pinned_free(self._reid_pin)
+                self._reid_pin = None
 
     def __del__(self):
         try:
@@ -411,6 +425,95 @@ class Context:
         out = np.full(max(rows, 1), -1, np.int32)
         self._check(self.lib.dv_mot_assign(self.h, cost.ctypes.data if cost.size else None, rows, cols, out.ctypes.data))
         return out[:rows].copy()
+
+    # ---- the ReID extractor (Extractor::extract, mot/extractor.cpp:31-52; ReIdNetImpl, mot/reid_net.cpp): colour image + rectangles -> [n, 512] embeddings on the device ----
+    def reid_load(self, weights, in_w=64, in_h=128):
+        """weights: a float32 array or the path of the flat file ReIdNetImpl::load_form reads (11 178 496 floats); in_w x in_h = reid_input_width x reid_input_height.
+        A second load replaces the weights; a refused one leaves the ctx as it was"""
+        if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__"):
+            weights = np.fromfile(weights, np.float32)
+        weights = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        self._check(self.lib.dv_reid_load(self.h, weights.ctypes.data, weights.size, int(in_w), int(in_h)))
+        self._reid_size = (int(in_w), int(in_h))
+
+    def reid_extract_enqueue(self, bgr, rects, n=None, mem=DV_MEM_HOST, stride=None):
+        """one frame on the ctx's stream.  mem = DV_MEM_HOST: bgr an (height, width, 3) uint8 array of the ctx's size (any row stride), rects [n, 4] x, y, w, h float32;
+        both staged.  DV_MEM_DEVICE / DV_MEM_PINNED: bgr is a pointer (int) read in place until the collect, with n and the row stride in bytes; rects is a pointer of either
+        in-place kind, or a host array, which goes through a small pinned buffer of the ctx"""
+        if mem == DV_MEM_HOST:
+            rects = np.ascontiguousarray(rects, np.float32).reshape(-1, 4)
+            n = len(rects) if n is None else int(n)
+            if n:
+                if bgr.dtype != np.uint8 or bgr.ndim != 3 or bgr.shape[2] != 3 or bgr.strides[2] != 1 or bgr.strides[1] != 3:
+                    raise ValueError("reid_extract_enqueue: bgr must be (height, width, 3) uint8 with packed pixels")
+                if bgr.shape[:2] != (self.cfg.height, self.cfg.width):
+                    raise ValueError("reid_extract_enqueue: the image must have the ctx's size")
+                stride = bgr.strides[0]
+        else:
+            if n is None or (int(n) and stride is None):
+                raise ValueError("reid_extract_enqueue: n and stride are required with device or pinned pointers")
+            n = int(n)
+            if n and not isinstance(bgr, (int, np.integer)):
+                raise ValueError("reid_extract_enqueue: bgr must be a pointer (int) with device or pinned memory")
+            if n and not isinstance(rects, (int, np.integer)):      # a host array of rectangles beside an in-place image: through a small pinned buffer of the ctx
+                r = np.ascontiguousarray(rects, np.float32).reshape(-1, 4)
+                if len(r) != n or n > DV_REID_MAX_CROPS:
+                    raise ValueError(f"rects must be [{n}, 4], n <= {DV_REID_MAX_CROPS}")
+                if self._reid_pin is None:
+                    self._reid_pin = self.lib.dv_pinned_alloc(DV_REID_MAX_CROPS * 16)
+                    if not self._reid_pin:
+                        raise DvinsError("reid_extract_enqueue: no pinned memory")
+                C.memmove(self._reid_pin, r.ctypes.data, n * 16)
+                rects = int(self._reid_pin)
+        self._reid_keep = (bgr, rects)
+        self._check(self.lib.dv_reid_extract_enqueue(self.h, _ptr(bgr) if n else None, int(stride or 0), _ptr(rects) if n else None, n, mem))
+        self._reid_n = n
+
+    def reid_extract_collect(self):
+        """-> (device pointer of the [n, 512] float32 embeddings, valid until the next enqueue; n).  mot_update_enqueue(rects, ptr, n, DV_MEM_DEVICE) reads it in place"""
+        p = C.c_void_p(0)
+        n, self._reid_n, self._reid_keep = self._reid_n, 0, None
+        self._check(self.lib.dv_reid_extract_collect(self.h, C.byref(p)))
+        return int(p.value or 0), n
+
+    def reid_feats(self, n):
+        """the first n embeddings of the last collected frame, downloaded"""
+        out = np.zeros((int(n), DV_REID_FEAT_DIM), np.float32)
+        self._check(self.lib.dv_reid_get_feats(self.h, out.ctypes.data if n else None, int(n)))
+        return out
+
+    def reid_extract(self, bgr, rects, n=None, mem=DV_MEM_HOST, stride=None):
+        """reid_extract_enqueue + reid_extract_collect + the download -> [n, 512] float32"""
+        self.reid_extract_enqueue(bgr, rects, n, mem, stride)
+        _, n = self.reid_extract_collect()
+        return self.reid_feats(n)
+
+    def reid_input(self, n):
+        """the prepared [n, 3, in_h, in_w] tensor of the last collected frame of n crops (for tests)"""
+        if self._reid_size is None:
+            raise DvinsError("reid_input: reid_load first")
+        w, h = self._reid_size
+        out = np.zeros((max(int(n), 1), 3, h, w), np.float32)
+        self._check(self.lib.dv_reid_input(self.h, out.ctypes.data))
+        return out[: int(n)]
+
+    def reid_layer(self, x, weight, scale, shift, residual=None, stride=1, relu=True):
+        """the extractor's convolution kernel alone: relu?(conv2d(x, weight, stride, padding 1 for a 3 x 3, 0 for a 1 x 1) * scale + shift + residual), NCHW float32"""
+        x, weight = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(weight, np.float32)
+        scale, shift = np.ascontiguousarray(scale, np.float32), np.ascontiguousarray(shift, np.float32)
+        n, ci, h, w = x.shape
+        co, ci2, k, k2 = weight.shape
+        if ci2 != ci or k2 != k or scale.shape != (co,) or shift.shape != (co,):
+            raise ValueError("reid_layer: shapes do not agree")
+        ho, wo = (h + (2 if k == 3 else 0) - k) // stride + 1, (w + (2 if k == 3 else 0) - k) // stride + 1
+        out = np.zeros((n, co, max(ho, 1), max(wo, 1)), np.float32)
+        if residual is not None:
+            residual = np.ascontiguousarray(residual, np.float32)
+            if residual.shape != out.shape:
+                raise ValueError("reid_layer: residual must have the output's shape")
+        self._check(self.lib.dv_reid_layer(self.h, x.ctypes.data, n, ci, h, w, weight.ctypes.data, co, k, int(stride), scale.ctypes.data, shift.ctypes.data,
+                                           residual.ctypes.data if residual is not None else None, int(bool(relu)), out.ctypes.data))
+        return out
 
     def solo_head(self, outputs, params):
         """solo_head_enqueue + solo_head_collect"""

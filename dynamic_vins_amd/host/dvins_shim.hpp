@@ -708,6 +708,60 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// The ReID extractor (mot/extractor.h, mot/reid_net.h) on the device: dv_reid_load / dv_reid_extract_enqueue / _collect.  load_form reads the flat float32 file of
+// ReIdNetImpl::load_form; extract crops the rectangles out of an 8-bit BGR image of the ctx's size (host memory, or device memory with image.device), resizes, normalises
+// and runs the network.  extract_device leaves the [n, 512] embeddings on the device (valid until the next extract); extract downloads them.
+class Extractor {
+public:
+    using Ptr = std::shared_ptr<Extractor>;
+    explicit Extractor(dv_ctx* ctx) : ctx_(ctx) {}
+    void load_form(const std::string& bin_path, int in_w = 64, int in_h = 128) {
+        std::ifstream fs(bin_path, std::ios::binary | std::ios::ate);
+        if (!fs) throw std::runtime_error("Extractor::load_form: cannot open " + bin_path);
+        const std::streamoff bytes = fs.tellg();
+        if (bytes < 0 || bytes % 4) throw std::runtime_error("Extractor::load_form: " + bin_path + " is not a float32 file");
+        if (dv_reid_check((size_t)bytes / 4, in_w, in_h) != 0) throw std::runtime_error(std::string("Extractor::load_form: ") + dv_last_error(nullptr));
+        std::vector<float> w((size_t)bytes / 4);
+        fs.seekg(0);
+        fs.read(reinterpret_cast<char*>(w.data()), bytes);
+        if (fs.gcount() != bytes) throw std::runtime_error("Extractor::load_form: short read of " + bin_path);
+        detail::check(ctx_, dv_reid_load(ctx_, w.data(), w.size(), in_w, in_h), "Extractor::load_form");
+    }
+    // -> device pointer of [n, 512] float32, nullptr for an empty list (Extractor::extract returns an empty tensor, mot/extractor.cpp:32-34)
+    const float* extract_device(const ImageView& image, const std::vector<std::array<float, 4>>& rects) {
+        const int n = (int)rects.size();
+        if (n > DV_REID_MAX_CROPS) throw std::runtime_error("Extractor::extract: more than 64 rectangles");
+        if (n && (image.empty() || !image.bgr)) throw std::runtime_error("Extractor::extract: an 8-bit BGR image is required");
+        const float* r = n ? rects[0].data() : nullptr;
+        if (n && image.device) {      // in-place kinds travel together: the rectangles go to the device beside the image
+            detail::check(ctx_, dv_reid_extract_enqueue(ctx_, image.data, image.stride, to_pinned(r, n), n, DV_MEM_PINNED), "Extractor::extract");
+        } else {
+            detail::check(ctx_, dv_reid_extract_enqueue(ctx_, image.data, image.stride, r, n, DV_MEM_HOST), "Extractor::extract");
+        }
+        const float* feats = nullptr;
+        detail::check(ctx_, dv_reid_extract_collect(ctx_, &feats), "Extractor::extract");
+        return feats;
+    }
+    std::vector<float> extract(const ImageView& image, const std::vector<std::array<float, 4>>& rects) {
+        extract_device(image, rects);
+        std::vector<float> out(rects.size() * DV_REID_FEAT_DIM);
+        detail::check(ctx_, dv_reid_get_feats(ctx_, out.data(), (int)rects.size()), "Extractor::extract");
+        return out;
+    }
+    ~Extractor() { if (pinned_) dv_pinned_free(pinned_); }
+    Extractor(const Extractor&) = delete;
+    Extractor& operator=(const Extractor&) = delete;
+private:
+    const float* to_pinned(const float* r, int n) {
+        if (!pinned_) pinned_ = static_cast<float*>(dv_pinned_alloc(DV_REID_MAX_CROPS * 4 * sizeof(float)));
+        if (!pinned_) throw std::runtime_error("Extractor::extract: no pinned memory");
+        std::memcpy(pinned_, r, (size_t)n * 4 * sizeof(float));
+        return pinned_;
+    }
+    dv_ctx* ctx_; float* pinned_ = nullptr;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // The multi-object tracker (mot/deep_sort.h) on the device: dv_mot_update_enqueue / _collect.  The reference's update(detections, ori_img) extracts the embeddings from
 // cv::Mat crops itself; the shim has no crops, so the caller's ReID network runs first and hands its [n, feat_dim] float32 output (L2-normalised rows, mot/reid_net.cpp)
 // as a pointer: feat_mem = DV_MEM_HOST, or DV_MEM_DEVICE / DV_MEM_PINNED (read in place until the collect).  The rectangles come from the detections on the host
@@ -761,6 +815,21 @@ public:
         }
         dets.resize(m); if (planes.size() > m) planes.resize(m);
     }
+    // The reference's own signature (mot/deep_sort.cpp:72): update(detections, ori_img).  The embeddings come from the device extractor (set_extractor, its weights
+    // loaded) and never leave the device: dv_reid_extract_collect's pointer goes straight into dv_mot_update_enqueue
+    void set_extractor(Extractor::Ptr e) { extractor_ = std::move(e); }
+    std::vector<int32_t> update(const std::vector<std::array<float, 4>>& rects, const ImageView& ori_img) {
+        if (!extractor_) throw std::runtime_error("DeepSORT::update(detections, ori_img): set_extractor first");
+        if (rects.empty()) return {};
+        return update(rects, extractor_->extract_device(ori_img, rects), DV_MEM_DEVICE);
+    }
+    void AddInstancesByTracking(std::vector<dv_inst_det>& dets, std::vector<int32_t>& planes, const ImageView& ori_img) {
+        if (!extractor_) throw std::runtime_error("DeepSORT::AddInstancesByTracking(dets, planes, ori_img): set_extractor first");
+        if (dets.empty()) return;
+        std::vector<std::array<float, 4>> rects(dets.size());
+        for (size_t i = 0; i < dets.size(); ++i) rects[i] = {(float)dets[i].x, (float)dets[i].y, (float)dets[i].w, (float)dets[i].h};
+        AddInstancesByTracking(dets, planes, extractor_->extract_device(ori_img, rects), DV_MEM_DEVICE);
+    }
     std::vector<dv_mot_track> tracks() {
         std::vector<dv_mot_track> t(DV_MOT_MAX_TRACKS); int n = 0;
         detail::check(ctx_, dv_mot_get_tracks(ctx_, t.data(), (int)t.size(), &n), "DeepSORT::tracks");
@@ -769,7 +838,7 @@ public:
     }
     int n_tracks() const { return n_tracks_; } int n_confirmed() const { return n_confirmed_; }
 private:
-    dv_ctx* ctx_; dv_mot_params para_; float* pinned_ = nullptr; int n_ = 0, n_tracks_ = 0, n_confirmed_ = 0;
+    dv_ctx* ctx_; dv_mot_params para_; float* pinned_ = nullptr; int n_ = 0, n_tracks_ = 0, n_confirmed_ = 0; Extractor::Ptr extractor_;
 };
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -241,9 +241,21 @@ class DynamicPipeline(Pipeline):
         if mot is not None:
             if live_masks or not (mask_stack or solo_head is not None):
                 raise ValueError("DynamicPipeline: mot needs mask_stack=True or solo_head; it cannot be combined with pre-computed masks or live_masks")
-            if not (isinstance(mot, (tuple, list)) and len(mot) == 2 and callable(mot[0]) and isinstance(mot[1], dict)):
+            if not (isinstance(mot, (tuple, list)) and len(mot) == 2 and (callable(mot[0]) or mot[0] == "device") and isinstance(mot[1], dict)):
                 raise ValueError("DynamicPipeline: mot must be (callable (k, dets, stack) -> feats, dict of mot_params keywords)")
-        self.mot, self._mot_keep = mot, None
+            # mot = ("device", params): the embeddings come from the device extractor (Context.reid_*; Extractor::extract, mot/extractor.cpp:31-52) instead of a callable.
+            # params then also carries reid_weights (an array or the path of ReIdNetImpl::load_form's flat file) and optionally reid_input = (width, height); the rest are
+            # mot_params keywords as before (feat_dim must stay 512).  The extractor reads reid_image(k): the sequence's left colour image where it has one (seq.color0[k],
+            # an (h, w, 3) uint8 BGR device tensor), else the left GRAY image replicated to three channels (the rendered sequences of this package carry no colour)
+            if mot[0] == "device":
+                par = dict(mot[1])
+                if "reid_weights" not in par:
+                    raise ValueError("DynamicPipeline: mot must be (\"device\", params) with params['reid_weights']")
+                self._reid_load = (par.pop("reid_weights"), tuple(par.pop("reid_input", (64, 128))))
+                if int(par.get("feat_dim", 512)) != 512:
+                    raise ValueError("DynamicPipeline: mot must be (\"device\", params) with feat_dim 512, the extractor's width")
+                mot = ("device", par)
+        self.mot, self._mot_keep, self._reid_img = mot, None, (None, None)
         self.extra_from_disparity = extra_from_disparity      # False: the detections' own `points` are handed through (the caller ran the extra-point pipeline)
         self.seq, self.host = seq, None
         c = make_cam(*sim.cam_tuple(seq.cam))
@@ -252,6 +264,8 @@ class DynamicPipeline(Pipeline):
         self.ctx.inst_config(max_dynamic_cnt, min_dynamic_dist, use_det3d)
         if self.mot is not None:
             self.ctx.mot_config(**self.mot[1])
+            if self.mot[0] == "device":
+                self.ctx.reid_load(self._reid_load[0], *self._reid_load[1])
         self.est_kw = dict(use_imu=use_imu, stereo=1, max_iters=max_iters, ric=seq.rig["est_ric"], tic=seq.rig["est_tic"], dynamic=1, use_det3d=use_det3d,
                            static_inst_threshold=static_inst_threshold, use_line=int(segments is not None), **seq.noise)
         self.est_kw.update(est_kw or {})
@@ -300,6 +314,15 @@ class DynamicPipeline(Pipeline):
         from .frontend import DV_MEM_DEVICE as DEV
         if not len(dets):
             return dets
+        rects = np.array([d["rect"] for d in dets], np.float32)
+        if self.mot[0] == "device":          # image and embeddings stay on the device: the collect's pointer goes straight into the tracker
+            import torch
+            img = self.reid_image(k)
+            torch.cuda.current_stream().synchronize()
+            self.ctx.reid_extract_enqueue(img.data_ptr(), rects, n=len(dets), mem=DEV, stride=img.stride(0))
+            feats, _ = self.ctx.reid_extract_collect()
+            ids, _, _ = self.ctx.mot_update(rects, feats, n=len(dets), mem=DEV)
+            return [dict(d, track_id=int(i)) for d, i in zip(dets, ids) if i >= 0]
         feats = self.mot[0](k, dets, stack)
         if hasattr(feats, "data_ptr"):
             import torch
@@ -307,8 +330,17 @@ class DynamicPipeline(Pipeline):
                 raise ValueError("DynamicPipeline: mot feats must be a contiguous float32 [n, feat_dim] tensor")
             torch.cuda.current_stream().synchronize()      # the caller's network ran on the tensor library's stream
             self._mot_keep, feats = feats, feats.data_ptr()
-        ids, _, _ = self.ctx.mot_update(np.array([d["rect"] for d in dets], np.float32), int(feats), n=len(dets), mem=DEV)
+        ids, _, _ = self.ctx.mot_update(rects, int(feats), n=len(dets), mem=DEV)
         return [dict(d, track_id=int(i)) for d, i in zip(dets, ids) if i >= 0]
+
+    def reid_image(self, k):
+        """the image the device extractor crops for frame k, an (h, w, 3) uint8 BGR device tensor: seq.color0[k] where the sequence has colour, else the left gray image
+        replicated to three channels"""
+        if self._reid_img[0] != k:
+            c = getattr(self.seq, "color0", None)
+            img = c[k] if c is not None else self.seq.frames[k][0].unsqueeze(-1).expand(-1, -1, 3).contiguous()
+            self._reid_img = (k, img)
+        return self._reid_img[1]
 
     def _enqueue_stack(self, k):
         from .frontend import DV_MEM_DEVICE as DEV

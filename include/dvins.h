@@ -312,6 +312,47 @@ int dv_mot_update_enqueue(dv_ctx* ctx, const float* rects_xywh, const float* fea
 int dv_mot_update_collect(dv_ctx* ctx, int32_t* track_id, int* n_tracks, int* n_confirmed);
 int dv_mot_get_tracks(dv_ctx* ctx, dv_mot_track* out, int cap, int* n);
 int dv_mot_assign(dv_ctx* ctx, const float* cost, int rows, int cols, int32_t* assignment);
+/* The ReID EXTRACTOR in front of the multi-object tracker: the frame's colour image and the detections' rectangles -> one L2-normalised 512-float embedding per detection,
+ * as DeepSORT::update gets them from Extractor::extract (mot/extractor.cpp:31-52) and ReIdNetImpl::forward (mot/reid_net.cpp:113-121).  float32 throughout.
+ * Weights (dv_reid_load): host memory in the order ReIdNetImpl::load_form reads its flat file (mot/reid_net.cpp:123-135, the modules of :17-44 and :98-110):
+ *   conv1     weight [64, 3, 3, 3], bias [64], then its BatchNorm2d: weight, bias, running_mean, running_var (64 each);
+ *   8 blocks  (c_in, c_out, down) = (64,64,0) (64,64,0) (64,128,1) (128,128,0) (128,256,1) (256,256,0) (256,512,1) (512,512,0), each: conv.0 weight [c_out, c_in, 3, 3]
+ *             (stride 2 when down) and its batch-norm (4 x c_out), conv.3 weight [c_out, c_out, 3, 3] and its batch-norm, and for a down block the 1 x 1 stride-2
+ *             weight [c_out, c_in, 1, 1] and its batch-norm.  No num_batches_tracked.
+ * That is 2 048 + 2 x 74 240 + 230 912 + 295 936 + 920 576 + 1 181 696 + 3 676 160 + 4 722 688 = DV_REID_N_FLOATS; any other length is refused (the reference reads short
+ * without a word).  Batch-norm is the eval-mode form with eps 1e-5, folded on the host in float64 into one scale and one shift per channel, conv1's bias inside the shift
+ * (declared: the reference evaluates it unfolded in float32).  in_w x in_h = reid_input_width x reid_input_height (mot/mot_parameter.h:29-30, 64 x 128): accepted are the
+ * sizes whose last map is 8 x 4 after four stride-2 stages n -> ceil(n / 2), so that avg_pool2d({8, 4}, 1) leaves 512 values: widths 49..64, heights 113..128.
+ * A second load replaces the weights; a refused one leaves the ctx as it was.  Activations for DV_REID_MAX_CROPS crops are allocated at the load.
+ * Crops (one launch, no host image work), per rectangle x, y, w, h (float32; Rect2f -> Rect is cvRound per field, half to even): ori_img(rect), cv::resize(.., {in_w,
+ * in_h}), cvtColor(RGB2BGR) = a channel swap, convertTo(CV_32F, 1 / 255), (v - mean[c]) / std[c] with mot/mot_parameter.h:26-27 on the SWAPPED order, NCHW.  The resize
+ * is OpenCV's 8-bit INTER_LINEAR restated (unpinned): scale = src / (double) dst; f = (float)((d + 0.5) scale - 0.5); s = floor(f); f -= s;
+ * horizontally s < 0 -> s = 0, f = 0 and s >= src - 1 -> s = src - 1, f = 0; vertically f is kept and the two row indices are clamped to [0, src - 1] (the CROP's
+ * edges); coefficients cvRound((1 - f) 2048) and cvRound(f 2048); S = s0 a0 + s1 a1; the byte is (((b0 (S0 >> 4)) >> 16) + ((b1 (S1 >> 4)) >> 16) + 2) >> 2.  A crop of
+ * exactly 2 in_w x 2 in_h takes the fast area path (a + b + c + d + 2) >> 2.  The float is (u * (1 / 255.f) - mean) / std in that order, float32, IEEE division.
+ * A rounded rectangle that is empty or leaves the image makes the reference throw: here the frame FAILS at _collect with a message and the stage stays usable.
+ * Network: conv1 + batch-norm + ReLU + max_pool2d(3, 2, 1) (padding -inf) in one kernel; every other convolution is one implicit-GEMM kernel on the f32 matrix cores
+ * whose epilogue applies scale and shift, the residual (the block's input, or the 1 x 1 branch's output) and the ReLU; the tail (average over the 8 x 4 map in a fixed
+ * order, row 2-norm, division) is one kernel.
+ * dv_reid_check: the refusals of dv_reid_load without a device.
+ * _enqueue: on the ctx's stream, the image being the ctx's width x height, 8-bit BGR with `stride` bytes per row.  mem = DV_MEM_HOST (image and rectangles staged) or
+ * DV_MEM_DEVICE / DV_MEM_PINNED (both read in place until the collect).  One frame may be in flight; n > 64 is refused; n = 0 returns at once as extract does on an empty
+ * list.  _collect: *feats_dev = the library's [n, 512] float32 device buffer, valid until the next enqueue; dv_mot_update_enqueue(.., DV_MEM_DEVICE) reads it in place.
+ * dv_reid_get_feats: the first n rows of the last collected frame, downloaded (tests, the shim).  dv_reid_input: the prepared [n, 3, in_h, in_w] tensor of the last frame.
+ * dv_reid_layer: the operator form of the convolution kernel alone on host tensors: x [n, c_in, h, w], weight [c_out, c_in, k, k], scale and shift [c_out], residual
+ * [n, c_out, h_out, w_out] or null -> out [n, c_out, h_out, w_out] = relu?(conv(x) * scale + shift + residual), h_out = (h + 2 pad - k) / stride + 1 with pad 1 for
+ * k = 3 and 0 for k = 1.  (k, stride) in {(3, 1), (3, 2), (1, 2)}, c_in a multiple of 32, c_out of 64, both <= 512, h and w <= 128, n <= 64, n h w max(c_in, c_out) <= 2^24. */
+#define DV_REID_N_FLOATS 11178496
+#define DV_REID_FEAT_DIM 512
+#define DV_REID_MAX_CROPS 64
+int dv_reid_check(size_t n_floats, int in_w, int in_h);
+int dv_reid_load(dv_ctx* ctx, const float* weights, size_t n_floats, int in_w, int in_h);
+int dv_reid_extract_enqueue(dv_ctx* ctx, const uint8_t* bgr, int stride, const float* rects_xywh, int n, int mem);
+int dv_reid_extract_collect(dv_ctx* ctx, const float** feats_dev);
+int dv_reid_get_feats(dv_ctx* ctx, float* out, int n);
+int dv_reid_input(dv_ctx* ctx, float* out);
+int dv_reid_layer(dv_ctx* ctx, const float* x, int n, int c_in, int h, int w, const float* weight, int c_out, int k, int stride, const float* scale, const float* shift,
+                  const float* residual_or_null, int relu, float* out);
 /* cv::cvtColor(BGR2GRAY) on 8-bit images: (B 1868 + G 9617 + R 4899 + 8192) >> 14; gray is w x h, tightly packed */
 int dv_bgr2gray(dv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, uint8_t* gray, int mem);
 /* cv::remap(src, dst, map1, map2, INTER_LINEAR) — BORDER_CONSTANT 0 — with the fixed-point maps cv::initUndistortRectifyMap(..., CV_16SC2, ...)
