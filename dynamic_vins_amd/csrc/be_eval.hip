@@ -9,7 +9,8 @@
 //                    Hessian pieces (h, g, w[a], gp[a], Ddiag[a], Danch[a]) are summed over its residual
 //                    blocks in a fixed order and written as one 7.4 KB packet.  Nothing is accumulated
 //                    with atomics, so the reduced system is bitwise reproducible.
-//   IMU block      : lane 0 evaluates the raw 15-residual / 15x30 Jacobian, all lanes whiten with the cached
+//   IMU block      : lane 0 evaluates the raw 15-residual / 15x30 Jacobian (single-window form: one lane of each of the
+//                    four waves, a share of the Jacobian's blocks each), all lanes whiten with the cached
 //                    sqrt-information and form the factor's 30x30 Hessian block and gradient.
 //   prior block    : g = b' + A' dx and cost = c0/2 + b'.dx + dx.A'dx/2 (information form of the
 //                    MarginalizationFactor, factor/marginalization_factor.cpp:350-396).
@@ -42,6 +43,87 @@ __device__ __forceinline__ int be_eval_block_of(int bx, int nlm) {
 // ARGS: BeEvalArgs (kernel arguments by value: invariant scalar loads) or the same struct in the constant address space (batched form: the argument table in
 // HBM read through the scalar / invariant path instead of re-loading every field after each store)
 #define DV_CONSTANT __attribute__((address_space(4)))
+// ---- the single-window form's (LPB = 1) shortened chains: the same operands and the same order of additions as the loops they stand in for (which the batched forms keep,
+// their register counts decide their occupancy); what changes is that an entry's LDS / global reads are issued together, ahead of the additions ----
+// One packet entry as a sum of terms Jb[f][ca] * Jb[f][cb] + Jb[f][cc] * Jb[f][cd].  mode: -1 not written (a frame the landmark does not touch), 0 zero, 1 the cost,
+// 2 every factor, 3 every two-frame factor (the anchor's entries), 4 the (<= 2) factors whose frame j is fa
+struct EvPkEnt { int mode, fa, ca, cb, cc, cd; };
+__device__ __forceinline__ EvPkEnt ev_pk_decode(int e, int anchor, int obs) {
+    EvPkEnt d{0, 0, 0, 0, 0, 0};
+    if (e >= BE_PK_SIZE) { d.mode = -1; return d; }
+    if (e == BE_PK_H) { d.mode = 2; d.ca = 26; d.cb = 26; d.cc = 27; d.cd = 27; }
+    else if (e == BE_PK_G) { d.mode = 2; d.ca = 26; d.cb = 0; d.cc = 27; d.cd = 1; }
+    else if (e == BE_PK_COST) d.mode = 1;
+    else if (e < BE_PK_DD) {
+        const bool is_w = e < BE_PK_GP;
+        const int q = e - (is_w ? BE_PK_W : BE_PK_GP), fa = q / 6, rr = q - fa * 6;
+        d.fa = fa; d.cb = is_w ? 26 : 0; d.cd = is_w ? 27 : 1;
+        if (fa == anchor) { d.mode = 3; d.ca = 2 + rr; d.cc = 8 + rr; } else { d.mode = 4; d.ca = 14 + rr; d.cc = 20 + rr; }
+        if (!is_w && !((obs >> fa) & 1)) d.mode = -1;
+    } else if (e < BE_PK_DA + BE_NF * 36) {
+        const bool dd = e < BE_PK_DA;
+        const int q = e - (dd ? BE_PK_DD : BE_PK_DA), fa = q / 36, rc = q - fa * 36, rr = rc / 6, cc = rc - rr * 6;
+        d.fa = fa;
+        if (dd) {
+            if (fa == anchor) { d.mode = 3; d.ca = 2 + rr; d.cb = 2 + cc; d.cc = 8 + rr; d.cd = 8 + cc; }
+            else { d.mode = 4; d.ca = 14 + rr; d.cb = 14 + cc; d.cc = 20 + rr; d.cd = 20 + cc; }
+        } else if (fa != anchor) { d.mode = 4; d.ca = 2 + rr; d.cb = 14 + cc; d.cc = 8 + rr; d.cd = 20 + cc; }
+        if (!((obs >> fa) & 1)) d.mode = -1;
+    }
+    return d;
+}
+// the packet of one landmark by 256 threads: a thread's (<= 4) entries are decoded first, the slot lists of all of them are read together, then the operands of all their
+// terms, then the additions run in the order slot 0, slot 1; an entry over all factors (H, G, the anchor's: 2 + 48 of the 928) reads eight factors' operands per trip and
+// adds them in index order under the same skip rule
+__device__ __forceinline__ void ev_packet_256(double (*Jb)[28], const int* s_two, int (*s_flist)[2], int nf, int anchor, int obs, double cost,
+                                              int lane, double* o_packets, int b) {
+    constexpr int NE = (BE_PK_SIZE + EV_THREADS - 1) / EV_THREADS;
+    EvPkEnt d[NE];
+    int fs[NE][2];
+    double op[NE][2][4], v[NE];
+#pragma unroll
+    for (int k = 0; k < NE; ++k) d[k] = ev_pk_decode(lane + EV_THREADS * k, anchor, obs);
+#pragma unroll
+    for (int k = 0; k < NE; ++k) { fs[k][0] = s_flist[d[k].fa][0]; fs[k][1] = s_flist[d[k].fa][1]; }
+#pragma unroll
+    for (int k = 0; k < NE; ++k)
+#pragma unroll
+        for (int sl = 0; sl < 2; ++sl) {
+            const double* J = Jb[fs[k][sl] < 0 ? 0 : fs[k][sl]];
+            op[k][sl][0] = J[d[k].ca]; op[k][sl][1] = J[d[k].cb]; op[k][sl][2] = J[d[k].cc]; op[k][sl][3] = J[d[k].cd];
+        }
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {
+        double s = 0.0;
+#pragma unroll
+        for (int sl = 0; sl < 2; ++sl)
+            if (d[k].mode == 4 && fs[k][sl] >= 0) s += op[k][sl][0] * op[k][sl][1] + op[k][sl][2] * op[k][sl][3];
+        v[k] = d[k].mode == 1 ? cost : s;
+    }
+#pragma unroll
+    for (int k = 0; k < NE; ++k)
+        if (d[k].mode == 2 || d[k].mode == 3) {
+            const bool two_only = d[k].mode == 3;
+            double s = 0.0;
+            for (int f0 = 0; f0 < nf; f0 += 8) {
+                double A[8], B[8], C[8], D[8]; int tw[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int f = f0 + u < BE_MAX_OBS_FACTORS ? f0 + u : BE_MAX_OBS_FACTORS - 1;      // (rows behind nf: in bounds, never added)
+                    const double* J = Jb[f];
+                    A[u] = J[d[k].ca]; B[u] = J[d[k].cb]; C[u] = J[d[k].cc]; D[u] = J[d[k].cd]; tw[u] = s_two[f];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    if (f0 + u < nf && (!two_only || tw[u])) s += A[u] * B[u] + C[u] * D[u];
+            }
+            v[k] = s;
+        }
+#pragma unroll
+    for (int k = 0; k < NE; ++k)
+        if (d[k].mode >= 0) BE_PK(o_packets, lane + EV_THREADS * k, b) = v[k];
+}
+
 // LPB = landmarks per workgroup: 1 (the single-window launch: 256 threads sum one landmark's packet, lowest latency) or 4 (the batched launch: one WAVE per landmark
 // — only L.count <= 22 lanes of a workgroup do the factor arithmetic and the kernel's 214 VGPRs allow two workgroups per CU, so with one landmark per workgroup a CU
 // worked on 2 landmarks at a time; with four it works on 8 and the frame geometry is formed once for all four).  Same arithmetic, same order per landmark.
@@ -81,16 +163,22 @@ __device__ __forceinline__ void be_eval_body(const ARGS& a, int mode, int bg) {
         const bool valid = b < nlm && !(b < a.lm_lo || b >= a.lm_hi);      // (sharded window: another rank's landmark)
         if (LPB == 1 && !valid) return;
         BeLm L{}; if (valid) L = a.lm[b];
+        // single-window form: the factor record, the inverse depth and td are requested HERE, so that their round trip runs beside the geometry instead of behind its barrier
+        BeFactor f_early{}; double lambda_early = 1.0, td_early = 0.0;
+        if constexpr (LPB == 1) {
+            if (lane < L.count) f_early = a.fac[L.first + lane];
+            lambda_early = st->inv_depth[b]; td_early = st->td;
+        }
         be_frame_geom_dev(st, a.dims.nframes, fg, ric, tic, (int)threadIdx.x);
         if (LPB == 1) { if (lane >= 64 && lane < 64 + 2 * BE_NF) s_flist[(lane - 64) >> 1][(lane - 64) & 1] = -1; }
         else if (lane >= TPL - 2 * BE_NF) s_flist[(lane - (TPL - 2 * BE_NF)) >> 1][(lane - (TPL - 2 * BE_NF)) & 1] = -1;      // (the last 22 lanes of the landmark's group: TPL >= 32)
         __syncthreads();
         if (b == 0) ETS(1);
-        const double lambda = valid ? st->inv_depth[b] : 1.0;
+        const double lambda = LPB == 1 ? lambda_early : (valid ? st->inv_depth[b] : 1.0);
         if (valid && lane < L.count) {
-            const BeFactor f = a.fac[L.first + lane];
+            const BeFactor f = LPB == 1 ? f_early : a.fac[L.first + lane];
             double r[2], Ji[12], Jj[12], Jl[2];
-            proj_factor<FULL, false>(f, fg[f.fi], fg[f.fj], ric[0], tic[0], ric[1], tic[1], lambda, st->td, r, Ji, Jj, Jl, nullptr, nullptr, nullptr);
+            proj_factor<FULL, false>(f, fg[f.fi], fg[f.fj], ric[0], tic[0], ric[1], tic[1], lambda, LPB == 1 ? td_early : st->td, r, Ji, Jj, Jl, nullptr, nullptr, nullptr);
             double rho0, sc;
             huber1(r[0] * r[0] + r[1] * r[1], rho0, sc);
             s_cost[lane] = 0.5 * rho0;
@@ -121,6 +209,8 @@ __device__ __forceinline__ void be_eval_body(const ARGS& a, int mode, int bg) {
         const unsigned long long votes = __ballot(wl < a.dims.nframes && (wl == anchor || s_flist[wl < BE_NF ? wl : 0][0] >= 0 || s_flist[wl < BE_NF ? wl : 0][1] >= 0));
         const int obs = (int)((votes >> (((int)threadIdx.x & 63) & ~(GL - 1))) & ((1ull << BE_NF) - 1));
         if (lane == 0 && mode != BE_EVAL_CAND_COST) a.lm_obs[b] = obs;
+        if constexpr (LPB == 1) ev_packet_256(Jb, s_two, s_flist, nf, anchor, obs, cost, lane, o_packets, b);
+        else
         for (int e = lane; e < BE_PK_SIZE; e += TPL) {
             if (e >= BE_PK_GP && e < BE_PK_DA + BE_NF * 36) {
                 const int fa = e < BE_PK_DD ? (e - BE_PK_GP) / 6 : (e < BE_PK_DA ? (e - BE_PK_DD) / 36 : (e - BE_PK_DA) / 36);
@@ -193,11 +283,63 @@ __device__ __forceinline__ void be_eval_body(const ARGS& a, int mode, int bg) {
         const BeImu* m = &s_m;
         double* Jraw = s_imu; double* Jw = s_imu + 450; double* rr = s_imu + 900;      // rr[0..14] raw, rr[15..29] whitened
         for (int i = lane; i < 450; i += EV_THREADS) Jraw[i] = 0.0;
+        // single-window form: the four state blocks the factor reads (pose_i 7, sb_i 9, pose_j 7, sb_j 9) are staged with the record, by the last wave — they were lane 0's
+        // global loads BEHIND the barrier
+        __shared__ double s_par[32];
+        if constexpr (LPB == 1) {
+            const int t = lane - (EV_THREADS - 32);
+            if (t >= 0) {
+                const int fi = a.imu[k].fi, fj = a.imu[k].fj;
+                s_par[t] = t < 7 ? st->pose[fi][t] : t < 16 ? st->sb[fi][t - 7] : t < 23 ? st->pose[fj][t - 16] : st->sb[fj][t - 23];
+            }
+        }
         __syncthreads();
         if (b == nlm) ETS(9);
-        if (lane == 0) imu_raw<FULL>(*m, a.g_norm, st->pose[m->fi], st->sb[m->fi], st->pose[m->fj], st->sb[m->fj], rr, Jraw);
+        if constexpr (LPB == 1) {
+            // the Jacobian's blocks hang off a short common prefix: one lane of EVERY wave evaluates the prefix (the same instructions on the same inputs) and its share of
+            // the blocks, the two quaternion-product blocks on different waves (imu_raw_sel: the block order of be_factor_dev.h)
+            if (FULL) {
+                constexpr unsigned SEL[4] = {
+                    BE_IMU_SEL_R | BE_IMU_SEL_BLK(0) | BE_IMU_SEL_BLK(1) | BE_IMU_SEL_BLK(3) | BE_IMU_SEL_BLK(4),
+                    BE_IMU_SEL_BLK(2) | BE_IMU_SEL_BLK(8) | BE_IMU_SEL_BLK(13) | BE_IMU_SEL_BLK(15),
+                    BE_IMU_SEL_BLK(7) | BE_IMU_SEL_BLK(5) | BE_IMU_SEL_BLK(6) | BE_IMU_SEL_BLK(9) | BE_IMU_SEL_BLK(10),
+                    BE_IMU_SEL_BLK(14) | BE_IMU_SEL_BLK(11) | BE_IMU_SEL_BLK(12) | BE_IMU_SEL_BLK(16) | BE_IMU_SEL_BLK(17) };
+                static_assert((SEL[0] | SEL[1] | SEL[2] | SEL[3]) == (2u << BE_IMU_BLOCKS) - 1 && (SEL[0] & SEL[1]) == 0 && ((SEL[0] | SEL[1]) & SEL[2]) == 0 && ((SEL[0] | SEL[1] | SEL[2]) & SEL[3]) == 0,
+                              "every block and the residual on exactly one wave");
+                if ((lane & 63) == 0) {
+                    const int w = lane >> 6;
+                    imu_raw_sel<true>(*m, a.g_norm, s_par, s_par + 7, s_par + 16, s_par + 23, w == 0 ? SEL[0] : w == 1 ? SEL[1] : w == 2 ? SEL[2] : SEL[3], rr, Jraw);
+                }
+            } else if (lane == 0) imu_raw<false>(*m, a.g_norm, s_par, s_par + 7, s_par + 16, s_par + 23, rr, Jraw);
+        } else if (lane == 0) imu_raw<FULL>(*m, a.g_norm, st->pose[m->fi], st->sb[m->fi], st->pose[m->fj], st->sb[m->fj], rr, Jraw);
         __syncthreads();
         if (b == nlm) ETS(10);
+        if constexpr (LPB == 1) {
+            // whitening with the fifteen terms' reads issued together; added in ascending q from the diagonal on, as the triangular loops below do
+            const int tr = lane - (EV_THREADS - 15);          // the residual on the last wave's upper lanes (they hold one Jacobian entry, the others two)
+            if (tr >= 0) {
+                double A[15], R[15];
+#pragma unroll
+                for (int q = 0; q < 15; ++q) { A[q] = m->sqrt_info[tr * 15 + q]; R[q] = rr[q]; }
+                double s = 0;
+#pragma unroll
+                for (int q = 0; q < 15; ++q) if (q >= tr) s += A[q] * R[q];
+                rr[15 + tr] = s;
+            }
+            if (FULL) {
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const int e = lane + EV_THREADS * t, ec = e < 450 ? e : 0, i = ec / 30, cc = ec - i * 30;
+                    double A[15], B[15];
+#pragma unroll
+                    for (int q = 0; q < 15; ++q) { A[q] = m->sqrt_info[i * 15 + q]; B[q] = Jraw[q * 30 + cc]; }
+                    double s = 0;
+#pragma unroll
+                    for (int q = 0; q < 15; ++q) if (q >= i) s += A[q] * B[q];
+                    if (e < 450) Jw[e] = s;
+                }
+            }
+        } else {
         if (lane < 15) { double s = 0; for (int q = lane; q < 15; ++q) s += m->sqrt_info[lane * 15 + q] * rr[q]; rr[15 + lane] = s; }
         if (FULL)
             for (int e = lane; e < 450; e += EV_THREADS) {
@@ -205,6 +347,7 @@ __device__ __forceinline__ void be_eval_body(const ARGS& a, int mode, int bg) {
                 for (int q = i; q < 15; ++q) s += m->sqrt_info[i * 15 + q] * Jraw[q * 30 + cc];
                 Jw[e] = s;
             }
+        }
         __syncthreads();
         if (b == nlm) ETS(11);
         double cost = 0;
@@ -214,11 +357,43 @@ __device__ __forceinline__ void be_eval_body(const ARGS& a, int mode, int bg) {
         if (!FULL) return;
         double* o = o_imu + (size_t)k * IMU_OUT_STRIDE;
         if (lane == 0) o[0] = cost;
+        if constexpr (LPB == 1) {
+            // g on the last wave's upper lanes (three H entries each, the lower lanes four); H two entries at a time, their thirty operand pairs read together
+            const int tg = lane - (EV_THREADS - 30);
+            if (tg >= 0) {
+                double A[15], R[15];
+#pragma unroll
+                for (int i = 0; i < 15; ++i) { A[i] = Jw[i * 30 + tg]; R[i] = rr[15 + i]; }
+                double s = 0;
+#pragma unroll
+                for (int i = 0; i < 15; ++i) s += A[i] * R[i];
+                o[1 + tg] = s;
+            }
+#pragma unroll
+            for (int t0 = 0; t0 < 4; t0 += 2) {
+                double A[2][15], B[2][15];
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const int e = lane + EV_THREADS * (t0 + t), ec = e < 900 ? e : 0, r0 = ec / 30, c0 = ec - r0 * 30;
+#pragma unroll
+                    for (int i = 0; i < 15; ++i) { A[t][i] = Jw[i * 30 + r0]; B[t][i] = Jw[i * 30 + c0]; }
+                }
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const int e = lane + EV_THREADS * (t0 + t);
+                    double s = 0;
+#pragma unroll
+                    for (int i = 0; i < 15; ++i) s += A[t][i] * B[t][i];
+                    if (e < 900) o[31 + e] = s;
+                }
+            }
+        } else {
         if (lane < 30) { double s = 0; for (int i = 0; i < 15; ++i) s += Jw[i * 30 + lane] * rr[15 + i]; o[1 + lane] = s; }
         for (int e = lane; e < 900; e += EV_THREADS) {
             const int r0 = e / 30, c0 = e - r0 * 30; double s = 0;
             for (int i = 0; i < 15; ++i) s += Jw[i * 30 + r0] * Jw[i * 30 + c0];
             o[31 + e] = s;
+        }
         }
         if (b == nlm) ETS(12);
       }

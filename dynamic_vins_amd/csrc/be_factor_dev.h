@@ -107,9 +107,15 @@ BE_HD m33 qlqr_br(quat a, quat b) {        // bottom-right 3x3 of Qleft(a) * Qri
     return o;
 }
 
+// Block-selecting form (the one source of the arithmetic): bit 0 of sel = the residual, bit 1 + k = Jacobian block k in the order the blocks are written below
+// (BE_IMU_BLOCKS of them).  Every block hangs off the same short prefix and has its own expression, so callers that hold several waves (be_eval's IMU workgroup)
+// give each wave a share of the blocks; whatever is selected gets exactly the bits imu_raw gives it.
+#define BE_IMU_BLOCKS 18
+#define BE_IMU_SEL_R 1u
+#define BE_IMU_SEL_BLK(k) (2u << (k))
 template <bool JAC>
-BE_HD void imu_raw(const BeImu& m, double g_norm, const double* pose_i, const double* sb_i, const double* pose_j, const double* sb_j,
-                   double* r15, double* J /* 15 x 30, pre-zeroed */) {
+BE_HD void imu_raw_sel(const BeImu& m, double g_norm, const double* pose_i, const double* sb_i, const double* pose_j, const double* sb_j,
+                       unsigned sel, double* r15, double* J /* 15 x 30, pre-zeroed */) {
     const d3 G = mk3(0, 0, g_norm);
     const d3 Pi = P3(pose_i), Pj = P3(pose_j); const quat Qi = Q4(pose_i), Qj = Q4(pose_j);
     const d3 Vi = P3(sb_i), Bai = P3(sb_i + 3), Bgi = P3(sb_i + 6), Vj = P3(sb_j), Baj = P3(sb_j + 3), Bgj = P3(sb_j + 6);
@@ -127,24 +133,40 @@ BE_HD void imu_raw(const BeImu& m, double g_norm, const double* pose_i, const do
     const d3 rq = qvec(qmul(qinv(cq), qmul(Qi_inv, Qj))) * 2.0;
     const d3 rv = b - cv;
     const d3 rba = Baj - Bai, rbg = Bgj - Bgi;
-    for (int k = 0; k < 3; ++k) { r15[k] = get(rp, k); r15[3 + k] = get(rq, k); r15[6 + k] = get(rv, k); r15[9 + k] = get(rba, k); r15[12 + k] = get(rbg, k); }
+    if (sel & BE_IMU_SEL_R)
+        for (int k = 0; k < 3; ++k) { r15[k] = get(rp, k); r15[3 + k] = get(rq, k); r15[6 + k] = get(rv, k); r15[9 + k] = get(rba, k); r15[12 + k] = get(rbg, k); }
     if (!JAC) return;
     const m33 RiT = qR(Qi_inv);
+#define BE_IMU_ON(k) (sel & BE_IMU_SEL_BLK(k))
     // pose_i: cols 0..5
-    set33(J, 30, 0, 0, scale(RiT, -1.0));
-    set33(J, 30, 0, 3, skew(a));
-    set33(J, 30, 3, 3, scale(qlqr_br(qmul(qinv(Qj), Qi), cq), -1.0));
-    set33(J, 30, 6, 3, skew(b));
+    if (BE_IMU_ON(0)) set33(J, 30, 0, 0, scale(RiT, -1.0));
+    if (BE_IMU_ON(1)) set33(J, 30, 0, 3, skew(a));
+    if (BE_IMU_ON(2)) set33(J, 30, 3, 3, scale(qlqr_br(qmul(qinv(Qj), Qi), cq), -1.0));
+    if (BE_IMU_ON(3)) set33(J, 30, 6, 3, skew(b));
     // sb_i: cols 6..14
-    set33(J, 30, 0, 6, scale(RiT, -dt)); set33(J, 30, 0, 9, scale(dp_dba, -1.0)); set33(J, 30, 0, 12, scale(dp_dbg, -1.0));
-    set33(J, 30, 3, 12, scale(mul(qleft_br(qmul(qmul(qinv(Qj), Qi), dq)), dq_dbg), -1.0));
-    set33(J, 30, 6, 6, scale(RiT, -1.0)); set33(J, 30, 6, 9, scale(dv_dba, -1.0)); set33(J, 30, 6, 12, scale(dv_dbg, -1.0));
-    set33(J, 30, 9, 9, scale(eye3(), -1.0)); set33(J, 30, 12, 12, scale(eye3(), -1.0));
+    if (BE_IMU_ON(4)) set33(J, 30, 0, 6, scale(RiT, -dt));
+    if (BE_IMU_ON(5)) set33(J, 30, 0, 9, scale(dp_dba, -1.0));
+    if (BE_IMU_ON(6)) set33(J, 30, 0, 12, scale(dp_dbg, -1.0));
+    if (BE_IMU_ON(7)) set33(J, 30, 3, 12, scale(mul(qleft_br(qmul(qmul(qinv(Qj), Qi), dq)), dq_dbg), -1.0));
+    if (BE_IMU_ON(8)) set33(J, 30, 6, 6, scale(RiT, -1.0));
+    if (BE_IMU_ON(9)) set33(J, 30, 6, 9, scale(dv_dba, -1.0));
+    if (BE_IMU_ON(10)) set33(J, 30, 6, 12, scale(dv_dbg, -1.0));
+    if (BE_IMU_ON(11)) set33(J, 30, 9, 9, scale(eye3(), -1.0));
+    if (BE_IMU_ON(12)) set33(J, 30, 12, 12, scale(eye3(), -1.0));
     // pose_j: cols 15..20
-    set33(J, 30, 0, 15, RiT);
-    set33(J, 30, 3, 18, qleft_br(qmul(qinv(cq), qmul(Qi_inv, Qj))));
+    if (BE_IMU_ON(13)) set33(J, 30, 0, 15, RiT);
+    if (BE_IMU_ON(14)) set33(J, 30, 3, 18, qleft_br(qmul(qinv(cq), qmul(Qi_inv, Qj))));
     // sb_j: cols 21..29
-    set33(J, 30, 6, 21, RiT); set33(J, 30, 9, 24, eye3()); set33(J, 30, 12, 27, eye3());
+    if (BE_IMU_ON(15)) set33(J, 30, 6, 21, RiT);
+    if (BE_IMU_ON(16)) set33(J, 30, 9, 24, eye3());
+    if (BE_IMU_ON(17)) set33(J, 30, 12, 27, eye3());
+#undef BE_IMU_ON
+}
+
+template <bool JAC>
+BE_HD void imu_raw(const BeImu& m, double g_norm, const double* pose_i, const double* sb_i, const double* pose_j, const double* sb_j,
+                   double* r15, double* J /* 15 x 30, pre-zeroed */) {
+    imu_raw_sel<JAC>(m, g_norm, pose_i, sb_i, pose_j, sb_j, ~0u, r15, J);
 }
 
 }  // namespace be
