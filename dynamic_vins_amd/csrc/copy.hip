@@ -7,6 +7,7 @@
 // reference's system/main.cpp:178-330 layout).  Pinned host memory is mapped into the device's address space: a kernel on the consumer's own stream
 // reads it over PCIe directly (16 B per lane, four loads in flight per lane), stream order does the rest, and no copy engine exists in the per-frame path any more.
 // Copies from / to CALLER memory (frames, masks handed over as DV_MEM_HOST) stay hipMemcpy: that memory may be pageable.
+// Also here: the one static-instance unmask kernel, which makes the copy of a caller's device mask in the same pass.
 #include "dv_internal.h"
 #include <algorithm>
 #include <cstdlib>
@@ -52,47 +53,25 @@ hipError_t dv_copy_async(void* dst, const void* src, size_t bytes, hipStream_t s
 
 int dv_copy_prepare() { hipFuncAttributes fa; return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(dv_copy_kernel)) == hipSuccess ? 0 : -1; }
 
-// FeatureTrack's static-instance unmasking (system/main.cpp:217-245): the ROI mask lives in pinned host memory and is read in place
-__global__ __launch_bounds__(256) void dv_unmask_kernel(uint8_t* __restrict__ inv_mask, int pitch, int W, int H, int x0, int y0, int w, int h, const uint8_t* __restrict__ roi) {
-    const int c = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
-    if (c >= w || r >= h) return;
-    const int x = x0 + c, y = y0 + r;
-    if (x < W && y < H && roi[(size_t)r * w + c] >= 1) inv_mask[(size_t)y * pitch + x] = 255;
-}
-void dv_launch_unmask(uint8_t* inv_mask, int pitch, int W, int H, int x0, int y0, int w, int h, const uint8_t* roi_mask, hipStream_t s) {
-    if (w > 0 && h > 0) hipLaunchKernelGGL(dv_unmask_kernel, dim3((w + 255) / 256, h), dim3(256), 0, s, inv_mask, pitch, W, H, x0, y0, w, h, roi_mask);
-}
-
-// The key-image form (dv_track_unmask_static_keys): the instance's ROI mask is the comparison of the frame's key image with the instance's key, read where it lies
-// (HBM, or the caller's pinned host memory), one dword per lane along a row; the rectangle was checked against the image by the entry
-__global__ __launch_bounds__(256) void dv_unmask_keys_kernel(uint8_t* __restrict__ inv_mask, int pitch, int W, int H, int x0, int y0, int w, int h, const uint32_t* __restrict__ key, int kpitch, uint32_t id) {
-    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
-    if (c >= w || r >= h) return;
-    const int x = x0 + c, y = y0 + r;
-    if (x < W && y < H && key[(size_t)y * kpitch + x] == id) inv_mask[(size_t)y * pitch + x] = 255;
-}
-void dv_launch_unmask_keys(uint8_t* inv_mask, int pitch, int W, int H, int x0, int y0, int w, int h, const uint32_t* key, int kpitch, uint32_t id, hipStream_t s) {
-    if (w > 0 && h > 0) hipLaunchKernelGGL(dv_unmask_keys_kernel, dim3((w + 63) / 64, (h + 3) / 4), dim3(64, 4), 0, s, inv_mask, pitch, W, H, x0, y0, w, h, key, kpitch, id);
-}
-
-// The same over a job table, for the members of a dv_batch round (front_track.hip): ALL staged rectangles of ALL members in one launch, and the copy of a caller's device
-// mask into the member's own buffer with it (the caller's buffer is never written).  Grid (ceil(W / 256), H, jobs); a pixel becomes 255 where any rectangle of its member
-// covers it with roi >= 1 — dv_unmask_kernel's rule, whose writes commute — and keeps the source's value elsewhere
-__global__ __launch_bounds__(256) void dv_unmask_multi_kernel(const DvUnmaskJob* __restrict__ jobs, const DvUnmaskRect* __restrict__ rects) {
+// FeatureTrack's static-instance unmasking (system/main.cpp:217-245): the static instances' pixels leave the merged mask (inv_merge_mask = 255 there) before anything
+// reads it.  ALL staged rectangles of ALL masks of a launch — one for a sequence's own entry, one per member for a dv_batch round (front_track.hip) — and the copy of a
+// caller's device mask into the library's buffer with it (the caller's buffer is never written).  Grid (ceil(W / 256), H, jobs); whether a rectangle's instance has the
+// pixel is pix_src.h's answer, whatever the source (pinned ROI mask, key image, stack plane).  All writes of a job are 255 or the source's value: they commute
+__global__ __launch_bounds__(256) void dv_unmask_kernel(const DvUnmaskJob* __restrict__ jobs, const DvUnmaskRect* __restrict__ rects) {
     const DvUnmaskJob j = jobs[blockIdx.z];
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= j.W || y >= j.H) return;
-    uint8_t v = j.src ? j.src[(size_t)y * j.spitch + x] : j.dst[(size_t)y * j.dpitch + x];
-    for (int k = j.first; k < j.first + j.n; ++k) {
-        const DvUnmaskRect r = rects[k];
-        const int c = x - r.x, q = y - r.y;
-        if (c >= 0 && c < r.w && q >= 0 && q < r.h && r.roi[(size_t)q * r.w + c] >= 1) v = 255;
+    bool hit = false;
+    for (int k = j.first; k < j.first + j.n && !hit; ++k) {
+        const DvUnmaskRect& r = rects[k];
+        hit = x >= r.x && x - r.x < r.w && y >= r.y && y - r.y < r.h && dv_pix_has(r.src, x, y);
     }
-    j.dst[(size_t)y * j.dpitch + x] = v;
+    if (hit) j.dst[(size_t)y * j.dpitch + x] = 255;
+    else if (j.src) j.dst[(size_t)y * j.dpitch + x] = j.src[(size_t)y * j.spitch + x];
 }
-void dv_launch_unmask_multi(const DvUnmaskJob* jobs_dev, int n_jobs, const DvUnmaskRect* rects_dev, int w_max, int h_max, hipStream_t s) {
+void dv_launch_unmask(const DvUnmaskJob* jobs_dev, int n_jobs, const DvUnmaskRect* rects_dev, int w_max, int h_max, hipStream_t s) {
     if (n_jobs <= 0 || w_max <= 0 || h_max <= 0) return;
-    hipLaunchKernelGGL(dv_unmask_multi_kernel, dim3((w_max + 255) / 256, h_max, n_jobs), dim3(256), 0, s, jobs_dev, rects_dev);
+    hipLaunchKernelGGL(dv_unmask_kernel, dim3((w_max + 255) / 256, h_max, n_jobs), dim3(256), 0, s, jobs_dev, rects_dev);
 }
 
 // A queue's first dispatch of a kernel that needs scratch (private-segment) memory makes the runtime allocate that memory for the queue — a device allocation plus a queue

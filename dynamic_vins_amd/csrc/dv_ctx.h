@@ -215,14 +215,16 @@ struct dv_ctx {
     DevBuf cand_buf; int cand_cap = 0; int* n_cand = nullptr; unsigned* max_ord = nullptr; int* err_flag = nullptr;
     DevBuf hw_buf; int hw_radius = -1;
     DevBuf mask_buf;
-    // dv_track_unmask_static: the ROI masks of the static instances of the next frame, staged in pinned memory at the call (rect + offset into unmask_pinned), applied by a
-    // kernel behind the mask's upload in dv_track_stereo_enqueue
-    struct UnmaskJob { int x, y, w, h; size_t off; };
-    std::vector<UnmaskJob> unmask; void* unmask_pinned = nullptr; size_t unmask_pinned_bytes = 0;
-    // dv_track_unmask_static_keys: the same rectangles, the per-pixel test being key_image == id.  The key image is read in place (device / pinned) or staged once
-    // into unmask_keys_buf by the enqueue (host).  Dropped on EVERY return of the next dv_track_stereo_enqueue / dv_batch_track_enqueue
-    struct UnmaskKeyJob { int x, y, w, h; uint32_t id; };
-    std::vector<UnmaskKeyJob> unmask_keys; const uint32_t* unmask_key_img = nullptr; int unmask_key_stride = 0, unmask_key_mem = 0; DevBuf unmask_keys_buf;
+    // dv_track_unmask_static / _keys / _planes: the static instances' rectangles of the NEXT frame, one list whatever the form, and where that frame's membership is
+    // read (unmask_src: ROI masks copied into unmask_pinned at the call | the key image | the checked mask stack, strides filled in).  A later call of any of the three
+    // replaces what an earlier one staged; EVERY return of the next dv_track_stereo_enqueue / dv_batch_track_enqueue drops the list (UnmaskGuard, front_track.hip).
+    // unmask_pinned = [the single entry's job and rectangle tables, read in place by the kernel | the ROI masks], allocated by dv_create for the tables of
+    // DV_STACK_MAX_PLANES rectangles and grown by the staging entries; a host key image or a host stack the frame's stage did not stage is staged once into
+    // unmask_src_buf by the enqueue
+    struct UnmaskRect { int x, y, w, h; size_t off; uint32_t id; int plane; };      // off: the ROI mask in unmask_pinned; id: the key; plane: the stack's plane
+    enum UnmaskForm { UNMASK_MASKS = 0, UNMASK_KEYS, UNMASK_PLANES };      // which of the three entries staged the list (a stack's element kind is the stack's own field)
+    struct UnmaskSrc { int form = UNMASK_MASKS; const uint32_t* key_img = nullptr; int key_stride = 0, key_mem = 0; dv_mask_stack stack{}; };
+    std::vector<UnmaskRect> unmask; UnmaskSrc unmask_src; void* unmask_pinned = nullptr; size_t unmask_pinned_bytes = 0; DevBuf unmask_src_buf;
     // dv_viode_frame_enqueue / _collect: thread T1's per-frame stage (label images -> inverse merged mask, key images, boxes) on the ctx's stream.  Two buffer sets
     // used alternately: set[cur] belongs to the frame enqueued last; the key images of the frame before stay intact while its objects are tracked
     struct ViodeFrame* viode = nullptr;      // (defined in dvins_api.hip, released by dv_destroy)
@@ -234,10 +236,6 @@ struct dv_ctx {
     struct MotTracker* mot = nullptr;
     // dv_reid_*: the ReID extractor in front of it (colour image + rectangles -> embeddings; reid.hip, released by dv_reid_release)
     struct ReidNet* reid = nullptr;
-    // dv_track_unmask_static_planes: the same rectangles, the per-pixel test being "the detection's plane has the pixel".  Dropped on EVERY return of the next
-    // dv_track_stereo_enqueue / dv_batch_track_enqueue; a host stack the frame's stage did not stage is staged into unmask_stack_buf by that enqueue
-    struct UnmaskPlaneJob { int x, y, w, h, plane; };
-    std::vector<UnmaskPlaneJob> unmask_planes; dv_mask_stack unmask_stack{}; DevBuf unmask_stack_buf;
     DevBuf undist_buf[2]; bool undist[2] = { false, false }; int undist_w = 0, undist_h = 0;      // cfg::is_undistort_input: fixed-point maps per camera (map1 | map2)
     bool cam_switched = false; dv_cam cam_orig[2]{};      // dv_undistort_setup: cfg.cam0 / cam1 hold (newK, 0); the cameras the ctx was created with, restored when the maps are removed
     DevBuf out_buf; dv_feat* out_dev = nullptr; int* nout_dev = nullptr;
@@ -306,6 +304,8 @@ struct HostScope {
 void dv_harvest_timers(dv_ctx* ctx, hipStream_t synced);      // harvests the timers recorded on `synced` (must be idle)
 // ---- host helpers of dvins_api.hip that the tracker entries (front_track.hip) share with the operator-level entries ----
 int dv_ensure_hw(dv_ctx* ctx, int radius);         // the disc half widths of `radius` in hw_buf
+size_t dv_unmask_tab_bytes(size_t n);             // front_track.hip: the head of unmask_pinned that holds the tables of n rectangles
+void circle_half_widths(int radius, std::vector<uint8_t>& hw);      // hw[0..radius] of cv::circle's midpoint rasteriser (drawing.cpp Circle(), fill = true)
 int dv_ensure_cand(dv_ctx* ctx, int w, int h);     // the candidate buffer of a w x h image
 // One frame's way into a pyramid (an image or a pair) in the job types of the table kernels: filled by dv_plan_pyramids, launched by value (dv_launch_pyramids) or scattered into a dv_batch round's tables
 struct PyrPlan { bool has_l0, pair; int levels; DvLevel0Job l0; DvPyrJob down[DV_MAX_LEVELS - 1]; DvPyr apron[2]; };

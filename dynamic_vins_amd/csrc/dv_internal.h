@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 #include "../../include/dvins.h"
+#include "pix_src.h"
 
 #define DV_LK_WIN 21          // cv::Size(21,21) at every reference call site
 #define DV_MAX_LEVELS 4       // maxLevel = 3 -> 4 levels
@@ -118,29 +119,24 @@ void dv_launch_lk_cuda_track(const DvPyr& A, const DvPyr& B, const float2* pts_a
 void dv_launch_lk_cuda_track_multi(const DvLkJob* jobs_dev, int n_jobs, int n_max, int flow_back, float dist_thresh, hipStream_t s);      // the same over a job table: grid (n_max, n_jobs), maxLevel 3, 30 iterations
 void dv_launch_lk_cuda_generic(const DvPyr& A, const DvPyr& B, const float2* pts_a, int n, int max_level, int iters, int use_initial, float2* pts_b, uint8_t* status, hipStream_t s);
 void dv_launch_gftt_tile(const GfttTileArgs& a, hipStream_t s);
-// system/main.cpp:217-245: inv_mask(y0 + r, x0 + c) = 255 where roi_mask(r, c) >= 1 (a static instance's pixels become background); roi_mask: w x h bytes in PINNED host memory, read in place
-void dv_launch_unmask(uint8_t* inv_mask, int pitch, int W, int H, int x0, int y0, int w, int h, const uint8_t* roi_mask, hipStream_t s);
-// the same for a dv_batch round: job = one member's mask (src: the caller's device mask, copied to dst with the launch; null: dst holds it already) and its slice of the rectangle table
-struct DvUnmaskRect { const uint8_t* roi; int x, y, w, h; };
+// FeatureTrack's static-instance unmasking (system/main.cpp:217-245) over a job table, copy.hip: a job is one mask (src: the caller's device mask, copied to dst with the
+// launch; null: dst holds it already) and its slice of the rectangle table; a pixel becomes 255 where a rectangle of its job covers it and the rectangle's source has it
+// (pix_src.h), and keeps the source's value elsewhere.  Every rectangle lies inside what its source covers (checked by the entry that staged it).  Both tables are
+// device-addressable: HBM, or pinned host memory read in place
+struct DvUnmaskRect { DvPixSrc src; int x, y, w, h; };
 struct DvUnmaskJob { uint8_t* dst; const uint8_t* src; int dpitch, spitch, W, H, first, n; };
-void dv_launch_unmask_multi(const DvUnmaskJob* jobs_dev, int n_jobs, const DvUnmaskRect* rects_dev, int w_max, int h_max, hipStream_t s);
-// the key-image form (dv_track_unmask_static_keys): inv_mask(y0 + r, x0 + c) = 255 where key(y0 + r, x0 + c) == id; key: W x H uint32 (VIODE::PixelToKey), rows of kpitch ELEMENTS, device-addressable
-void dv_launch_unmask_keys(uint8_t* inv_mask, int pitch, int W, int H, int x0, int y0, int w, int h, const uint32_t* key, int kpitch, uint32_t id, hipStream_t s);
-// the ROI masks of all visible objects of a frame from its key image in ONE launch (dv_inst_track_enqueue_keys): dst(r, c) = key(y0 + r, x0 + c) == id ? 255 : 0 for
-// c < w, 0 for w <= c < dpitch (the padding carries a defined value), r < h.  kpitch in ELEMENTS; the rectangle lies inside the key image (checked by the caller)
-struct DvKeyRoiJob { const uint32_t* key; uint8_t* dst; int kpitch, x0, y0, w, h, dpitch; uint32_t id; int pad_; };
-void dv_launch_key_roi_mask_multi(const DvKeyRoiJob* jobs_dev, int n_jobs, int dpitch_max, int h_max, hipStream_t s);
+void dv_launch_unmask(const DvUnmaskJob* jobs_dev, int n_jobs, const DvUnmaskRect* rects_dev, int w_max, int h_max, hipStream_t s);
+// the ROI masks of all visible objects of a frame cut from a device-addressable source in ONE launch (inst_track.hip): dst(r, c) = src has (x0 + c, y0 + r) ? 255 : 0
+// for c < w, 0 for w <= c < dpitch (the padding carries a defined value), r < h.  dst 16-byte aligned, dpitch a multiple of 16; the rectangle lies inside the source
+struct DvRoiMaskJob { DvPixSrc src; uint8_t* dst; int dpitch, w, h, x0, y0; };
 // the detector's mask stack (inst_stack.hip; include/dvins.h dv_mask_stack): a device-addressable view of it, strides in BYTES
 struct DvStackSrc { const uint8_t* base; long long plane_stride; int row_stride, n_planes, kind; float thr; };
+// one plane of it, and a key image (rows of stride_bytes), as membership sources
+inline DvPixSrc dv_plane_src(const DvStackSrc& S, int plane) { return DvPixSrc{ S.base + (size_t)plane * S.plane_stride, S.row_stride, S.kind == DV_STACK_F32 ? DV_PIX_PLANE_F32 : DV_PIX_PLANE_U8, 0u, S.thr, 0, 0 }; }
+inline DvPixSrc dv_key_src(const uint32_t* img, int stride_bytes, uint32_t id) { return DvPixSrc{ (const uint8_t*)img, stride_bytes, DV_PIX_KEY_U32, id, 0.f, 0, 0 }; }
 // one pass over the stack: merge / inv (w x h bytes, tightly packed) and boxes[n_planes][4] = row_min, row_max, col_min, col_max (the caller initialises them to max, -1, max, -1)
 void dv_launch_inst_stack(const DvStackSrc& S, int w, int h, uint8_t* merge, uint8_t* inv, int32_t* boxes, hipStream_t s);
 void dv_launch_stack_finish_remap(const uint8_t* src, int spitch, int w, int h, uint8_t* merge, uint8_t* inv, hipStream_t s);      // merge = src made tight, inv = ~src
-// the ROI masks of all visible objects of a frame from their planes in ONE launch (dv_inst_track_enqueue_planes): dst(r, c) = plane has (y0 + r, x0 + c) ? 255 : 0 for c < w,
-// 0 for w <= c < dpitch, r < h.  dst 4-byte aligned, dpitch a multiple of 4; the rectangle lies inside the plane (checked by the caller)
-struct DvPlaneRoiJob { const uint8_t* plane; uint8_t* dst; int row_stride, x0, y0, w, h, dpitch, kind; float thr; };
-void dv_launch_plane_roi_mask_multi(const DvPlaneRoiJob* jobs_dev, int n_jobs, int dpitch_max, int h_max, hipStream_t s);
-// the plane form of dv_launch_unmask (dv_track_unmask_static_planes): inv_mask(y0 + r, x0 + c) = 255 where the plane has that pixel
-void dv_launch_unmask_plane(uint8_t* inv_mask, int pitch, int W, int H, int x0, int y0, int w, int h, const uint8_t* plane, int row_stride, int kind, float thr, hipStream_t s);
 hipError_t dv_copy_async(void* dst, const void* src, size_t bytes, hipStream_t s);      // copy.hip: device <-> PINNED host (or device <-> device) as a kernel on s — no copy engine in the per-frame path
 int  dv_launch_gftt_select(const GfttSelectArgs& a, hipStream_t s);
 void dv_launch_compact(const DvTrackState& tr, const uint8_t* in_mask, int mask_pitch, int sort_by_cnt, int* n_cand,

@@ -20,7 +20,7 @@ void dv_set_error(dv_ctx* ctx, const std::string& msg) {
 }
 
 // disc half-widths of cv::circle's midpoint rasteriser (drawing.cpp Circle(), fill = true)
-static void circle_half_widths(int radius, std::vector<uint8_t>& hw) {
+void circle_half_widths(int radius, std::vector<uint8_t>& hw) {
     hw.assign(radius + 1, 0);
     int err = 0, dx = radius, dy = 0, plus = 1, minus = (radius << 1) - 1;
     while (dx >= dy) {
@@ -295,6 +295,9 @@ dv_ctx* dv_create(const dv_config* cfg) {
     void* pinned = nullptr;
     if ((e = hipHostMalloc(&pinned, N * sizeof(dv_feat) + 256, hipHostMallocDefault)) != hipSuccess) return fail("hipHostMalloc", e);
     ctx->out_pinned = (dv_feat*)pinned; ctx->nout_pinned = (int*)((uint8_t*)pinned + N * sizeof(dv_feat)); ctx->err_pinned = ctx->nout_pinned + 1;
+    // the tables of the static-instance unmask launch (front_track.hip) are read in place from pinned memory: room for a full stack's rectangles from the start
+    if ((e = hipHostMalloc(&ctx->unmask_pinned, dv_unmask_tab_bytes(DV_STACK_MAX_PLANES), hipHostMallocDefault)) != hipSuccess) return fail("hipHostMalloc", e);
+    ctx->unmask_pinned_bytes = dv_unmask_tab_bytes(DV_STACK_MAX_PLANES);
     if (dv_reset(ctx) != 0) { std::string m = ctx->err; delete ctx; dv_set_error(nullptr, m); return nullptr; }
     return ctx;
 }
@@ -321,9 +324,9 @@ void dv_destroy(dv_ctx* ctx) {
     if (ctx->be_stream) (void)hipStreamDestroy(ctx->be_stream);
     if (ctx->out_pinned) (void)hipHostFree(ctx->out_pinned);
     if (ctx->unmask_pinned) (void)hipHostFree(ctx->unmask_pinned);
-    ctx->unmask_keys_buf.release();
+    ctx->unmask_src_buf.release();
     dv_viode_frame_release(ctx);
-    dv_inst_stack_frame_release(ctx); ctx->unmask_stack_buf.release();
+    dv_inst_stack_frame_release(ctx);
     dv_solo_head_release(ctx);
     dv_mot_release(ctx);
     dv_reid_release(ctx);

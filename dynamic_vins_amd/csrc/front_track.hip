@@ -42,6 +42,66 @@ static int front_plan_mask(dv_ctx* ctx, int mode, const uint8_t* mask, int mask_
     return 0;
 }
 
+// ---- the static instances' rectangles of a frame (dv_track_unmask_static / _keys / _planes): staged on the ctx, applied by ONE launch of the enqueue that follows ----
+// What is staged belongs to one frame: applied by the call this guard lives in, or dropped with whichever return ends it — no rectangle survives into a later frame
+struct UnmaskGuard {
+    dv_ctx* const* c; int n;
+    ~UnmaskGuard() { for (int i = 0; i < n; ++i) { c[i]->unmask.clear(); c[i]->unmask_src = dv_ctx::UnmaskSrc{}; } }
+};
+static const char* unmask_entry(int form) { return form == dv_ctx::UNMASK_MASKS ? "dv_track_unmask_static" : form == dv_ctx::UNMASK_KEYS ? "dv_track_unmask_static_keys" : "dv_track_unmask_static_planes"; }
+static bool unmask_selected(const dv_inst_det& d, const uint32_t* ids, int n) { return std::find(ids, ids + n, d.track_id) != ids + n; }
+static bool unmask_rect_ok(const dv_inst_det& d, int W, int H) { return d.w > 0 && d.h > 0 && d.x >= 0 && d.y >= 0 && d.w <= W && d.h <= H && d.x <= W - d.w && d.y <= H - d.h; }
+// unmask_pinned = [DvUnmaskJob | n DvUnmaskRect | ROI masks]: where the tables of n rectangles end
+size_t dv_unmask_tab_bytes(size_t n) { return (256 + n * sizeof(DvUnmaskRect) + 255) / 256 * 256; }
+// room for them and for roi_bytes of ROI masks, at the staging call: the frame before was collected, nothing on the device reads the block.  The tables of up to
+// DV_STACK_MAX_PLANES rectangles fit what dv_create allocated: the key and plane forms allocate nothing and wait for nothing here
+static int unmask_reserve(dv_ctx* ctx, size_t n, size_t roi_bytes) {
+    const size_t need = dv_unmask_tab_bytes(n) + roi_bytes;
+    if (ctx->unmask_pinned_bytes < need) {
+        DV_CHECK(hipStreamSynchronize(ctx->stream));          // (a previous frame's kernels may still read the old staging area)
+        if (ctx->unmask_pinned) (void)hipHostFree(ctx->unmask_pinned);
+        ctx->unmask_pinned = nullptr; ctx->unmask_pinned_bytes = 0;
+        // (the tables of a full stack's planes and, with ROI masks, a frame's worth from the start: the rectangles grow as objects come closer)
+        const size_t want = std::max<size_t>(2 * need, dv_unmask_tab_bytes(DV_STACK_MAX_PLANES) + (roi_bytes ? (size_t)ctx->cfg.width * ctx->cfg.height : 0));
+        DV_CHECK(hipHostMalloc(&ctx->unmask_pinned, want, hipHostMallocDefault));
+        ctx->unmask_pinned_bytes = want;
+    } else if (roi_bytes && ctx->last_done && ctx->last_done == ctx->done) DV_CHECK(hipEventSynchronize(ctx->done));      // the previous frame's unmask kernel has read the block (a no-op wait in the usual case: that frame was collected)
+    return 0;
+}
+// One mask's job and its rectangles, rects[first ...], from what is staged on ctx.  The frame's source is resolved on s: ROI masks lie in unmask_pinned, a device / pinned
+// key image or stack is read where it lies, a host one is staged once.  The job works in the ctx's own mask_buf: a host mask is there already, a caller's device mask is
+// copied by the launch that applies the rectangles and never written.  mask_buf holds align_up(w, 16) x h bytes (the caller's ensure, under its own error text)
+static int front_unmask_tables(dv_ctx* ctx, const FrontPlan& P, hipStream_t s, int first, DvUnmaskJob* job, DvUnmaskRect* rects) {
+    const dv_ctx::UnmaskSrc& U = ctx->unmask_src;
+    const int w = ctx->cfg.width, h = ctx->cfg.height, mp = align_up(w, 16);
+    const uint32_t* kimg = U.key_img; int kstride = U.key_stride;
+    DvStackSrc S{};
+    if (U.form == dv_ctx::UNMASK_KEYS && U.key_mem == DV_MEM_HOST) {
+        DV_CHECK(ctx->unmask_src_buf.ensure((size_t)4 * w * h));
+        DV_CHECK(hipMemcpy2DAsync(ctx->unmask_src_buf.p, (size_t)4 * w, kimg, (size_t)kstride, (size_t)4 * w, h, hipMemcpyHostToDevice, s));
+        kimg = (const uint32_t*)ctx->unmask_src_buf.p; kstride = 4 * w;
+    }
+    if (U.form == dv_ctx::UNMASK_PLANES && dv_stack_resolve(ctx, U.stack, ctx->unmask_src_buf, s, &S)) return -1;
+    uint8_t* own = (uint8_t*)ctx->mask_buf.p;
+    *job = DvUnmaskJob{ own, P.mask == own ? nullptr : P.mask, mp, P.mask_pitch, w, h, first, (int)ctx->unmask.size() };
+    for (const dv_ctx::UnmaskRect& r : ctx->unmask) {
+        const DvPixSrc src = U.form == dv_ctx::UNMASK_MASKS ? DvPixSrc{ (const uint8_t*)ctx->unmask_pinned + r.off, r.w, DV_PIX_ROI_U8, 0u, 0.f, r.x, r.y }
+                           : U.form == dv_ctx::UNMASK_KEYS ? dv_key_src(kimg, kstride, r.id) : dv_plane_src(S, r.plane);
+        rects[first++] = DvUnmaskRect{ src, r.x, r.y, r.w, r.h };
+    }
+    return 0;
+}
+// the single entry's step (system/main.cpp:217-245, before anything reads the mask): tables in unmask_pinned, read in place, one launch; the stages then read mask_buf
+static int front_apply_unmask(dv_ctx* ctx, int mode, hipStream_t s, FrontPlan& P) {
+    if (ctx->unmask.empty()) return 0;
+    if (!P.mask) DV_FAIL(std::string(unmask_entry(ctx->unmask_src.form)) + ": the frame carries no mask");
+    DvUnmaskJob* job = (DvUnmaskJob*)ctx->unmask_pinned; DvUnmaskRect* rects = (DvUnmaskRect*)((uint8_t*)ctx->unmask_pinned + 256);
+    DV_CHECK(ctx->mask_buf.ensure((size_t)align_up(ctx->cfg.width, 16) * ctx->cfg.height));
+    if (front_unmask_tables(ctx, P, s, 0, job, rects)) return -1;
+    dv_launch_unmask(job, 1, rects, job->W, job->H, s);
+    return front_plan_mask(ctx, mode, job->dst, job->dpitch, P);
+}
+
 // Everything a frame needs before its first launch: the member-level checks, the lazily created resources, the frames' and the mask's way to the device (copies on s)
 // and the stages' arguments under the frame's mode.  The frame is built in the pyramid the ctx is NOT looking at (cur ^ 1) and the ctx is not changed: front_commit
 // does that, once the whole enqueue has succeeded, so that a refused or failed enqueue of either kind leaves no flipped `cur` and no pending frame behind.
@@ -135,8 +195,7 @@ int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gr
                             const uint8_t* mask_or_null, int mode, int mem) {
     if (!ctx) return -1;
     HostScope hs(ctx, "h_front_enqueue");
-    // what dv_track_unmask_static_keys staged belongs to THIS call: applied below, or dropped with whichever return ends the call
-    struct KeyJobsGuard { dv_ctx* c; ~KeyJobsGuard() { c->unmask_keys.clear(); c->unmask_key_img = nullptr; c->unmask_planes.clear(); c->unmask_stack = dv_mask_stack{}; } } key_jobs_guard{ ctx };
+    dv_ctx* const self[1] = { ctx }; UnmaskGuard unmask_guard{ self, 1 };
     if (!gray0) DV_FAIL("dv_track_stereo: gray0 is null");
     if (w != ctx->cfg.width || h != ctx->cfg.height) DV_FAIL("dv_track_stereo: image size differs from config (reference: std::terminate, main.cpp:95-99)");
     if (ctx->pending) DV_FAIL("dv_track_stereo_enqueue: previous frame not collected");
@@ -164,48 +223,7 @@ int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gr
         if (P.cuda_prev) { dv_launch_cuda_pyramids(P.cpyr_prev, s); ctx->leftc_valid[cur ^ 1] = true; }
         DV_CHECK(hipGetLastError());
     }
-    // the unmasking forms below write the mask: a caller's device buffer is never written to, they work on a copy in mask_buf
-    auto own_mask = [&](const uint8_t*& mask_dev, int& mask_pitch) -> int {
-        if (mask_dev == (const uint8_t*)ctx->mask_buf.p) return 0;
-        const int mp = align_up(w, 16);
-        DV_CHECK(ctx->mask_buf.ensure((size_t)mp * h));
-        DV_CHECK(hipMemcpy2DAsync(ctx->mask_buf.p, mp, mask_dev, mask_pitch, w, h, hipMemcpyDeviceToDevice, s));
-        mask_dev = (const uint8_t*)ctx->mask_buf.p; mask_pitch = mp;
-        return 0;
-    };
-    if (!ctx->unmask.empty()) {          // system/main.cpp:217-245: the static instances' pixels leave the merged mask (inv_merge_mask = 255 there) before anything reads it
-        const uint8_t* mask_dev = P.mask; int mask_pitch = P.mask_pitch;
-        if (!mask_dev) { ctx->unmask.clear(); DV_FAIL("dv_track_unmask_static: the frame carries no mask"); }
-        if (own_mask(mask_dev, mask_pitch)) return -1;
-        for (const dv_ctx::UnmaskJob& j : ctx->unmask)
-            dv_launch_unmask((uint8_t*)ctx->mask_buf.p, mask_pitch, w, h, j.x, j.y, j.w, j.h, (const uint8_t*)ctx->unmask_pinned + j.off, s);
-        ctx->unmask.clear();
-        if (front_plan_mask(ctx, mode, mask_dev, mask_pitch, P)) return -1;
-    }
-    if (!ctx->unmask_keys.empty()) {     // the key-image form of the same step (dv_track_unmask_static_keys): the per-pixel test is key == id
-        const uint8_t* mask_dev = P.mask; int mask_pitch = P.mask_pitch;
-        if (!mask_dev) DV_FAIL("dv_track_unmask_static_keys: the frame carries no mask");
-        if (own_mask(mask_dev, mask_pitch)) return -1;
-        const uint32_t* kimg = ctx->unmask_key_img; int kpitch = ctx->unmask_key_stride / 4;
-        if (ctx->unmask_key_mem == DV_MEM_HOST) {                   // staged once for the frame
-            DV_CHECK(ctx->unmask_keys_buf.ensure((size_t)4 * w * h));
-            DV_CHECK(hipMemcpy2DAsync(ctx->unmask_keys_buf.p, (size_t)4 * w, kimg, (size_t)ctx->unmask_key_stride, (size_t)4 * w, h, hipMemcpyHostToDevice, s));
-            kimg = (const uint32_t*)ctx->unmask_keys_buf.p; kpitch = w;
-        }
-        for (const dv_ctx::UnmaskKeyJob& j : ctx->unmask_keys)
-            dv_launch_unmask_keys((uint8_t*)ctx->mask_buf.p, mask_pitch, w, h, j.x, j.y, j.w, j.h, kimg, kpitch, j.id, s);
-        if (front_plan_mask(ctx, mode, mask_dev, mask_pitch, P)) return -1;
-    }
-    if (!ctx->unmask_planes.empty()) {   // the mask-stack form (dv_track_unmask_static_planes): the per-pixel test is "the detection's plane has the pixel"
-        const uint8_t* mask_dev = P.mask; int mask_pitch = P.mask_pitch;
-        if (!mask_dev) DV_FAIL("dv_track_unmask_static_planes: the frame carries no mask");
-        if (own_mask(mask_dev, mask_pitch)) return -1;
-        DvStackSrc S{};
-        if (dv_stack_resolve(ctx, ctx->unmask_stack, ctx->unmask_stack_buf, s, &S)) return -1;
-        for (const dv_ctx::UnmaskPlaneJob& j : ctx->unmask_planes)
-            dv_launch_unmask_plane((uint8_t*)ctx->mask_buf.p, mask_pitch, w, h, j.x, j.y, j.w, j.h, S.base + (size_t)j.plane * S.plane_stride, S.row_stride, S.kind, S.thr, s);
-        if (front_plan_mask(ctx, mode, mask_dev, mask_pitch, P)) return -1;
-    }
+    if (front_apply_unmask(ctx, mode, s, P)) return -1;
     if (P.has_erode) { const DvErodeJob& k = P.erode; dv_launch_erode(k.src, k.w, k.h, k.spitch, k.k, k.tmp, k.tpitch, k.dst, k.dpitch, s); }
     if (ctx->have_prev) {
         StageScope sc(ctx, "lk_temporal");
@@ -244,41 +262,41 @@ int dv_track_stereo_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gr
     return 0;
 }
 
+// The three forms stage the same list (dv_ctx::unmask) for the next dv_track_stereo_enqueue / dv_batch_track_enqueue; each call replaces what an earlier one staged.
+// Every selected rectangle is checked before anything is sized, allocated or staged: the kernel's reads are bounded by them.
+// This one: the ROI mask of detection d is dv_inst_det::mask, copied into unmask_pinned here
 int dv_track_unmask_static(dv_ctx* ctx, const dv_inst_det* dets, int n_dets, const uint32_t* static_ids, int n_static) {
     if (!ctx) return -1;
-    ctx->unmask.clear();
+    ctx->unmask.clear(); ctx->unmask_src = dv_ctx::UnmaskSrc{};
     if (n_static <= 0 || n_dets <= 0) return 0;
     if (!dets || !static_ids) DV_FAIL("dv_track_unmask_static: null argument");
     if (ctx->pending) DV_FAIL("dv_track_unmask_static: call it before dv_track_stereo_enqueue of the frame it belongs to");
-    size_t need = 0;
-    for (int i = 0; i < n_dets; ++i) if (std::find(static_ids, static_ids + n_static, dets[i].track_id) != static_ids + n_static) need += ((size_t)dets[i].w * dets[i].h + 15) / 16 * 16;
-    if (!need) return 0;
-    if (ctx->unmask_pinned_bytes < need) {
-        DV_CHECK(hipStreamSynchronize(ctx->stream));          // (a previous frame's kernels may still read the old staging area)
-        if (ctx->unmask_pinned) (void)hipHostFree(ctx->unmask_pinned);
-        ctx->unmask_pinned = nullptr; ctx->unmask_pinned_bytes = 0;
-        const size_t want = std::max<size_t>(2 * need, (size_t)ctx->cfg.width * ctx->cfg.height);      // (a frame's worth from the start: the rectangles grow as objects come closer)
-        DV_CHECK(hipHostMalloc(&ctx->unmask_pinned, want, hipHostMallocDefault));
-        ctx->unmask_pinned_bytes = want;
-    } else if (ctx->last_done && ctx->last_done == ctx->done) DV_CHECK(hipEventSynchronize(ctx->done));      // the previous frame's unmask kernels have read the staging area (a no-op wait in the usual case: that frame was collected)
-    size_t off = 0;
+    size_t n = 0, roi_bytes = 0;
     for (int i = 0; i < n_dets; ++i) {
         const dv_inst_det& d = dets[i];
-        if (std::find(static_ids, static_ids + n_static, d.track_id) == static_ids + n_static) continue;
-        if (!d.mask || d.w <= 0 || d.h <= 0 || d.x < 0 || d.y < 0 || d.x + d.w > ctx->cfg.width || d.y + d.h > ctx->cfg.height) { ctx->unmask.clear(); DV_FAIL("dv_track_unmask_static: bad detection rectangle / mask"); }
+        if (!unmask_selected(d, static_ids, n_static)) continue;
+        if (!d.mask || !unmask_rect_ok(d, ctx->cfg.width, ctx->cfg.height)) DV_FAIL("dv_track_unmask_static: bad detection rectangle / mask");
+        ++n; roi_bytes += ((size_t)d.w * d.h + 15) / 16 * 16;
+    }
+    if (!n) return 0;
+    if (unmask_reserve(ctx, n, roi_bytes)) return -1;
+    size_t off = dv_unmask_tab_bytes(n);
+    for (int i = 0; i < n_dets; ++i) {
+        const dv_inst_det& d = dets[i];
+        if (!unmask_selected(d, static_ids, n_static)) continue;
         std::memcpy((uint8_t*)ctx->unmask_pinned + off, d.mask, (size_t)d.w * d.h);
-        ctx->unmask.push_back({ d.x, d.y, d.w, d.h, off });
+        ctx->unmask.push_back({ d.x, d.y, d.w, d.h, off, 0u, 0 });
         off += ((size_t)d.w * d.h + 15) / 16 * 16;
     }
     return 0;
 }
 
-// the key-image form: the same rectangle jobs, the ROI mask of detection d being key_image(y + d.y, x + d.x) == d.track_id (dv_inst_det::mask is ignored).  The key
-// image is read in place by the next dv_track_stereo_enqueue (device / pinned) or staged there once (host): it must stay valid until that call returns — host — or
-// until the frame is collected — device / pinned
+// the key-image form: the ROI mask of detection d is key_image(y + d.y, x + d.x) == d.track_id (dv_inst_det::mask is ignored).  The key image is read in place by the
+// next dv_track_stereo_enqueue (device / pinned) or staged there once (host): it must stay valid until that call returns — host — or until the frame is collected —
+// device / pinned
 int dv_track_unmask_static_keys(dv_ctx* ctx, const dv_inst_det* dets, int n_dets, const uint32_t* static_ids, int n_static, const uint32_t* key_image, int stride_bytes, int mem) {
     if (!ctx) return -1;
-    ctx->unmask_keys.clear(); ctx->unmask_key_img = nullptr;
+    ctx->unmask.clear(); ctx->unmask_src = dv_ctx::UnmaskSrc{};
     if (n_static <= 0 || n_dets <= 0) return 0;
     if (!dets || !static_ids) DV_FAIL("dv_track_unmask_static_keys: null argument");
     if (!key_image) DV_FAIL("dv_track_unmask_static_keys: null key image");
@@ -286,38 +304,42 @@ int dv_track_unmask_static_keys(dv_ctx* ctx, const dv_inst_det* dets, int n_dets
     if (stride_bytes == 0) stride_bytes = 4 * ctx->cfg.width;
     if (stride_bytes < 4 * ctx->cfg.width || (stride_bytes & 3)) DV_FAIL("dv_track_unmask_static_keys: bad stride");
     if (ctx->pending) DV_FAIL("dv_track_unmask_static_keys: call it before dv_track_stereo_enqueue of the frame it belongs to");
-    for (int i = 0; i < n_dets; ++i) {          // every rectangle is checked before a job is staged: the kernel's reads are bounded by them
-        const dv_inst_det& d = dets[i];
-        if (std::find(static_ids, static_ids + n_static, d.track_id) == static_ids + n_static) continue;
-        if (d.w <= 0 || d.h <= 0 || d.x < 0 || d.y < 0 || d.w > ctx->cfg.width || d.h > ctx->cfg.height || d.x > ctx->cfg.width - d.w || d.y > ctx->cfg.height - d.h) DV_FAIL("dv_track_unmask_static_keys: detection rectangle outside the image");
+    size_t n = 0;
+    for (int i = 0; i < n_dets; ++i) {
+        if (!unmask_selected(dets[i], static_ids, n_static)) continue;
+        if (!unmask_rect_ok(dets[i], ctx->cfg.width, ctx->cfg.height)) DV_FAIL("dv_track_unmask_static_keys: detection rectangle outside the image");
+        ++n;
     }
+    if (!n) return 0;
+    if (unmask_reserve(ctx, n, 0)) return -1;
     for (int i = 0; i < n_dets; ++i) {
         const dv_inst_det& d = dets[i];
-        if (std::find(static_ids, static_ids + n_static, d.track_id) == static_ids + n_static) continue;
-        ctx->unmask_keys.push_back({ d.x, d.y, d.w, d.h, d.track_id });
+        if (unmask_selected(d, static_ids, n_static)) ctx->unmask.push_back({ d.x, d.y, d.w, d.h, 0, d.track_id, 0 });
     }
-    if (!ctx->unmask_keys.empty()) { ctx->unmask_key_img = key_image; ctx->unmask_key_stride = stride_bytes; ctx->unmask_key_mem = mem; }
+    ctx->unmask_src.form = dv_ctx::UNMASK_KEYS; ctx->unmask_src.key_img = key_image; ctx->unmask_src.key_stride = stride_bytes; ctx->unmask_src.key_mem = mem;
     return 0;
 }
 
-// the mask-stack form: the same rectangle jobs, the ROI mask of detection i being "plane planes[i] has the pixel" (include/dvins.h, dv_mask_stack).  The stack is read in
-// place by the next dv_track_stereo_enqueue (device / pinned), taken from the copy the frame's stage staged, or staged there once (any other host stack)
+// the mask-stack form: the ROI mask of detection i is "plane planes[i] has the pixel" (include/dvins.h, dv_mask_stack).  The stack is read in place by the next
+// dv_track_stereo_enqueue (device / pinned), taken from the copy the frame's stage staged, or staged there once (any other host stack)
 int dv_track_unmask_static_planes(dv_ctx* ctx, const dv_inst_det* dets, const int32_t* planes, int n_dets, const uint32_t* static_ids, int n_static, const dv_mask_stack* stack) {
     if (!ctx) return -1;
-    ctx->unmask_planes.clear(); ctx->unmask_stack = dv_mask_stack{};
+    ctx->unmask.clear(); ctx->unmask_src = dv_ctx::UnmaskSrc{};
     if (n_static <= 0 || n_dets <= 0) return 0;
     if (!dets || !planes || !static_ids) DV_FAIL("dv_track_unmask_static_planes: null argument");
     DvStackLayout L;
     if (const char* why = dv_stack_check(stack, ctx->cfg.width, ctx->cfg.height, &L)) DV_FAIL(std::string("dv_track_unmask_static_planes: ") + why);
     if (ctx->pending) DV_FAIL("dv_track_unmask_static_planes: call it before dv_track_stereo_enqueue of the frame it belongs to");
-    // every rectangle and plane index is checked before a job is staged: the kernel's reads are bounded by them
     if (const char* why = dv_stack_check_dets(dets, planes, n_dets, stack->n_planes, ctx->cfg.width, ctx->cfg.height, static_ids, n_static)) DV_FAIL(std::string("dv_track_unmask_static_planes: ") + why);
+    size_t n = 0;
+    for (int i = 0; i < n_dets; ++i) n += unmask_selected(dets[i], static_ids, n_static);
+    if (!n) return 0;
+    if (unmask_reserve(ctx, n, 0)) return -1;
     for (int i = 0; i < n_dets; ++i) {
         const dv_inst_det& d = dets[i];
-        if (std::find(static_ids, static_ids + n_static, d.track_id) == static_ids + n_static) continue;
-        ctx->unmask_planes.push_back({ d.x, d.y, d.w, d.h, planes[i] });
+        if (unmask_selected(d, static_ids, n_static)) ctx->unmask.push_back({ d.x, d.y, d.w, d.h, 0, 0u, planes[i] });
     }
-    if (!ctx->unmask_planes.empty()) { ctx->unmask_stack = *stack; ctx->unmask_stack.row_stride = L.row_stride; ctx->unmask_stack.plane_stride = L.plane_stride; }
+    ctx->unmask_src.form = dv_ctx::UNMASK_PLANES; ctx->unmask_src.stack = *stack; ctx->unmask_src.stack.row_stride = L.row_stride; ctx->unmask_src.stack.plane_stride = L.plane_stride;
     return 0;
 }
 
@@ -362,7 +384,7 @@ int dv_track_stereo(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gray1, int
 // TrackSemanticImage members (DV_MODE_SEMANTIC with a mask, background_tracker.cpp:757-834 — the background tracking of a DYNAMIC sequence) are the third class, between
 // the two: TrackLeft on the plain pyramids with the raw slice (0.5 px), TrackRightGPU on the GPU tracker's pyramid with the naive slice (1.0 px), the CPU detector's
 // rule, the mask test, min_new = 10 and the erosion as in naive mode.  Two things a dynamic sequence adds ride on the group's stream: the staged
-// dv_track_unmask_static rectangles of all members (ONE launch, dv_unmask_multi_kernel, which also makes the copy of a caller's device mask) and the hand-shake with the
+// dv_track_unmask_static rectangles of all members (ONE launch, dv_unmask_kernel, which also makes the copy of a caller's device mask) and the hand-shake with the
 // member's object tracker (wait for its previous frame, ev_pyr behind the aprons, ev_bg_select behind the selection), so that dv_inst_track_enqueue — still one set of
 // launches per member on the tracker's own stream, like the extra-point stages — sees the order the member's own entry gives it.
 struct DvFrontBatch {
@@ -406,17 +428,16 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
     std::vector<int> kind(n, K_SINGLE);
     // whatever dv_track_unmask_static staged on the members handed in belongs to THIS frame: applied by the round's launch or by the member's own entry, or dropped with
     // a refused / failed call — no job survives into a later frame
-    struct UnmaskGuard {
-        const std::vector<dv_ctx*>& mem; const dv_track_job* jobs; int n;
-        ~UnmaskGuard() { for (int i = 0; i < n; ++i) if (jobs[i].member >= 0 && jobs[i].member < (int)mem.size()) { mem[jobs[i].member]->unmask.clear(); mem[jobs[i].member]->unmask_keys.clear(); mem[jobs[i].member]->unmask_planes.clear(); mem[jobs[i].member]->unmask_stack = dv_mask_stack{}; } }
-    } unmask_guard{ mem, jobs, n };
+    std::vector<dv_ctx*> handed;
+    for (int i = 0; i < n; ++i) if (jobs[i].member >= 0 && jobs[i].member < (int)mem.size()) handed.push_back(mem[jobs[i].member]);
+    UnmaskGuard unmask_guard{ handed.data(), (int)handed.size() };
     for (int i = 0; i < n; ++i) {
         const dv_track_job& j = jobs[i];
         if (j.member < 0 || j.member >= (int)mem.size()) DV_FAIL("dv_batch_track_enqueue: member index out of range");
         for (int q = 0; q < i; ++q) if (jobs[q].member == j.member) DV_FAIL("dv_batch_track_enqueue: a member appears twice");
         const dv_ctx* c = mem[j.member];
         if (c->timing || !j.gray0 || (c->cfg.stereo && !j.gray1)) continue;
-        if (!c->unmask_keys.empty() || !c->unmask_planes.empty()) continue;          // dv_track_unmask_static_keys / _planes jobs: the member's own entry applies them (the round's unmask launch reads host masks)
+        if (!c->unmask.empty() && c->unmask_src.form != dv_ctx::UNMASK_MASKS) continue;     // dv_track_unmask_static_keys / _planes rectangles: the member's own entry applies them
         if (j.mode == DV_MODE_SEMANTIC && j.mask) kind[i] = K_SEMANTIC;
         else if (c->inst) continue;
         else if (j.mode == DV_MODE_RAW && !j.mask) kind[i] = K_RAW;
@@ -503,13 +524,12 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
         // uploads and levels overwrite
         if (c->inst && dv_inst_wait_before_next_frame(c, s, false)) { dv_set_error(c, "dv_track_stereo: hipStreamWaitEvent"); dv_set_error(ctx, c->err); return -1; }
         if (front_plan(c, j, s, P)) { dv_set_error(ctx, c->err); return -1; }      // (with dv_track_stereo's text, on the member and on the first one)
-        if (kind[M[k]] == K_SEMANTIC && !c->unmask.empty()) {      // the static instances' pixels leave the mask in the member's own mask_buf: a host mask is there already, a device mask is copied by the launch that applies the rectangles
-            const int mp = align_up(w, 16);
-            if (c->mask_buf.ensure((size_t)mp * h) != hipSuccess) { dv_set_error(c, "dv_track_unmask_static: cannot allocate the mask copy"); dv_set_error(ctx, c->err); return -1; }
-            const bool own = P.mask == (const uint8_t*)c->mask_buf.p;
-            h_um[n_um++] = DvUnmaskJob{ (uint8_t*)c->mask_buf.p, own ? nullptr : P.mask, mp, P.mask_pitch, w, h, n_ur, (int)c->unmask.size() };
-            for (const dv_ctx::UnmaskJob& u : c->unmask) h_ur[n_ur++] = DvUnmaskRect{ (const uint8_t*)c->unmask_pinned + u.off, u.x, u.y, u.w, u.h };
-            if (front_plan_mask(c, j.mode, (const uint8_t*)c->mask_buf.p, mp, P)) { dv_set_error(ctx, c->err); return -1; }
+        if (kind[M[k]] == K_SEMANTIC && !c->unmask.empty()) {      // the static instances' pixels leave the mask in the member's own mask_buf, by the round's one launch
+            if (c->mask_buf.ensure((size_t)align_up(w, 16) * h) != hipSuccess) { dv_set_error(c, "dv_track_unmask_static: cannot allocate the mask copy"); dv_set_error(ctx, c->err); return -1; }
+            if (front_unmask_tables(c, P, s, n_ur, &h_um[n_um], h_ur)) { dv_set_error(ctx, c->err); return -1; }
+            n_ur += h_um[n_um].n;
+            if (front_plan_mask(c, j.mode, h_um[n_um].dst, h_um[n_um].dpitch, P)) { dv_set_error(ctx, c->err); return -1; }
+            ++n_um;
         }
         if (P.pyr.has_l0) h_l0[n_l0++] = P.pyr.l0;
         levels = P.pyr.levels;
@@ -537,7 +557,7 @@ extern "C" int dv_batch_track_enqueue(dv_batch* B, const dv_track_job* jobs, int
         const DvPyrJob& j0 = h_cp[(size_t)(l - 1) * N];
         dv_launch_pyr_down_multi((const DvPyrJob*)(dp + o_cp) + (size_t)(l - 1) * N, N, j0.dw, j0.dh, s, 1);
     }
-    if (n_um) dv_launch_unmask_multi((const DvUnmaskJob*)(dp + o_um), n_um, (const DvUnmaskRect*)(dp + o_ur), w, h, s);      // system/main.cpp:217-245, before anything reads the masks
+    if (n_um) dv_launch_unmask((const DvUnmaskJob*)(dp + o_um), n_um, (const DvUnmaskRect*)(dp + o_ur), w, h, s);      // system/main.cpp:217-245, before anything reads the masks
     if (n_er) dv_launch_erode_multi((const DvErodeJob*)(dp + o_er), n_er, w, h, s);
     // temporal: FeatureTrackByLK at 0.5 px over raw + semantic (TrackLeft), FeatureTrackByLKGpu at 1.0 px over naive (TrackLeftGPU)
     dv_launch_lk_track_multi(d_lk, R + Q, std::max(n_max_cls[0], n_max_cls[1]), ref->flow_back, 0.5f, s);

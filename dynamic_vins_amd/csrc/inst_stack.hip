@@ -1,11 +1,10 @@
 // inst_stack.hip — the detector branch of thread T1 on gfx950: a frame's instances arrive as a STACK of N mask planes (the segmentation network's output tensor, left in
 // HBM) instead of a label image.  Reference: Detector2D::Launch's `seg_label > kSoloMaskThr` (det2d/detector2d.cpp:441), BuildBoxes2D (det2d/detector2d.cpp:58-97),
-// SemanticImage::SetMaskAndRoi / SetBackgroundMask (basic/semantic_image.cpp:20-93).  Three kernels:
+// SemanticImage::SetMaskAndRoi / SetBackgroundMask (basic/semantic_image.cpp:20-93).  Two kernels:
 //   inst_stack_kernel            one pass over the stack -> merged mask, its inverse, per-plane bounding boxes (dv_inst_stack_frame_enqueue)
-//   plane_roi_mask_multi_kernel  the ROI masks of all visible objects of a frame from their planes, one launch (dv_inst_track_enqueue_planes)
-//   dv_unmask_plane_kernel       FeatureTrack's static-instance unmasking with "the plane has the pixel" as the test (dv_track_unmask_static_planes)
-// The membership rule (include/dvins.h, dv_mask_stack): a byte belongs unless it is 0 or 128 — mask_tensor.to(kInt8).abs().clamp(0, 1), where abs(int8 -128) wraps to
-// -128 —; a float belongs when it is > threshold (false for NaN).
+//   stack_finish_remap_kernel    the tail of the naive form: the remapped merged mask made tight, and its inverse
+// The objects' ROI masks and the static-instance unmasking read single planes of the stack as a DvPixSrc (dv_plane_src): inst_track.hip, copy.hip.
+// The membership rule (include/dvins.h, dv_mask_stack) is pix_src.h's: a byte belongs unless it is 0 or 128, a float belongs when it is > threshold (false for NaN).
 #include "dv_internal.h"
 
 namespace {
@@ -13,7 +12,7 @@ namespace {
 __device__ __forceinline__ unsigned u8_hits(uint32_t v) {          // bit i: byte i belongs
     unsigned m = 0;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { const unsigned b = (v >> (8 * i)) & 255u; m |= (unsigned)(b != 0u && b != 128u) << i; }
+    for (int i = 0; i < 4; ++i) { m |= (unsigned)dv_pix_u8_has((v >> (8 * i)) & 255u) << i; }
     return m;
 }
 
@@ -25,14 +24,14 @@ __device__ __forceinline__ unsigned plane_hits(const uint8_t* __restrict__ row, 
     unsigned m = 0;
     if (KIND == DV_STACK_U8) {
         if (nv == 4 && ((uintptr_t)row & 3) == 0) return u8_hits(*reinterpret_cast<const uint32_t*>(row + x0));
-        for (int i = 0; i < nv; ++i) { const unsigned b = row[x0 + i]; m |= (unsigned)(b != 0u && b != 128u) << i; }
+        for (int i = 0; i < nv; ++i) m |= (unsigned)dv_pix_u8_has(row[x0 + i]) << i;
     } else {
         const float* rf = reinterpret_cast<const float*>(row);
         if (nv == 4 && ((uintptr_t)row & 15) == 0) {
             const float4 v = *reinterpret_cast<const float4*>(rf + x0);
-            return (unsigned)(v.x > thr) | ((unsigned)(v.y > thr) << 1) | ((unsigned)(v.z > thr) << 2) | ((unsigned)(v.w > thr) << 3);
+            return (unsigned)dv_pix_f32_has(v.x, thr) | ((unsigned)dv_pix_f32_has(v.y, thr) << 1) | ((unsigned)dv_pix_f32_has(v.z, thr) << 2) | ((unsigned)dv_pix_f32_has(v.w, thr) << 3);
         }
-        for (int i = 0; i < nv; ++i) m |= (unsigned)(rf[x0 + i] > thr) << i;
+        for (int i = 0; i < nv; ++i) m |= (unsigned)dv_pix_f32_has(rf[x0 + i], thr) << i;
     }
     return m;
 }
@@ -100,40 +99,6 @@ __global__ __launch_bounds__(256) void stack_finish_remap_kernel(const uint8_t* 
     merge[(size_t)y * w + x] = v; inv[(size_t)y * w + x] = (uint8_t)~v;
 }
 
-// blockIdx.z = object; a lane owns 4 consecutive columns of the padded slice and writes them as ONE dword (the slice starts 16-byte aligned and its pitch is a multiple of
-// 16); the plane is read element by element (the rectangle's left edge is arbitrary) — a wave still covers 256 contiguous bytes, or 1 KiB of floats, of one plane row.
-// Columns w <= c < dpitch are written as zero, so no byte of the slice depends on an earlier frame.
-__global__ __launch_bounds__(256) void plane_roi_mask_multi_kernel(const DvPlaneRoiJob* __restrict__ jobs) {
-    const DvPlaneRoiJob j = jobs[blockIdx.z];
-    const int c = (blockIdx.x * 64 + threadIdx.x) * 4, r = blockIdx.y * 4 + threadIdx.y;
-    if (c >= j.dpitch || r >= j.h) return;
-    const uint8_t* row = j.plane + (size_t)(j.y0 + r) * j.row_stride;
-    uint32_t v = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (c + i >= j.w) break;
-        bool hit;
-        if (j.kind == DV_STACK_F32) hit = reinterpret_cast<const float*>(row)[j.x0 + c + i] > j.thr;
-        else { const unsigned b = row[j.x0 + c + i]; hit = b != 0u && b != 128u; }
-        if (hit) v |= 0xffu << (8 * i);
-    }
-    *reinterpret_cast<uint32_t*>(j.dst + (size_t)r * j.dpitch + c) = v;
-}
-
-// system/main.cpp:217-245 with the plane as the instance's ROI mask; the rectangle was checked against the image by the entry
-__global__ __launch_bounds__(256) void dv_unmask_plane_kernel(uint8_t* __restrict__ inv_mask, int pitch, int W, int H, int x0, int y0, int w, int h, const uint8_t* __restrict__ plane,
-                                                              int row_stride, int kind, float thr) {
-    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
-    if (c >= w || r >= h) return;
-    const int x = x0 + c, y = y0 + r;
-    if (x >= W || y >= H) return;
-    const uint8_t* row = plane + (size_t)y * row_stride;
-    bool hit;
-    if (kind == DV_STACK_F32) hit = reinterpret_cast<const float*>(row)[x] > thr;
-    else { const unsigned b = row[x]; hit = b != 0u && b != 128u; }
-    if (hit) inv_mask[(size_t)y * pitch + x] = 255;
-}
-
 }  // namespace
 
 void dv_launch_inst_stack(const DvStackSrc& S, int w, int h, uint8_t* merge, uint8_t* inv, int32_t* boxes, hipStream_t s) {
@@ -143,11 +108,4 @@ void dv_launch_inst_stack(const DvStackSrc& S, int w, int h, uint8_t* merge, uin
 }
 void dv_launch_stack_finish_remap(const uint8_t* src, int spitch, int w, int h, uint8_t* merge, uint8_t* inv, hipStream_t s) {
     hipLaunchKernelGGL(stack_finish_remap_kernel, dim3((w + 255) / 256, h), dim3(256), 0, s, src, spitch, w, h, merge, inv);
-}
-void dv_launch_plane_roi_mask_multi(const DvPlaneRoiJob* jobs_dev, int n_jobs, int dpitch_max, int h_max, hipStream_t s) {
-    if (n_jobs <= 0 || dpitch_max <= 0 || h_max <= 0) return;
-    hipLaunchKernelGGL(plane_roi_mask_multi_kernel, dim3((dpitch_max / 4 + 63) / 64, (h_max + 3) / 4, n_jobs), dim3(64, 4), 0, s, jobs_dev);
-}
-void dv_launch_unmask_plane(uint8_t* inv_mask, int pitch, int W, int H, int x0, int y0, int w, int h, const uint8_t* plane, int row_stride, int kind, float thr, hipStream_t s) {
-    if (w > 0 && h > 0) hipLaunchKernelGGL(dv_unmask_plane_kernel, dim3((w + 63) / 64, (h + 3) / 4), dim3(64, 4), 0, s, inv_mask, pitch, W, H, x0, y0, w, h, plane, row_stride, kind, thr);
 }

@@ -5,13 +5,11 @@
 #include <algorithm>
 #include <cstdint>
 #include "../../include/dvins.h"
+#include "pix_src.h"
 
-// The reference's membership rule on one byte, mask_tensor.to(kInt8).abs().clamp(0, 1) (basic/semantic_image.cpp:20-93), as CPU torch 2.10 evaluates it — checked over
-// all 256 byte values, in a 6-element tensor (scalar loop) and in a 10240-element one (vectorised loop), with the same answer: bytes 1..127 -> 1; bytes 129..255 -> int8
-// -127..-1 -> abs 127..1 -> 1; byte 128 -> int8 -128, whose abs WRAPS to -128 and clamps to 0.  So 1, 127, 129 and 255 are object pixels and 128 is not.  sum(0) widens to
-// int64, so 64 planes cannot wrap the merged mask.  The kernels carry the same expression; tests/test_inst_stack_host.py re-establishes it against the installed torch.
-static inline bool dv_stack_u8_has(uint8_t b) { return b != 0 && b != 128; }
-static inline bool dv_stack_f32_has(float v, float thr) { return v > thr; }          // strict; false for NaN
+// the membership rule of a stack element: written once, in pix_src.h
+static inline bool dv_stack_u8_has(uint8_t b) { return dv_pix_u8_has(b); }
+static inline bool dv_stack_f32_has(float v, float thr) { return dv_pix_f32_has(v, thr); }
 
 // boxes[p] = row_min, row_max, col_min, col_max of plane p's pixels (row_max < row_min: the plane is empty — where the reference throws, torch::max of an empty tensor).
 // One detection per non-empty plane in ASCENDING plane order: rect = cv::Rect(min_pt, max_pt), i.e. the max row / column excluded; track_id = plane (Box2D::id = i),

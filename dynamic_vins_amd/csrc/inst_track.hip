@@ -9,6 +9,8 @@
 // ids from the tracker-wide counter) -> lk_track into the right image with the box offset added to the points (TrackRightByPad) ->
 // finalize (undistortion with the box offset, velocities, PostProcess) -> one D2H copy per frame for all objects.  No host round trip inside
 // a frame: the per-object point counts stay on the device.
+// The objects' masks come as host masks (copied) or are cut on the device from ONE membership source, the frame's key image or the detector's mask stack, by ONE
+// kernel (roi_mask_kernel) that asks pix_src.h's dv_pix_has.
 // Canonical choices: objects are visited in ascending id (the reference iterates an unordered_map) and run after the background tracker on the
 // same stream, so the shared id counter hands out ids in a fixed order (the reference increments it from two threads without a lock).
 #include <algorithm>
@@ -35,17 +37,30 @@ __global__ __launch_bounds__(256) void roi_pad_multi_kernel(const RoiJob* __rest
     j.dst[(size_t)y * j.dpitch + x] = (x < j.w && y < j.h) ? j.src[(size_t)(j.y0 + y) * j.spitch + j.x0 + x] : (uint8_t)0;
 }
 
-// dv_inst_track_enqueue_keys: the ROI masks of ALL visible objects of the frame from its key image (VIODE::PixelToKey of seg0), in the layout the host copy of
-// dv_inst_track_enqueue produces (pitch align_up(w, 16)).  blockIdx.z = object, a workgroup covers 64 columns x 4 rows of the padded slice: a wave reads 64 consecutive
-// dwords of one key-image row (256 contiguous bytes, dword aligned whatever x0 and the row stride are) and writes 64 consecutive mask bytes; the padding columns are
-// written as zero, so no byte of the slice depends on an earlier frame.
-__global__ __launch_bounds__(256) void key_roi_mask_multi_kernel(const DvKeyRoiJob* __restrict__ jobs) {
-    const DvKeyRoiJob j = jobs[blockIdx.z];
-    const int c = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y * 4 + threadIdx.y;
+// dv_inst_track_enqueue_keys / _planes: the ROI masks of ALL visible objects of the frame cut from its key image or from their planes of the detector's stack, in the
+// layout the host copy of dv_inst_track_enqueue produces (pitch align_up(w, 16)).  blockIdx.z = object, a workgroup covers 64 lanes x 4 rows of the padded slice, a lane
+// LANE_W consecutive columns; the source is read element by element through pix_src.h's rule (the rectangle's left edge is arbitrary).  LANE_W is chosen by the source's
+// element width so that one load instruction of a wave stays within 256 contiguous bytes:
+//   1  dword elements (key image): a wave reads 64 consecutive dwords of one key-image row and writes 64 consecutive mask bytes;
+//   4  byte and float planes: a lane writes its 4 columns as ONE dword (the slice starts 16-byte aligned and its pitch is a multiple of 16); a wave covers 256 contiguous
+//      bytes of a byte plane's row, or 1 KiB of a float plane's.
+// All jobs of a launch share one kind (one source per frame): roi_mask_lane_w is what the launcher sizes the grid by and what the kernel branches on, block-uniformly.
+// Columns w <= c < dpitch are written as zero, so no byte of the slice depends on an earlier frame.
+__host__ __device__ inline int roi_mask_lane_w(int kind) { return kind == DV_PIX_KEY_U32 ? 1 : 4; }
+template <int LANE_W>
+__device__ __forceinline__ void roi_mask_lanes(const DvRoiMaskJob& j) {
+    const int c = (blockIdx.x * 64 + threadIdx.x) * LANE_W, r = blockIdx.y * 4 + threadIdx.y;
     if (c >= j.dpitch || r >= j.h) return;
-    uint8_t v = 0;
-    if (c < j.w) v = j.key[(size_t)(j.y0 + r) * j.kpitch + j.x0 + c] == j.id ? (uint8_t)255 : (uint8_t)0;
-    j.dst[(size_t)r * j.dpitch + c] = v;
+    uint32_t v = 0;
+#pragma unroll
+    for (int i = 0; i < LANE_W; ++i)
+        if (c + i < j.w && dv_pix_has(j.src, j.x0 + c + i, j.y0 + r)) v |= 0xffu << (8 * i);
+    uint8_t* out = j.dst + (size_t)r * j.dpitch + c;
+    if (LANE_W == 4) *reinterpret_cast<uint32_t*>(out) = v; else *out = (uint8_t)v;
+}
+__global__ __launch_bounds__(256) void roi_mask_kernel(const DvRoiMaskJob* __restrict__ jobs) {
+    const DvRoiMaskJob j = jobs[blockIdx.z];
+    if (roi_mask_lane_w(j.src.kind) == 1) roi_mask_lanes<1>(j); else roi_mask_lanes<4>(j);
 }
 
 struct RoiPyr {          // pyramid storage with a fixed capacity (the full frame), re-laid-out per frame without re-allocation
@@ -104,12 +119,11 @@ struct dv_inst_tracker {
     // extra points from the frame's disparity map (dv_inst_set_disparity; extra_points.hip): the reference's second thread = a side stream
     const float* disp_user = nullptr; int disp_stride = 0, disp_mem = 0; double disp_baseline = 0; bool disp_next = false, xp_frame = false, xp_inflight = false;
     const uint32_t* keys_user = nullptr; int keys_stride = 0, keys_mem = 0; bool keys_next = false; DevBuf keys_buf;
-    DevBuf stack_buf;          // dv_inst_track_enqueue_planes with a DV_MEM_HOST stack the frame's stage did not stage
-    DevBuf keys0_buf;          // dv_inst_track_enqueue_keys with a DV_MEM_HOST key image: staged once per frame      // VIODE: seg1's key image of the next frame (dv_inst_set_right_keys)
+    DevBuf src_buf;            // dv_inst_track_enqueue_keys with a DV_MEM_HOST key image, _planes with a DV_MEM_HOST stack the frame's stage did not stage: staged once per frame
     DevBuf disp_buf, xp_pool; hipStream_t xstream = nullptr; hipEvent_t ev_xin = nullptr, ev_xdone = nullptr;
     void* xp_pinned = nullptr; size_t xp_cap_slots = 0;          // per output slot: count (64 bytes) + 3 * DV_XP_CAP doubles, written by the kernel straight into pinned memory
     ~dv_inst_tracker() {
-        disp_buf.release(); xp_pool.release(); keys_buf.release(); keys0_buf.release(); stack_buf.release();
+        disp_buf.release(); xp_pool.release(); keys_buf.release(); src_buf.release();
         if (xstream) { (void)hipStreamSynchronize(xstream); (void)hipStreamDestroy(xstream); }
         if (ev_xin) (void)hipEventDestroy(ev_xin);
         if (ev_xdone) (void)hipEventDestroy(ev_xdone);
@@ -126,10 +140,6 @@ struct dv_inst_tracker {
 };
 
 void dv_inst_destroy_internal(dv_inst_tracker* t) { delete t; }
-void dv_launch_key_roi_mask_multi(const DvKeyRoiJob* jobs_dev, int n_jobs, int dpitch_max, int h_max, hipStream_t s) {
-    if (n_jobs <= 0 || dpitch_max <= 0 || h_max <= 0) return;
-    hipLaunchKernelGGL(key_roi_mask_multi_kernel, dim3((dpitch_max + 63) / 64, (h_max + 3) / 4, n_jobs), dim3(64, 4), 0, s, jobs_dev);
-}
 // the background tracker's next frame, built on s (the ctx's own stream, or its dv_batch's front-end stream), must not rebuild the right pyramid while the objects of the
 // previous frame still read it.  consume = false: the wait is enqueued and the ctx is left as it is (the group entry changes no ctx before its round's commit: a refused
 // round must leave the member's next frame its wait, and a second wait for an event that has fired costs nothing)
@@ -137,17 +147,6 @@ int dv_inst_wait_before_next_frame(dv_ctx* ctx, hipStream_t s, bool consume) {
     if (!ctx->inst || !ctx->inst->frame_enqueued) return 0;
     if (consume) ctx->inst->frame_enqueued = false;
     return hipStreamWaitEvent(s, ctx->inst->done, 0) == hipSuccess ? 0 : -1;
-}
-
-static void circle_half_widths_i(int radius, std::vector<uint8_t>& hw) {      // cv::circle's midpoint rasteriser (as dvins_api.hip)
-    hw.assign(radius + 1, 0);
-    int err = 0, dx = radius, dy = 0, plus = 1, minus = (radius << 1) - 1;
-    while (dx >= dy) {
-        hw[dy] = (uint8_t)std::max<int>(hw[dy], dx); hw[dx] = (uint8_t)std::max<int>(hw[dx], dy);
-        dy++; err += plus; plus += 2;
-        int m = (err <= 0) - 1;
-        err -= minus & m; dx += m; minus -= m & 2;
-    }
 }
 
 static int slot_init(dv_ctx* ctx, Slot& s) {
@@ -204,7 +203,7 @@ int dv_inst_config(dv_ctx* ctx, int max_dynamic_cnt, int min_dynamic_dist, int u
     dv_inst_tracker& T = *ctx->inst;
     if (T.pending) DV_FAIL("dv_inst_config: a frame is in flight");
     T.max_cnt = max_dynamic_cnt; T.min_dist = min_dynamic_dist; T.use_det3d = use_det3d;
-    std::vector<uint8_t> hw; circle_half_widths_i(min_dynamic_dist, hw);
+    std::vector<uint8_t> hw; circle_half_widths(min_dynamic_dist, hw);
     DV_CHECK(T.hw.ensure(DV_MAX_RADIUS + 1));
     DV_CHECK(hipMemcpy(T.hw.p, hw.data(), hw.size(), hipMemcpyHostToDevice));
     T.hw_radius = min_dynamic_dist;
@@ -223,12 +222,11 @@ int dv_inst_reset(dv_ctx* ctx) {
     return 0;
 }
 
-// the frame's object masks: the detections' own host masks (dv_inst_track_enqueue: ks == nullptr) or the comparison of the frame's key image with each detection's
-// track id, done on the device (dv_inst_track_enqueue_keys)
-// — or "plane planes[i] of the detector's mask stack has the pixel", also on the device (dv_inst_track_enqueue_planes: ps != nullptr; st passed dv_stack_check, strides filled in)
-struct InstKeySrc { const uint32_t* img; int stride_bytes, mem; };
-struct InstPlaneSrc { const dv_mask_stack* st; const int32_t* planes; };
-static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_dets, const dv_box3d* boxes3d, int n_boxes3d, const InstKeySrc* ks, const InstPlaneSrc* ps = nullptr) {
+// the frame's object masks: the detections' own host masks (dv_inst_track_enqueue: ms == nullptr), or cut on the device from one source — the frame's key image
+// compared with each detection's track id (dv_inst_track_enqueue_keys: key_img != nullptr), or "plane planes[i] of the detector's mask stack has the pixel"
+// (dv_inst_track_enqueue_planes: st passed dv_stack_check, strides filled in)
+struct InstMaskSrc { const uint32_t* key_img; int key_stride, key_mem; const dv_mask_stack* st; const int32_t* planes; };
+static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_dets, const dv_box3d* boxes3d, int n_boxes3d, const InstMaskSrc* ms) {
     HostScope hs(ctx, "h_inst_enqueue");
     if (!ctx->inst) DV_FAIL("dv_inst_track: call dv_inst_config first");
     if (n_dets < 0 || (n_dets > 0 && !dets) || n_boxes3d < 0 || (n_boxes3d > 0 && !boxes3d)) DV_FAIL("dv_inst_track: bad argument");
@@ -253,7 +251,7 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
     for (int i = 0; i < n_dets; ++i) {
         const dv_inst_det& d = dets[i];
         if (d.w <= 0 || d.h <= 0 || d.x < 0 || d.y < 0 || d.x + d.w > W || d.y + d.h > H) DV_FAIL("dv_inst_track: detection rectangle outside the image");
-        if (!ks && !ps && !d.mask) DV_FAIL("dv_inst_track: detection without a mask");
+        if (!ms && !d.mask) DV_FAIL("dv_inst_track: detection without a mask");
         auto it = T.slots.find(d.track_id);
         if (it == T.slots.end()) {
             it = T.slots.emplace(d.track_id, Slot()).first; it->second.id = d.track_id;
@@ -262,7 +260,7 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
         Slot& S = it->second;
         if (S.visible) DV_FAIL("dv_inst_track: two detections with the same track id");
         S.visible = true; S.has_box2d = true; S.class_id = d.class_id; S.rx = d.x; S.ry = d.y; S.rw = d.w; S.rh = d.h;
-        if (ks || ps) S.pts_copy.clear();          // (the key and plane forms ignore dv_inst_det::points)
+        if (ms) S.pts_copy.clear();          // (the key and plane forms ignore dv_inst_det::points)
         else S.pts_copy.assign(d.points ? d.points : nullptr, d.points ? d.points + 3 * (size_t)std::max(d.n_points, 0) : nullptr);
         mask_bytes += (size_t)align_up(d.w, 16) * d.h;
     }
@@ -297,7 +295,7 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
         //  hipHostFree + hipHostMalloc resp. two stream synchronisations + hipFree + hipMalloc — 5 - 8 ms during which the estimator thread's HIP calls wait for the runtime's
         //  locks too; seen as one 6 ms frame somewhere in the first frames of the dynamic bench line's timed region in every second run)
         const size_t mask_floor = 2 * (size_t)align_up(W, 16) * H + 4096;
-        if (!ks && !ps && T.pinned_in_bytes < mask_bytes) {
+        if (!ms && T.pinned_in_bytes < mask_bytes) {
             if (T.pinned_in) (void)hipHostFree(T.pinned_in);
             T.pinned_in = nullptr; T.pinned_in_bytes = 0;
             const size_t want = std::max(mask_bytes * 2 + 4096, mask_floor);
@@ -341,7 +339,7 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
         {
             const size_t need = ((size_t)na * 2 * sizeof(RoiJob) + (size_t)na * DV_MAX_LEVELS * sizeof(DvPyrJob) + (size_t)na * sizeof(DvExtraJob) +
                                  (size_t)na * (sizeof(DvCompactJob) + sizeof(DvErodeJob) + sizeof(GfttTileArgs) + sizeof(GfttSelectArgs) + sizeof(DvFinalizeJob)) + 4096) +
-                                (ks ? (size_t)na * sizeof(DvKeyRoiJob) + 256 : 0) + (ps ? (size_t)na * sizeof(DvPlaneRoiJob) + 256 : 0);
+                                (ms ? (size_t)na * sizeof(DvRoiMaskJob) + 256 : 0);
             if (need > T.arena_cap) {
                 DV_CHECK(hipStreamSynchronize(s));
                 const size_t cap = need * 2;
@@ -364,22 +362,21 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
         auto up256 = [](size_t v) { return (v + 255) / 256 * 256; };
         const size_t cj_off = up256(xp_off + (size_t)na * sizeof(DvExtraJob)), ej_off = up256(cj_off + (size_t)na * sizeof(DvCompactJob)), gt_off = up256(ej_off + (size_t)na * sizeof(DvErodeJob)),
                      gs_off = up256(gt_off + (size_t)na * sizeof(GfttTileArgs)), fj_off = up256(gs_off + (size_t)na * sizeof(GfttSelectArgs)),
-                     kj_off = up256(fj_off + (size_t)na * sizeof(DvFinalizeJob)), arena_used = ks ? kj_off + (size_t)na * sizeof(DvKeyRoiJob) : ps ? kj_off + (size_t)na * sizeof(DvPlaneRoiJob) : fj_off + (size_t)na * sizeof(DvFinalizeJob);
+                     mj_off = up256(fj_off + (size_t)na * sizeof(DvFinalizeJob)), arena_used = ms ? mj_off + (size_t)na * sizeof(DvRoiMaskJob) : fj_off + (size_t)na * sizeof(DvFinalizeJob);
         DvCompactJob* h_cj = (DvCompactJob*)((uint8_t*)T.arena_pinned + cj_off); DvErodeJob* h_ej = (DvErodeJob*)((uint8_t*)T.arena_pinned + ej_off);
         GfttTileArgs* h_gt = (GfttTileArgs*)((uint8_t*)T.arena_pinned + gt_off); GfttSelectArgs* h_gs = (GfttSelectArgs*)((uint8_t*)T.arena_pinned + gs_off);
         DvFinalizeJob* h_fj = (DvFinalizeJob*)((uint8_t*)T.arena_pinned + fj_off);
-        // the key form: one job per object for key_roi_mask_multi_kernel behind the other tables in the same upload; a host key image is staged once for the frame
-        DvKeyRoiJob* h_kj = (DvKeyRoiJob*)((uint8_t*)T.arena_pinned + kj_off); int key_P = 0, key_H = 0;
-        const uint32_t* kimg0 = ks ? ks->img : nullptr; int kpitch0 = ks ? ks->stride_bytes / 4 : 0;
-        if (ks && na > 0 && ks->mem == DV_MEM_HOST) {
-            DV_CHECK(T.keys0_buf.ensure((size_t)W * H * 4));
-            DV_CHECK(hipMemcpy2DAsync(T.keys0_buf.p, (size_t)W * 4, ks->img, (size_t)ks->stride_bytes, (size_t)W * 4, H, hipMemcpyHostToDevice, s));
-            kimg0 = (const uint32_t*)T.keys0_buf.p; kpitch0 = W;
-        }
-        // the plane form: one job per object for plane_roi_mask_multi_kernel in the same place of the same upload; a host stack the frame's stage did not stage is staged once
-        DvPlaneRoiJob* h_pj = (DvPlaneRoiJob*)((uint8_t*)T.arena_pinned + kj_off);
+        // a device source: one job per object for roi_mask_kernel behind the other tables in the same upload; a host key image, or a host stack the frame's stage did
+        // not stage, is staged once for the frame
+        DvRoiMaskJob* h_mj = (DvRoiMaskJob*)((uint8_t*)T.arena_pinned + mj_off); int roi_P = 0, roi_Hm = 0;
+        const uint32_t* kimg0 = ms ? ms->key_img : nullptr; int kstride0 = ms ? ms->key_stride : 0;
         DvStackSrc psrc{};
-        if (ps && na > 0 && dv_stack_resolve(ctx, *ps->st, T.stack_buf, s, &psrc)) return -1;
+        if (ms && na > 0 && ms->key_img && ms->key_mem == DV_MEM_HOST) {
+            DV_CHECK(T.src_buf.ensure((size_t)W * H * 4));
+            DV_CHECK(hipMemcpy2DAsync(T.src_buf.p, (size_t)W * 4, ms->key_img, (size_t)ms->key_stride, (size_t)W * 4, H, hipMemcpyHostToDevice, s));
+            kimg0 = (const uint32_t*)T.src_buf.p; kstride0 = 4 * W;
+        }
+        if (ms && na > 0 && !ms->key_img && dv_stack_resolve(ctx, *ms->st, T.src_buf, s, &psrc)) return -1;
         int ero_W = 0, ero_H = 0, nj = 0;
         const double dt_fin = dt;
         T.xp_frame = T.disp_next; T.disp_next = false;
@@ -397,13 +394,10 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
             const int w = S.rw, h = S.rh;
             const int mp = align_up(w, 16);
             S.mask = (uint8_t*)T.mask_all.p + moff;
-            if (ks) {
-                h_kj[nj] = DvKeyRoiJob{ kimg0, S.mask, kpitch0, S.rx, S.ry, w, h, mp, S.id, 0 };
-                key_P = std::max(key_P, mp); key_H = std::max(key_H, h);
-            } else if (ps) {
-                int plane = 0; for (int i = 0; i < n_dets; ++i) if (dets[i].track_id == S.id) plane = ps->planes[i];
-                h_pj[nj] = DvPlaneRoiJob{ psrc.base + (size_t)plane * psrc.plane_stride, S.mask, psrc.row_stride, S.rx, S.ry, w, h, mp, psrc.kind, psrc.thr };
-                key_P = std::max(key_P, mp); key_H = std::max(key_H, h);
+            if (ms) {
+                int plane = 0; for (int i = 0; i < n_dets && !ms->key_img; ++i) if (dets[i].track_id == S.id) plane = ms->planes[i];
+                h_mj[nj] = DvRoiMaskJob{ ms->key_img ? dv_key_src(kimg0, kstride0, S.id) : dv_plane_src(psrc, plane), S.mask, mp, w, h, S.rx, S.ry };
+                roi_P = std::max(roi_P, mp); roi_Hm = std::max(roi_Hm, h);
             } else {
                 uint8_t* hm = (uint8_t*)T.pinned_in + moff;
                 const dv_inst_det* det = nullptr; for (int i = 0; i < n_dets; ++i) if (dets[i].track_id == S.id) det = &dets[i];
@@ -459,10 +453,9 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
             }
         }
         if (na > 0) {
-            if (!ks && !ps) DV_CHECK(dv_copy_async(T.mask_all.p, T.pinned_in, moff, s));
+            if (!ms) DV_CHECK(dv_copy_async(T.mask_all.p, T.pinned_in, moff, s));
             DV_CHECK(dv_copy_async(T.arena.p, T.arena_pinned, arena_used, s));
-            if (ks) dv_launch_key_roi_mask_multi((const DvKeyRoiJob*)((const uint8_t*)T.arena.p + kj_off), na, key_P, key_H, s);
-            if (ps) dv_launch_plane_roi_mask_multi((const DvPlaneRoiJob*)((const uint8_t*)T.arena.p + kj_off), na, key_P, key_H, s);
+            if (ms) hipLaunchKernelGGL(roi_mask_kernel, dim3((roi_P / roi_mask_lane_w(h_mj[0].src.kind) + 63) / 64, (roi_Hm + 3) / 4, na), dim3(64, 4), 0, s, (const DvRoiMaskJob*)((const uint8_t*)T.arena.p + mj_off));
             if (T.xp_frame && n_xp > 0) {
                 // the reference starts a thread for this (dynamic_tracker.cpp:378): a side stream behind the mask + table uploads; the objects' tracking goes on meanwhile
                 DV_CHECK(hipEventRecord(T.ev_xin, s));
@@ -556,8 +549,8 @@ int dv_inst_track_enqueue_keys(dv_ctx* ctx, double t, const dv_inst_det* dets, i
         const dv_inst_det& d = dets[i];
         if (d.w <= 0 || d.h <= 0 || d.x < 0 || d.y < 0 || d.x + d.w > ctx->cfg.width || d.y + d.h > ctx->cfg.height) DV_FAIL("dv_inst_track_enqueue_keys: detection rectangle outside the image");
     }
-    const InstKeySrc ks{ key_image, stride_bytes, mem };
-    return inst_track_enqueue_impl(ctx, t, dets, n_dets, boxes3d, n_boxes3d, &ks);
+    const InstMaskSrc ms{ key_image, stride_bytes, mem, nullptr, nullptr };
+    return inst_track_enqueue_impl(ctx, t, dets, n_dets, boxes3d, n_boxes3d, &ms);
 }
 
 // the mask-stack form (include/dvins.h): mask of detection i = "plane planes[i] has the pixel" over its rectangle, cut on the device
@@ -569,8 +562,8 @@ int dv_inst_track_enqueue_planes(dv_ctx* ctx, double t, const dv_inst_det* dets,
     // every rectangle and plane index before anything is staged: the kernel's reads are bounded by them
     if (const char* why = dv_stack_check_dets(dets, planes, n_dets, stack->n_planes, ctx->cfg.width, ctx->cfg.height, nullptr, 0)) DV_FAIL(std::string("dv_inst_track_enqueue_planes: ") + why);
     dv_mask_stack st = *stack; st.row_stride = L.row_stride; st.plane_stride = L.plane_stride;
-    const InstPlaneSrc ps{ &st, planes };
-    return inst_track_enqueue_impl(ctx, t, dets, n_dets, boxes3d, n_boxes3d, nullptr, &ps);
+    const InstMaskSrc ms{ nullptr, 0, 0, &st, planes };
+    return inst_track_enqueue_impl(ctx, t, dets, n_dets, boxes3d, n_boxes3d, &ms);
 }
 
 // VIODE: the keys of SemanticImage::seg1 of the frame the NEXT dv_inst_track_enqueue processes (include/dvins.h)
@@ -675,6 +668,29 @@ int dv_inst_track_collect(dv_ctx* ctx, dv_inst_obs* insts, int cap_insts, int* n
     }
     *n_insts = ki; *n_feats = kf; *n_points = kp;
     if (*ctx->err_pinned) { /* reported by the next dv_track_stereo_collect */ }
+    return 0;
+}
+
+// what the unmask and ROI-mask kernels wrote, for tests (include/dvins.h): which = 0 the background tracker's working mask (mask_buf: rows of align_up(w, 16) bytes),
+// which = 1 the ROI slice of object track_id as the last dv_inst_track_enqueue* laid it out.  The frame must be collected
+int dv_front_debug_mask(dv_ctx* ctx, int which, uint32_t track_id, void* host, long long cap_bytes, int* w, int* h, int* pitch) {
+    if (!ctx) return -1;
+    if ((which != 0 && which != 1) || !host || !w || !h || !pitch) DV_FAIL("dv_front_debug_mask: bad argument");
+    if (ctx->pending || (ctx->inst && ctx->inst->pending)) DV_FAIL("dv_front_debug_mask: a frame is in flight");
+    DV_CHECK(hipSetDevice(ctx->cfg.device));
+    const void* src = ctx->mask_buf.p; int mw = ctx->cfg.width, mh = ctx->cfg.height;
+    if (which == 1) {
+        auto it = ctx->inst ? ctx->inst->slots.find(track_id) : std::map<unsigned, Slot>::iterator();
+        if (!ctx->inst || it == ctx->inst->slots.end() || !it->second.mask) DV_FAIL("dv_front_debug_mask: no such object");
+        src = it->second.mask; mw = it->second.rw; mh = it->second.rh;
+        DV_CHECK(hipStreamSynchronize(ctx->inst->stream));
+    }
+    const int mp = align_up(mw, 16);
+    if (!src || (which == 0 && ctx->mask_buf.bytes < (size_t)mp * mh)) DV_FAIL("dv_front_debug_mask: no working mask");
+    if (cap_bytes < (long long)mp * mh) DV_FAIL("dv_front_debug_mask: output buffer too small");
+    DV_CHECK(hipStreamSynchronize(ctx->stream));
+    DV_CHECK(hipMemcpy(host, src, (size_t)mp * mh, hipMemcpyDeviceToHost));
+    *w = mw; *h = mh; *pitch = mp;
     return 0;
 }
 

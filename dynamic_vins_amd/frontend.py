@@ -574,6 +574,14 @@ class Context:
         self._check(self.lib.dv_inst_track_collect(self.h, oi.ctypes.data, len(oi), C.byref(ni), of.ctypes.data, len(of), C.byref(nf), op.ctypes.data, len(op), C.byref(npt)))
         return oi[: ni.value].copy(), of[: nf.value].copy(), op[: npt.value].copy()
 
+    def front_debug_mask(self, which, track_id=0):
+        """for tests, after the frame was collected: which = 0 the background tracker's working mask, which = 1 the ROI mask of object track_id -> (uint8 [h, pitch], w)"""
+        cap = (self.cfg.width + 15) // 16 * 16 * self.cfg.height
+        out = np.zeros(cap, np.uint8)
+        w, h, p = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self.lib.dv_front_debug_mask(self.h, int(which), int(track_id), out.ctypes.data, cap, C.byref(w), C.byref(h), C.byref(p)))
+        return out[: p.value * h.value].reshape(h.value, p.value).copy(), w.value
+
     def track_stereo_collect(self):
         n = C.c_int(0)
         self._check(self.lib.dv_track_stereo_collect(self.h, self._out.ctypes.data_as(C.POINTER(dv_feat)), C.byref(n)))

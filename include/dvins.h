@@ -735,6 +735,11 @@ int dv_ba_debug_slot_log(dv_ctx* ctx, unsigned long long* vals, long long cap_va
  * (ignored for 3, 4).  host != NULL: the first `bytes` bytes of the buffer, after the BA stream has drained; host == NULL: the whole buffer is filled with 0xFF bytes, so
  * that what a later launch does not write shows.  -1: bad argument or `bytes` beyond the buffer */
 int dv_ba_debug_buffer(dv_ctx* ctx, int which, int set, void* host, long long bytes);
+/* the mask bytes the dynamic front end's kernels wrote, for tests, after the frame was collected: which = 0 the background tracker's working mask of the last frame that
+ * was staged or unmasked into the library's own buffer (w x h = the configured size), which = 1 the ROI mask of object track_id of the last dv_inst_track_enqueue*
+ * (w x h = its rectangle).  Rows of *pitch = w rounded up to 16 bytes, padding columns included; host takes *pitch * *h bytes (cap_bytes: its size).  -1: bad argument,
+ * a frame in flight, no such mask / object, or cap_bytes too small */
+int dv_front_debug_mask(dv_ctx* ctx, int which, uint32_t track_id, void* host, long long cap_bytes, int* w, int* h, int* pitch);
 int dv_est_reset(dv_ctx* ctx);                                   /* Estimator::ClearState + SetParameter */
 int dv_est_input_imu(dv_ctx* ctx, double t, const double* acc, const double* gyr);      /* Estimator::InputIMU */
 /* one iteration of Estimator::ProcessMeasurements (estimator.cpp:1786-1863): IMU interval, pre-integration,

@@ -391,4 +391,24 @@ def test_errors_name_the_entry_and_leave_the_context_usable():
     ctx.inst_set_right_keys(k1, DV_MEM_DEVICE)
     ctx.inst_track_enqueue_keys(seq.times[1], dets, k0, DV_MEM_DEVICE)
     assert len(ctx.track_stereo_collect()) > 20 and len(ctx.inst_track_collect()[1]) > 0
+    # the host-mask form.  A detection with a negative width or height is refused by the entry's own check, before anything is sized from it
+    d2 = seq.dets[2]
+    sid = np.array([d["track_id"] for d in d2], np.uint32)
+    arr2, masks2 = ctx._det_array(d2), [np.ascontiguousarray(d["mask"], np.uint8) for d in d2]
+    for a, m in zip(arr2, masks2):
+        a.mask = m.ctypes.data
+    w0, h0 = arr2[0].w, arr2[0].h
+    for arr2[0].w, arr2[0].h in ((-w0, h0), (w0, -h0)):
+        fails(lib.dv_track_unmask_static(h, C.addressof(arr2), len(d2), sid.ctypes.data, len(sid)), "dv_track_unmask_static: bad detection rectangle / mask")
+    # ... and what it staged is dropped by a refused dv_track_stereo_enqueue (wrong size): the next frame's working mask is its input mask, byte for byte
+    l, r = seq.frames[2]
+    mask = seq.inv_mask_dev[2].cpu().numpy().reshape(H, W)
+    x, y, w, hh = d2[0]["rect"]
+    assert (mask[y:y + hh, x:x + w][masks2[0] >= 1] != 255).any(), "unmasking this detection would change nothing"
+    ctx.track_unmask_static(d2, sid)
+    fails(lib.dv_track_stereo_enqueue(h, l.data_ptr(), r.data_ptr(), W - 1, H, W, seq.times[2], seq.inv_mask_dev[2].data_ptr(), DV_MODE_SEMANTIC, DV_MEM_DEVICE), "dv_track_stereo")
+    ctx.track_stereo_enqueue(l.cpu().numpy(), r.cpu().numpy(), seq.times[2], mask, DV_MODE_SEMANTIC, DV_MEM_HOST)
+    ctx.track_stereo_collect()
+    got, _ = ctx.front_debug_mask(0)
+    assert got[:, :W].tobytes() == mask.tobytes(), "rectangles staged before a refused enqueue were applied to the next frame"
     ctx.close(); ref.close()
