@@ -184,7 +184,8 @@ __device__ __forceinline__ void gftt_tile_body(const GfttTileArgs& a, int tx, in
         if (RULE == 1) vmax = max(vmax, f2ord(v));      // cuda::minMax(eig_, 0, &maxVal): no mask
         if (!m) continue;
         if (RULE == 0) vmax = max(vmax, f2ord(v));      // minMaxLoc(eig, 0, &maxVal, 0, 0, mask)
-        if (x < 1 || x >= w - 1 || y < 1 || y >= h - 1 || (RULE == 0 && v == 0.f)) continue;
+        // v == 0 never exceeds the threshold, under either rule: not emitted (a flat region would fill the candidate buffer with its pixels)
+        if (x < 1 || x >= w - 1 || y < 1 || y >= h - 1 || v == 0.f) continue;
         float nb[8] = { s_eig[r][c], s_eig[r][c + 1], s_eig[r][c + 2], s_eig[r + 1][c], s_eig[r + 1][c + 2],
                         s_eig[r + 2][c], s_eig[r + 2][c + 1], s_eig[r + 2][c + 2] };
         float mx = nb[0], mn = nb[0];
@@ -263,7 +264,7 @@ __device__ __forceinline__ void gftt_select_body(const GfttSelectArgs& a) {
     if (use_grid && gw * gh > SEL_MAX_CELLS) { if (tid == 0 && a.err_flag) atomicOr(a.err_flag, 2); n_cand = 0; }
 
     for (int i = tid; i <= SEL_BINS; i += SEL_THREADS) hist[i] = 0;
-    if (use_grid) for (int i = tid; i < gw * gh; i += SEL_THREADS) head[i] = -1;
+    if (use_grid && gw * gh <= SEL_MAX_CELLS) for (int i = tid; i < gw * gh; i += SEL_THREADS) head[i] = -1;      // (a refused grid is not initialised: head holds SEL_MAX_CELLS entries)
     if (tid == 0) { s_acc = 0; s_hi = SEL_BINS - 1; s_done = 0; }
     __syncthreads();
     // a candidate survives THRESH_TOZERO iff v > thr (v < 0 can never survive: thr >= 0 whenever maxVal >= 0)

@@ -129,7 +129,17 @@ int dv_track_by_lk_gpu(dv_ctx* ctx, const uint8_t* img1, const uint8_t* img2, in
                        float* pts2, uint8_t* status, int mem);
 int dv_pyr_down_cuda(dv_ctx* ctx, const uint8_t* src, int w, int h, int stride, uint8_t* dst, int mem);      /* cuda::pyrDown, 8-bit: the same sums as cv::pyrDown, rounded half to even */
 /* cv::goodFeaturesToTrack(img, out, max_n, quality, min_dist, mask) call sites:
- * background_tracker.cpp:85,238; instance_feature.cpp:381; dynamic_tracker.cpp:435 */
+ * background_tracker.cpp:85,238; instance_feature.cpp:381; dynamic_tracker.cpp:435
+ * Limits (dv_gftt, dv_gftt_cuda and the detector inside dv_track_stereo*): an input beyond one of them is refused with an error that names the flag
+ * ("device error flags=N", N the sum of the flags raised), nothing is returned for it, and the context stays usable.
+ *   flag 1  more candidates (interior, unmasked pixels with a non-zero response that is >= its eight neighbours) than the context's candidate buffer holds:
+ *           max(4096, w * h / 4) of the largest image the context has processed so far (the buffer only grows);
+ *   flag 2  min_dist >= 1 and ceil(w / c) * ceil(h / c) > 32768 grid cells, c = min_dist rounded half to even (320 x 240 at min_dist 1 has 76800);
+ *           min_dist < 1 uses no grid and has no such limit;
+ *   flag 4  the selection, taking the 2048 equal bins between the quality threshold and the maximum from the top, reaches a bin with more than 8192
+ *           candidates before max_n corners are accepted (many exactly equal responses: a 4 px checkerboard over 320 x 240); a request that is
+ *           met from the bins above such a bin is served.
+ * At most 1024 corners are returned (max_n <= 0: 1024). */
 int dv_gftt(dv_ctx* ctx, const uint8_t* img, const uint8_t* mask_or_null, int w, int h, int stride,
             int max_n, double quality, double min_dist, float* out_xy, int* n_out, int mem);
 /* cv::cornerMinEigenVal(img, eig, 3, 3) (inside goodFeaturesToTrack) */
