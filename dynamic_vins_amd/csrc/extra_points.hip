@@ -208,7 +208,9 @@ __global__ __launch_bounds__(XP_THREADS) void xp_finish_kernel(const DvExtraJob*
             }
         }
     }
-    if (tid == 0) *j.n_out = result;
+    // the second word of the slot's header: the flags raised so far, this object's among them (flag 8 by an earlier launch, flag 16 by this thread above); the host
+    // takes the union over the frame's slots (dv_inst_track_collect)
+    if (tid == 0) { j.n_out[0] = result; j.n_out[1] = a.err_flag ? atomicOr(a.err_flag, 0) : 0; }
 }
 
 }  // namespace

@@ -115,6 +115,11 @@ struct dv_inst_tracker {
     DevBuf jobs; void* jobs_pinned = nullptr; size_t jobs_cap = 0;     // DvLkJob tables of the two batched LK stages (temporal | right)
     DevBuf arena; void* arena_pinned = nullptr; size_t arena_cap = 0;  // per-frame job tables of the batched per-object stages (ROI crops, pyramid levels): filled on the host, ONE upload
     DevBuf scal, mask_all; int cand_cap = 0; int* err_flag = nullptr;
+    // device error flags of the objects' detector (err_flag: gftt.hip's 1, 2, 4, raised on `stream`) and of the extra-point kernels (xerr_flag: extra_points.hip's 8, 16,
+    // raised on `xstream`), and how a frame hands them to dv_inst_track_collect without a launch or a copy of their own: the frame's first finalize job leaves err_flag in
+    // the second word of its output slot's 64-byte tail (its err_in / err_out pair, as the background tracker's; the tail is downloaded with the rows), every
+    // xp_finish workgroup leaves xerr_flag in the second word of its pinned slot's header (read behind ev_xdone).  xp_jobs: extra-point slots written this frame
+    int* xerr_flag = nullptr; int xp_jobs = 0;
     std::vector<unsigned> out_order;                            // ids written this frame, in output order
     // extra points from the frame's disparity map (dv_inst_set_disparity; extra_points.hip): the reference's second thread = a side stream
     const float* disp_user = nullptr; int disp_stride = 0, disp_mem = 0; double disp_baseline = 0; bool disp_next = false, xp_frame = false, xp_inflight = false;
@@ -198,7 +203,7 @@ int dv_inst_config(dv_ctx* ctx, int max_dynamic_cnt, int min_dynamic_dist, int u
         const int cap = std::max(4096, (ctx->cfg.width * ctx->cfg.height) / 4);
         ctx->inst->cand_cap = cap;
         DV_CHECK(ctx->inst->scal.ensure(256)); DV_CHECK(hipMemset(ctx->inst->scal.p, 0, 256));
-        ctx->inst->err_flag = (int*)ctx->inst->scal.p + 2;
+        ctx->inst->err_flag = (int*)ctx->inst->scal.p + 2; ctx->inst->xerr_flag = (int*)ctx->inst->scal.p + 16;
     }
     dv_inst_tracker& T = *ctx->inst;
     if (T.pending) DV_FAIL("dv_inst_config: a frame is in flight");
@@ -217,7 +222,8 @@ int dv_inst_reset(dv_ctx* ctx) {
     DV_CHECK(hipStreamSynchronize(ctx->stream)); DV_CHECK(hipStreamSynchronize(ctx->inst->stream));
     for (auto& kv : ctx->inst->slots) kv.second.release();
     DV_CHECK(hipStreamSynchronize(ctx->inst->xstream));
-    ctx->inst->disp_next = ctx->inst->xp_frame = ctx->inst->xp_inflight = false;
+    ctx->inst->disp_next = ctx->inst->xp_frame = ctx->inst->xp_inflight = false; ctx->inst->xp_jobs = 0;
+    DV_CHECK(hipMemset(ctx->inst->scal.p, 0, 256));      // flags of a frame that was never collected
     ctx->inst->slots.clear(); ctx->inst->pending = false; ctx->inst->last_time = ctx->inst->cur_time = 0; ctx->inst->out_order.clear();
     return 0;
 }
@@ -286,7 +292,7 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
             if (bi >= 0) { taken[bi] = 1; S.has_box3d = true; S.box3d = boxes3d[bi]; }
         }
     }
-    T.out_order.clear();
+    T.out_order.clear(); T.xp_jobs = 0;
     if (n_dets == 0) { T.xp_frame = false; T.disp_next = false; }
     StageScope sc_all(ctx, "inst_track", s);
     if (n_dets > 0) {
@@ -433,7 +439,7 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
                 h_gs[nj] = sa;
                 dv_feat* od = (dv_feat*)((uint8_t*)T.out_buf.p + (size_t)nj * slot_bytes);
                 DvFinalizeJob f{}; f.tr = S.tr; f.cam0 = ctx->cfg.cam0; f.cam1 = ctx->cfg.cam1; f.stereo = stereo ? 1 : 0; f.use_off = 1; f.dt = dt_fin; f.out = od;
-                f.n_out = (int*)((uint8_t*)od + INST_CAP * sizeof(dv_feat)); f.err_in = nullptr; f.err_out = nullptr; f.off_x = (float)(double)S.rx; f.off_y = (float)(double)S.ry;
+                f.n_out = (int*)((uint8_t*)od + INST_CAP * sizeof(dv_feat)); f.err_in = nj == 0 ? T.err_flag : nullptr; f.err_out = nj == 0 ? f.n_out + 1 : nullptr; f.off_x = (float)(double)S.rx; f.off_y = (float)(double)S.ry;
                 h_fj[nj] = f;
                 ++nj;
             }
@@ -467,10 +473,10 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
                     dmap = (const float*)T.disp_buf.p; dpitch = W;
                 }
                 if (T.xp_pool.bytes < dv_extra_points_scratch_bytes(n_xp)) { DV_CHECK(hipStreamSynchronize(T.xstream)); DV_CHECK(T.xp_pool.ensure(dv_extra_points_scratch_bytes(std::max(8, 2 * n_xp)))); }
-                DvExtraArgs xa{ dmap, dpitch, W, H, (float)ctx->cfg.cam0.fx, (float)ctx->cfg.cam0.fy, (float)ctx->cfg.cam0.cx, (float)ctx->cfg.cam0.cy, (float)T.disp_baseline, T.err_flag, 0, (uint8_t*)T.xp_pool.p };
+                DvExtraArgs xa{ dmap, dpitch, W, H, (float)ctx->cfg.cam0.fx, (float)ctx->cfg.cam0.fy, (float)ctx->cfg.cam0.cx, (float)ctx->cfg.cam0.cy, (float)T.disp_baseline, T.xerr_flag, 0, (uint8_t*)T.xp_pool.p };
                 StageScope scx(ctx, "inst_extra_points", T.xstream);
                 if (dv_launch_extra_points((const DvExtraJob*)((const uint8_t*)T.arena.p + xp_off), n_xp, xa, T.xstream)) DV_FAIL("extra_points: cannot set dynamic LDS size");
-                T.xp_inflight = true;
+                T.xp_inflight = true; T.xp_jobs = n_xp;
             }
             { dim3 grid((roi_W + 255) / 256, roi_H, n_roi); hipLaunchKernelGGL(roi_pad_multi_kernel, grid, dim3(256), 0, s, (const RoiJob*)T.arena.p); }
             const DvPyrJob* d_pyr = (const DvPyrJob*)((const uint8_t*)T.arena.p + pyr_off);
@@ -644,6 +650,16 @@ int dv_inst_track_collect(dv_ctx* ctx, dv_inst_obs* insts, int cap_insts, int* n
     if (ctx->timing) { DV_CHECK(hipStreamSynchronize(T.stream)); dv_harvest_timers(ctx, T.stream); DV_CHECK(hipStreamSynchronize(T.xstream)); dv_harvest_timers(ctx, T.xstream); }
     const size_t xp_slot_bytes = 64 + (size_t)3 * DV_XP_CAP * sizeof(double);
     const size_t slot_bytes = INST_CAP * sizeof(dv_feat) + 64;
+    *n_insts = 0; *n_feats = 0; *n_points = 0;
+    // the limits documented beside dv_inst_config (include/dvins.h): a frame one of whose objects raised a flag is refused as a whole, as the background tracker's
+    int ef = T.out_order.empty() ? 0 : ((const int*)((const uint8_t*)T.out_pinned + INST_CAP * sizeof(dv_feat)))[1];
+    for (int k = 0; k < T.xp_jobs; ++k) ef |= ((const int*)((const uint8_t*)T.xp_pinned + (size_t)k * xp_slot_bytes))[1];
+    T.xp_jobs = 0;
+    if (ef) {
+        DV_CHECK(hipMemsetAsync(T.err_flag, 0, 4, T.stream)); DV_CHECK(hipMemsetAsync(T.xerr_flag, 0, 4, T.xstream));
+        DV_FAIL(std::string("object tracker device error flags=") + std::to_string(ef) +
+                " (1: candidate buffer overflow, 2: min-distance grid too large, 4: value bin overflow, 8: more than DV_XP_CAP sampled points, 16: clustering not converged)");
+    }
     int ki = 0, kf = 0, kp = 0;
     for (unsigned id : T.out_order) {
         auto it = T.slots.find(id);

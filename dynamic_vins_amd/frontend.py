@@ -223,6 +223,10 @@ class Context:
         from .dynsim import INSTOBS_DTYPE
         self._inst_out = (np.zeros(64, INSTOBS_DTYPE), np.zeros(64 * 256, FEAT_DTYPE), np.zeros((1 << 16, 3), np.float64))
 
+    def inst_reset(self):
+        """drops every object (dv_inst_reset); the background tracker and the shared id counter go on"""
+        self._check(self.lib.dv_inst_reset(self.h))
+
     def inst_track_enqueue(self, t, dets, boxes3d=None):
         """dets: list of dict(track_id, class_id, rect=(x, y, w, h), mask=uint8[h, w], points=float64[n, 3] or None); boxes3d: BOX3D_DTYPE array or None.
         Call right after track_stereo_enqueue of the same frame."""

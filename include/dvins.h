@@ -948,7 +948,18 @@ typedef struct dv_inst_det {
     const uint8_t* mask;                /* h rows of w bytes, > 0 = object (host memory) */
     const double* points; int32_t n_points, pad_;      /* ignored for a frame whose disparity map was handed over (dv_inst_set_disparity) */
 } dv_inst_det;
-/* fe_para::kMaxDynamicCnt / kMinDynamicDist (front_end/front_end_parameters.cpp), cfg::use_det3d; call once before the first frame */
+/* fe_para::kMaxDynamicCnt / kMinDynamicDist (front_end/front_end_parameters.cpp), cfg::use_det3d; call once before the first frame.
+ * max_dynamic_cnt in [1, 248], min_dynamic_dist in [0, 128] (0: no min-distance grid and discs of radius 0).
+ * Limits of the per-object detector and of the extra-point kernels: those stated beside dv_gftt, applied to every object's ROI (w x h = its rectangle), plus two.
+ * A frame in which ANY object exceeds one makes dv_inst_track_collect fail with "device error flags=N" (N the sum of the flags raised by all objects of the frame);
+ * nothing is returned for that frame (the three counts are 0), the flags are cleared and the context stays usable: the next dv_inst_track_enqueue / _collect pair works
+ * on the objects' state as the refused frame left it; dv_inst_reset starts over.
+ *   flag 1  more candidates in one ROI than the object's candidate buffer holds, max(4096, W * H / 4) of the context's frame size W x H;
+ *   flag 2  min_dynamic_dist >= 1 and ceil(w / d) * ceil(h / d) > 32768 grid cells for one ROI, d = min_dynamic_dist (at d = 5 a 1240 x 700 rectangle has
+ *           248 * 140 = 34720 cells; at d = 1 every rectangle over 32768 pixels);
+ *   flag 4  a value bin of more than 8192 candidates in one ROI, as for dv_gftt;
+ *   flag 8  dv_inst_set_disparity frames: more than DV_XP_CAP points sampled on one object;
+ *   flag 16 dv_inst_set_disparity frames: the clustering of one object's points did not converge. */
 int dv_inst_config(dv_ctx* ctx, int max_dynamic_cnt, int min_dynamic_dist, int use_det3d);
 int dv_inst_reset(dv_ctx* ctx);
 /* FeatureTrack's object branch for one frame (system/main.cpp:198-250): AddInstancesByTracking + InstsFeatManager::InstsTrack.  Works on the pyramids
@@ -995,7 +1006,9 @@ int dv_inst_set_right_keys(dv_ctx* ctx, const uint32_t* key_image, int stride_by
  * cloud); stage 1: InstFeat::DetectExtraPoints alone (the sampled points before any filtering).  out_xyz: cap_out triples at most, the float results widened to double. */
 int dv_extra_points(dv_ctx* ctx, const uint8_t* mask, int x, int y, int w, int h, const float* disp, int stride_bytes, int mem, double baseline, int stage,
                     double* out_xyz, int cap_out, int* n_out);
-/* InstsFeatManager::Output() (front_end/dynamic_tracker.cpp:521-577): waits for the frame; insts / feats / points are laid out as dv_est_process_dynamic takes them */
+/* InstsFeatManager::Output() (front_end/dynamic_tracker.cpp:521-577): waits for the frame; insts / feats / points are laid out as dv_est_process_dynamic takes them.
+ * Once the frame has been waited for, every failure (a device flag, see dv_inst_config; output buffers too small) ends the frame — it cannot be collected again —
+ * and leaves *n_insts = *n_feats = *n_points = 0. */
 int dv_inst_track_collect(dv_ctx* ctx, dv_inst_obs* insts, int cap_insts, int* n_insts, dv_feat* feats, int cap_feats, int* n_feats,
                           double* points, int cap_points, int* n_points);
 
