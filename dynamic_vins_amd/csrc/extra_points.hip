@@ -9,8 +9,11 @@
 //      RadiusOutlierRemoval::applyFilterIndices decides on a dense cloud; distances as flann::L2_Simple<float> ((dx dx + dy dy) + dz dz); order kept;
 //      fewer than 5 survivors: the object gets no extra points (dynamic_tracker.cpp:287-289);
 //   3. Euclidean clustering: PCL grows regions over a strict radius search (d^2 < 1) from seeds in index order — the clusters are the connected components
-//      of that graph, numbered by lowest member.  Here: min-label propagation with pointer jumping until nothing changes (a few sweeps; every sweep is an
-//      all-pairs pass over LDS), component sizes by LDS atomics, the largest component with 10 <= size <= 25000 (equal sizes: the lowest label = the cluster
+//      of that graph, numbered by lowest member.  Here: min-label propagation with pointer jumping until nothing changes; every sweep is an all-pairs pass
+//      over LDS.  XP_SWEEPS = 16 sweeps are launched: a convex blob needs 4 to 6, but a label that has to travel against the row-major scan order (a U, a
+//      serpentine) moves one < 1 m hop per sweep — 16 sweeps from a 13 m arm on, 48 at 37 m —, so xp_finish goes on to the fixed point in its one workgroup when
+//      the 16th sweep still moved a label: every cloud of up to DV_XP_CAP points gets the reference's cluster and flag 16 ("not converged") CANNOT be raised any
+//      more (tests/test_extra_points_hostile.py).  Then component sizes by LDS atomics, the largest component with 10 <= size <= 25000 (equal sizes: the lowest label = the cluster
 //      PCL finds first), members written in ascending index order (PCL sorts the indices) as doubles (PclToEigen widens the floats).
 // Integer / index work and float comparisons only: bit-exact against the CPU restatement the tests hold (tests/test_extra_points.py).
 // The mask read is the detection's mask as uploaded — NOT the 5x5-eroded one: the reference's extra-point thread races with the in-place erosion on the
@@ -55,7 +58,8 @@ __device__ __forceinline__ int xp_block_prefix(bool flag, int* s_wsum, int* tota
 //   xp_compact  (1 workgroup / object)   kept points in order, labels = own index                     -> pts_b, n_b, label[0]
 //   xp_sweep x XP_SWEEPS (n / 256 wgs)   label[i] <- min label over {d^2 < 1}, with pointer jumping on the way in; a sweep that changes nothing ends the chain
 //                                        (the later launches return at once)
-//   xp_finish   (1 workgroup / object)   component sizes, the winner, its members in index order -> out (pinned host memory), n_out
+//   xp_finish   (1 workgroup / object)   (only if the last sweep still changed a label: on to the fixed point, in place, with hooking;) component sizes, the
+//                                        winner, its members in index order -> out (pinned host memory), n_out
 #define XP_SWEEPS 16
 struct XpScratch { float4* a; float4* b; uint8_t* keep; int* lab; int* ctl; };      // per object: a[CAP] | b[CAP] | keep[CAP] | lab[2][CAP] | ctl: n_a, n_b, changed[XP_SWEEPS + 1]
 __device__ __forceinline__ XpScratch xp_scratch(uint8_t* pool, int obj) {
@@ -175,16 +179,44 @@ __global__ __launch_bounds__(XP_THREADS) void xp_finish_kernel(const DvExtraJob*
     int* csize = reinterpret_cast<int*>(xp_smem);
     __shared__ int s_wsum[XP_THREADS / 64];
     __shared__ unsigned long long s_best;
+    __shared__ int s_moved;
     const DvExtraJob j = jobs[blockIdx.x];
     const XpScratch sc = xp_scratch(a.pool, blockIdx.x);
     if (a.stage == 1) return;
     const int m = sc.ctl[1], tid = threadIdx.x;
     int result = 0;
     if (m > 0) {
-        // the sweeps ended when one changed nothing; if even the last one still did, the labels are not the components' yet: flagged, never silent
+        // the sweeps ended when one changed nothing
         int last = 0; for (int t = 0; t < XP_SWEEPS; ++t) if (sc.ctl[2 + t]) last = t + 1;
-        if (last >= XP_SWEEPS && tid == 0 && a.err_flag) atomicOr(a.err_flag, 16);
-        const int* label = sc.lab + (size_t)(min(last + 1, XP_SWEEPS) & 1) * DV_XP_CAP;      // the set the last executed sweep wrote (equal to the other one once converged)
+        int* label = sc.lab + (size_t)(min(last + 1, XP_SWEEPS) & 1) * DV_XP_CAP;      // the set the last executed sweep wrote (equal to the other one once converged)
+        if (last >= XP_SWEEPS) {
+            // even the last one still did (the lowest label travels against the scan order, one hop per sweep: a U or a serpentine): this workgroup goes on to the fixed
+            // point, labels in LDS, updated in place.  A point that finds a lower label also hands it to its old root (hook), so the next pass's pointer jumping takes
+            // it to the root's whole tree.  Labels only decrease, stay inside their component and never exceed their index: the pass that moves nothing has the
+            // components' lowest indices, whatever the order of the updates.
+            int* L = csize;
+            for (int i = tid; i < m; i += XP_THREADS) L[i] = label[i];
+            for (;;) {
+                __syncthreads();
+                if (tid == 0) s_moved = 0;
+                __syncthreads();
+                bool moved = false;
+                for (int i = tid; i < m; i += XP_THREADS) {
+                    const float4 p = sc.b[i];
+                    const int old = L[i];
+                    int lmin = L[old]; lmin = L[lmin];
+#pragma unroll 4
+                    for (int q = 0; q < m; ++q) { const int l = L[q]; lmin = (xp_d2(p, sc.b[q]) < 1.0f && l < lmin) ? l : lmin; }
+                    if (lmin < old) { atomicMin(&L[i], lmin); atomicMin(&L[old], lmin); moved = true; }
+                }
+                if (moved) s_moved = 1;
+                __syncthreads();
+                if (!s_moved) break;
+            }
+            for (int i = tid; i < m; i += XP_THREADS) label[i] = L[i];
+            __threadfence_block();
+            __syncthreads();
+        }
         for (int i = tid; i < m; i += XP_THREADS) csize[i] = 0;
         if (tid == 0) s_best = 0ull;
         __syncthreads();
@@ -208,7 +240,7 @@ __global__ __launch_bounds__(XP_THREADS) void xp_finish_kernel(const DvExtraJob*
             }
         }
     }
-    // the second word of the slot's header: the flags raised so far, this object's among them (flag 8 by an earlier launch, flag 16 by this thread above); the host
+    // the second word of the slot's header: the flags raised so far, this object's among them (flag 8 by an earlier launch; flag 16 is no longer raised); the host
     // takes the union over the frame's slots (dv_inst_track_collect)
     if (tid == 0) { j.n_out[0] = result; j.n_out[1] = a.err_flag ? atomicOr(a.err_flag, 0) : 0; }
 }

@@ -115,7 +115,7 @@ struct dv_inst_tracker {
     DevBuf jobs; void* jobs_pinned = nullptr; size_t jobs_cap = 0;     // DvLkJob tables of the two batched LK stages (temporal | right)
     DevBuf arena; void* arena_pinned = nullptr; size_t arena_cap = 0;  // per-frame job tables of the batched per-object stages (ROI crops, pyramid levels): filled on the host, ONE upload
     DevBuf scal, mask_all; int cand_cap = 0; int* err_flag = nullptr;
-    // device error flags of the objects' detector (err_flag: gftt.hip's 1, 2, 4, raised on `stream`) and of the extra-point kernels (xerr_flag: extra_points.hip's 8, 16,
+    // device error flags of the objects' detector (err_flag: gftt.hip's 1, 2, 4, raised on `stream`) and of the extra-point kernels (xerr_flag: extra_points.hip's 8,
     // raised on `xstream`), and how a frame hands them to dv_inst_track_collect without a launch or a copy of their own: the frame's first finalize job leaves err_flag in
     // the second word of its output slot's 64-byte tail (its err_in / err_out pair, as the background tracker's; the tail is downloaded with the rows), every
     // xp_finish workgroup leaves xerr_flag in the second word of its pinned slot's header (read behind ev_xdone).  xp_jobs: extra-point slots written this frame
@@ -630,7 +630,7 @@ int dv_extra_points(dv_ctx* ctx, const uint8_t* mask, int x, int y, int w, int h
     DV_CHECK(hipMemcpyAsync(&n, ob, 4, hipMemcpyDeviceToHost, s));
     DV_CHECK(hipMemcpyAsync(&ef, ctx->err_flag, 4, hipMemcpyDeviceToHost, s));
     DV_CHECK(hipStreamSynchronize(s));
-    if (ef) { DV_CHECK(hipMemsetAsync(ctx->err_flag, 0, 4, s)); DV_FAIL("dv_extra_points: more than DV_XP_CAP sampled points (8) or clustering not converged (16) (device error flags=" + std::to_string(ef) + ")"); }
+    if (ef) { DV_CHECK(hipMemsetAsync(ctx->err_flag, 0, 4, s)); DV_FAIL("dv_extra_points: more than DV_XP_CAP sampled points (8) (device error flags=" + std::to_string(ef) + ")"); }
     if (n > cap_out) DV_FAIL("dv_extra_points: output buffer too small");
     if (n > 0) DV_CHECK(hipMemcpy(out_xyz, ob + 64, (size_t)n * 24, hipMemcpyDeviceToHost));
     *n_out = n;
@@ -658,7 +658,7 @@ int dv_inst_track_collect(dv_ctx* ctx, dv_inst_obs* insts, int cap_insts, int* n
     if (ef) {
         DV_CHECK(hipMemsetAsync(T.err_flag, 0, 4, T.stream)); DV_CHECK(hipMemsetAsync(T.xerr_flag, 0, 4, T.xstream));
         DV_FAIL(std::string("object tracker device error flags=") + std::to_string(ef) +
-                " (1: candidate buffer overflow, 2: min-distance grid too large, 4: value bin overflow, 8: more than DV_XP_CAP sampled points, 16: clustering not converged)");
+                " (1: candidate buffer overflow, 2: min-distance grid too large, 4: value bin overflow, 8: more than DV_XP_CAP sampled points)");
     }
     int ki = 0, kf = 0, kp = 0;
     for (unsigned id : T.out_order) {

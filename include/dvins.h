@@ -959,7 +959,8 @@ typedef struct dv_inst_det {
  *           248 * 140 = 34720 cells; at d = 1 every rectangle over 32768 pixels);
  *   flag 4  a value bin of more than 8192 candidates in one ROI, as for dv_gftt;
  *   flag 8  dv_inst_set_disparity frames: more than DV_XP_CAP points sampled on one object;
- *   flag 16 dv_inst_set_disparity frames: the clustering of one object's points did not converge. */
+ *   flag 16 reserved, never raised: it meant "the clustering of one object's points did not converge" while the label sweeps were a fixed number of launches;
+ *           the last kernel now goes on to the fixed point, so every cloud of up to DV_XP_CAP points gets its cluster (csrc/extra_points.hip). */
 int dv_inst_config(dv_ctx* ctx, int max_dynamic_cnt, int min_dynamic_dist, int use_det3d);
 int dv_inst_reset(dv_ctx* ctx);
 /* FeatureTrack's object branch for one frame (system/main.cpp:198-250): AddInstancesByTracking + InstsFeatManager::InstsTrack.  Works on the pyramids

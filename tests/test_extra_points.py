@@ -47,11 +47,11 @@ def scene(seed, rect, kind="box"):
     return mask, (x, y), disp
 
 
-def np_detect(mask, xy, disp):
+def np_detect(mask, xy, disp, cam=CAM, base=BASE):
     h, w = mask.shape
     step = int(max(np.sqrt(0.8 * h * w / 1000.0), 2.0))
     f32 = np.float32
-    fx, fy, cx, cy = (f32(v) for v in CAM)
+    fx, fy, cx, cy = (f32(v) for v in cam)
     out = []
     for i in range(0, h, step):
         for j in range(0, w, step):
@@ -61,14 +61,15 @@ def np_detect(mask, xy, disp):
             d = disp[r, c]
             if d <= 0 or d != d:
                 continue
-            depth = f32(f32(fx * f32(BASE)) / d)
+            depth = f32(f32(fx * f32(base)) / d)
             if float(depth) <= 0.1 or float(depth) > 100:
                 continue
             out.append((f32(f32((f32(c) - cx) * depth) / fx), f32(f32((f32(r) - cy) * depth) / fy), depth))
     return np.array(out, np.float32).reshape(-1, 3)
 
 
-def np_process(p):
+def np_process(p, radius_inclusive=True, adjacency_strict=True):
+    """radius_inclusive / adjacency_strict: the two comparisons as the reference has them; tests/xp_cases.py flips one to prove that a case sits on the threshold"""
     p = np.asarray(p, np.float32).reshape(-1, 3)
     n = len(p)
     if n == 0:
@@ -78,11 +79,11 @@ def np_process(p):
         dx = a[:, None, 0] - b[None, :, 0]; dy = a[:, None, 1] - b[None, :, 1]; dz = a[:, None, 2] - b[None, :, 2]
         return ((dx * dx + dy * dy).astype(np.float32) + dz * dz).astype(np.float32)
     D = d2(p, p)
-    keep = (D <= np.float32(0.25)).sum(1) >= 11
+    keep = ((D <= np.float32(0.25)) if radius_inclusive else (D < np.float32(0.25))).sum(1) >= 11
     f = p[keep]
     if len(f) < 5:
         return np.zeros((0, 3), np.float32)
-    A = d2(f, f) < np.float32(1.0)
+    A = (d2(f, f) < np.float32(1.0)) if adjacency_strict else (d2(f, f) <= np.float32(1.0))
     ncomp, lab = connected_components(coo_matrix(A), directed=False)
     best, best_size = -1, 0
     for c in range(ncomp):                 # components in order of their lowest member = PCL's discovery order

@@ -6,8 +6,8 @@ association's tests, the detector's limits — and the figures are printed.
 GPU: dv_track_stereo_enqueue / dv_inst_track_enqueue / the two collects against OracleTracker.track_image + OracleInsts.track on the same frames, bit for bit: the
 background rows, the instance table field by field, the object rows (ids, track counts, has_right, uint64 patterns), the points.  No tolerance anywhere.
 The limits (include/dvins.h beside dv_inst_config): a frame one of whose objects exceeds one is refused by dv_inst_track_collect with "device error flags=N", the
-context stays usable, and after dv_inst_reset parity holds again.  Flags 8 and 16 (extra points) have no input in tests/test_extra_points.py that raises them and are
-not driven here."""
+context stays usable, and after dv_inst_reset parity holds again.  Flag 8 (extra points) needs an image 8000 px wide and is driven through the operator form in
+tests/test_extra_points_hostile.py; flag 16 is no longer raised (include/dvins.h)."""
 import ctypes as C
 
 import numpy as np
