@@ -135,6 +135,11 @@ SIGNATURES = {
     "dv_mot_update_collect": (C.c_int, [_ctx, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dv_mot_get_tracks": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "dv_mot_assign": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dv_line_track_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "dv_line_track_reset": (C.c_int, [_ctx]),
+    "dv_line_track_enqueue": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "dv_line_track_collect": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "dv_line_match": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "dv_reid_check": (C.c_int, [C.c_size_t, C.c_int, C.c_int]),
     "dv_reid_load": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
     "dv_reid_extract_enqueue": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),

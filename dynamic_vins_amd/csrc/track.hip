@@ -14,21 +14,7 @@
 //   erode_{h,v}_kernel   : cv::erode rect k x k                 (feature_utils.h:130-146)
 //   lift_kernel          : PinholeCamera::liftProjective        (PinholeCamera.cc:450-508)
 #include "dv_internal.h"
-
-__device__ void dv_lift_projective_d(const dv_cam& c, double px, double py, double& ox, double& oy) {
-    const double ik11 = 1.0 / c.fx, ik13 = -c.cx / c.fx, ik22 = 1.0 / c.fy, ik23 = -c.cy / c.fy;
-    const double mx_d = ik11 * px + ik13, my_d = ik22 * py + ik23;
-    if (c.k1 == 0.0 && c.k2 == 0.0 && c.p1 == 0.0 && c.p2 == 0.0) { ox = mx_d; oy = my_d; return; }   // m_noDistortion
-    double mx_u = mx_d, my_u = my_d;
-    for (int i = 0; i < 8; ++i) {       // recursive distortion model, n = 8
-        double mx2 = mx_u * mx_u, my2 = my_u * my_u, mxy = mx_u * my_u, rho2 = mx2 + my2;
-        double rad = c.k1 * rho2 + c.k2 * rho2 * rho2;
-        double dx = mx_u * rad + 2.0 * c.p1 * mxy + c.p2 * (rho2 + 2.0 * mx2);
-        double dy = my_u * rad + 2.0 * c.p2 * mxy + c.p1 * (rho2 + 2.0 * my2);
-        mx_u = mx_d - dx; my_u = my_d - dy;
-    }
-    ox = mx_u; oy = my_u;
-}
+#include "lift_dev.h"
 
 __device__ __forceinline__ void track_compact_body(const DvTrackState& tr, const uint8_t* __restrict__ in_mask, int mask_pitch,
                                                    int sort_by_cnt, int* n_cand, unsigned* max_ord) {

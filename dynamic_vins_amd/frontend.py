@@ -116,6 +116,28 @@ def mot_check(params):
 
 DV_REID_N_FLOATS, DV_REID_FEAT_DIM, DV_REID_MAX_CROPS = 11178496, 512, 64
 
+# dv_key_line: what LineDetector::Detect leaves of a cv::line_descriptor::KeyLine (line_detector/line_detector.cpp:82-96)
+KEYLINE_DTYPE = np.dtype([("sx", np.float32), ("sy", np.float32), ("ex", np.float32), ("ey", np.float32), ("angle", np.float32), ("length", np.float32)])
+assert KEYLINE_DTYPE.itemsize == 24
+DV_LINE_MAX, DV_LINE_DESC_BYTES = 512, 32
+
+
+def _key_lines(lines, desc):
+    """host key lines ([n, 6] float32 or KEYLINE_DTYPE records) and descriptors ([n, 32] uint8), contiguous -> (lines, desc, n)"""
+    lines = np.asarray(lines)
+    lines = np.ascontiguousarray(lines.view(np.float32) if lines.dtype == KEYLINE_DTYPE else lines, np.float32).reshape(-1, 6)
+    desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, DV_LINE_DESC_BYTES)
+    if len(lines) != len(desc):
+        raise ValueError("one descriptor row per key line")
+    return lines, desc, len(lines)
+
+
+def line_track_check(left_lines, left_desc, n_left, right_lines=None, right_desc=None, n_right=0, mem=DV_MEM_HOST):
+    """the refusals of Context.line_track_enqueue, without a device (pointers as int or host arrays): raises DvinsError with the reason"""
+    lib = _abi.load()
+    if lib.dv_line_track_check(_ptr(left_lines), _ptr(left_desc), int(n_left), _ptr(right_lines), _ptr(right_desc), int(n_right), int(mem)) != 0:
+        raise DvinsError(lib.dv_last_error(None).decode())
+
 
 def reid_check(n_floats, in_w=64, in_h=128):
     """the refusals of Context.reid_load, without a device: raises DvinsError with the reason"""
@@ -429,6 +451,52 @@ class Context:
         out = np.full(max(rows, 1), -1, np.int32)
         self._check(self.lib.dv_mot_assign(self.h, cost.ctypes.data if cost.size else None, rows, cols, out.ctypes.data))
         return out[:rows].copy()
+
+    # ---- the line tracker (LineDetector::TrackLeftLine / TrackRightLine, line_detector/line_detector.cpp:101-297): key lines + LBD descriptors -> ids, counts, rows ----
+    def line_track_reset(self):
+        """no previous frame, id counter back to 0"""
+        self._check(self.lib.dv_line_track_reset(self.h))
+
+    def line_track_enqueue(self, left_lines, left_desc, right_lines=None, right_desc=None, n_left=None, n_right=0, mem=DV_MEM_HOST):
+        """Host: left_lines [n, 6] float32 (KEYLINE_DTYPE order), left_desc [n, 32] uint8; right_* the same or None (no right image).  Device / pinned: raw pointers
+        (int) with n_left / n_right, valid until line_track_collect."""
+        if mem == DV_MEM_HOST:
+            left_lines, left_desc, n_left = _key_lines(left_lines, left_desc)
+            if right_lines is not None:
+                right_lines, right_desc, n_right = _key_lines(right_lines, right_desc)
+        elif n_left is None:
+            raise ValueError("line_track_enqueue: n_left is required with device or pinned pointers")
+        self._line_keep = (left_lines, left_desc, right_lines, right_desc)
+        has_r = right_lines is not None
+        self._check(self.lib.dv_line_track_enqueue(self.h, _ptr(left_lines) if n_left else None, _ptr(left_desc) if n_left else None, int(n_left),
+                                                   _ptr(right_lines) if has_r and n_right else None, _ptr(right_desc) if has_r and n_right else None, int(n_right) if has_r else 0, int(mem)))
+
+    def line_track_collect(self):
+        """-> dict: rows (LINEROW_DTYPE, ascending id: what Estimator.set_lines takes), left_ids / left_src / left_cnt and right_ids / right_src per surviving line in
+        output order (*_src = the line's index in the enqueued array)"""
+        from .backend import LINEROW_DTYPE
+        rows = np.zeros(DV_LINE_MAX, LINEROW_DTYPE)
+        lid, lsrc, lcnt = np.zeros(DV_LINE_MAX, np.uint32), np.zeros(DV_LINE_MAX, np.int32), np.zeros(DV_LINE_MAX, np.int32)
+        rid, rsrc = np.zeros(DV_LINE_MAX, np.uint32), np.zeros(DV_LINE_MAX, np.int32)
+        nr, nl, nrt = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._line_keep = None
+        self._check(self.lib.dv_line_track_collect(self.h, rows.ctypes.data, len(rows), C.byref(nr), lid.ctypes.data, lsrc.ctypes.data, lcnt.ctypes.data, C.byref(nl),
+                                                   rid.ctypes.data, rsrc.ctypes.data, C.byref(nrt)))
+        return {"rows": rows[: nr.value].copy(), "left_ids": lid[: nl.value].copy(), "left_src": lsrc[: nl.value].copy(), "left_cnt": lcnt[: nl.value].copy(),
+                "right_ids": rid[: nrt.value].copy(), "right_src": rsrc[: nrt.value].copy()}
+
+    def line_track(self, left_lines, left_desc, right_lines=None, right_desc=None, **kw):
+        """line_track_enqueue + line_track_collect"""
+        self.line_track_enqueue(left_lines, left_desc, right_lines, right_desc, **kw)
+        return self.line_track_collect()
+
+    def line_match(self, query_desc, train_desc):
+        """BinaryDescriptorMatcher::match(query, train) alone on [n, 32] uint8 rows -> (train_idx, distance) int32; -1 / 0 where the minimum distance is >= 30"""
+        q = np.ascontiguousarray(query_desc, np.uint8).reshape(-1, DV_LINE_DESC_BYTES)
+        t = np.ascontiguousarray(train_desc, np.uint8).reshape(-1, DV_LINE_DESC_BYTES)
+        idx, dist = np.full(max(len(q), 1), -1, np.int32), np.zeros(max(len(q), 1), np.int32)
+        self._check(self.lib.dv_line_match(self.h, q.ctypes.data if len(q) else None, len(q), t.ctypes.data if len(t) else None, len(t), idx.ctypes.data, dist.ctypes.data))
+        return idx[: len(q)].copy(), dist[: len(q)].copy()
 
     # ---- the ReID extractor (Extractor::extract, mot/extractor.cpp:31-52; ReIdNetImpl, mot/reid_net.cpp): colour image + rectangles -> [n, 512] embeddings on the device ----
     def reid_load(self, weights, in_w=64, in_h=128):

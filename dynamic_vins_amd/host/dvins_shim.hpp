@@ -387,6 +387,106 @@ inline std::vector<dv_feat> to_rows(const FeatureBackground& fb) {
 }  // namespace detail
 
 // ---------------------------------------------------------------------------------------------------------------
+// FrameLines (basic/frame_lines.h) of plain structs: what LineDetector::Detect leaves (line_detector/line_detector.cpp:82-96) — a KeyLine's start / end point, angle and
+// lineLength as dv_key_line, one 32-byte LBD row per line — and what the tracker adds: line_ids, track_cnt, and `src`, the index of every surviving line in the detected
+// array (the tracker reorders and drops lines).
+struct FrameLines {
+    using Ptr = std::shared_ptr<FrameLines>;
+    std::vector<dv_key_line> keylsd;
+    std::vector<std::array<uint8_t, DV_LINE_DESC_BYTES>> lbd_descr;
+    std::vector<unsigned int> line_ids;
+    std::map<unsigned int, int> track_cnt;
+    std::vector<int> src;
+};
+
+// LineDetector's tracking half (line_detector/line_detector.cpp:101-297) on the device: dv_line_track_enqueue / _collect.  LSD and the LBD descriptor stay with the caller.
+// The previous left frame lives on the device, so TrackLeftLine's `prev` only says whether there is one: nullptr resets the tracker (the reference's first frame),
+// anything else must be the FrameLines the last frame was tracked into.  The device tracks both images in ONE launch: with stereo = true TrackLeftLine only records the
+// left detections and TrackRightLine runs the frame and fills both; with stereo = false TrackLeftLine runs it.  So between the two calls `curr` is NOT yet what the
+// reference's TrackLeftLine leaves (background_tracker.cpp:173-177 reads curr_lines there): TrackLeftLine empties curr's line_ids, track_cnt and src to say so, keylsd
+// and lbd_descr stay as detected, and a port reads them behind TrackRightLine.  Track() is both in one call; enqueue() / collect() is the two-phase form.
+// rows(): the frame's dv_line_rows (FeatureBackground::lines, ready for dv_est_set_lines).
+// The tracker's state (resident previous frame, id counter) belongs to the dv_ctx, not to this object: every LineDetector on one ctx, FeatureTracker's own included,
+// drives the same tracker.  The check of `prev` catches a second object stepping in only where it passes a frame; keep one LineDetector per ctx.
+class LineDetector {
+public:
+    using Ptr = std::shared_ptr<LineDetector>;
+    explicit LineDetector(dv_ctx* ctx, bool stereo = true) : ctx_(ctx), stereo_(stereo) {}
+    LineDetector(const LineDetector&) = delete;
+    LineDetector& operator=(const LineDetector&) = delete;
+    // the refusals of a frame without a device: throws with the library's reason
+    static void Check(const FrameLines& left, const FrameLines* right = nullptr) {
+        if (left.keylsd.size() != left.lbd_descr.size() || (right && right->keylsd.size() != right->lbd_descr.size())) throw std::runtime_error("LineDetector: one descriptor row per key line");
+        if (left.keylsd.size() > (size_t)INT32_MAX || (right && right->keylsd.size() > (size_t)INT32_MAX)) throw std::runtime_error("LineDetector: too many lines");
+        if (dv_line_track_check(left.keylsd.data(), desc(left), (int)left.keylsd.size(), right ? right->keylsd.data() : nullptr, right ? desc(*right) : nullptr,
+                                right ? (int)right->keylsd.size() : 0, DV_MEM_HOST) != 0)
+            throw std::runtime_error(std::string("LineDetector: ") + dv_last_error(nullptr));
+    }
+    void reset() { detail::check(ctx_, dv_line_track_reset(ctx_), "LineDetector::reset"); last_.reset(); left_.reset(); }
+    void TrackLeftLine(const FrameLines::Ptr& prev, const FrameLines::Ptr& curr) {
+        if (!curr) throw std::runtime_error("LineDetector::TrackLeftLine: null frame");
+        begin(prev);
+        left_ = curr;
+        curr->line_ids.clear(); curr->track_cnt.clear(); curr->src.clear();      // not tracked yet (stereo: until TrackRightLine)
+        if (!stereo_) { enqueue(curr, nullptr); collect(); }
+    }
+    void TrackRightLine(const FrameLines::Ptr& left, const FrameLines::Ptr& right) {
+        if (!stereo_) throw std::runtime_error("LineDetector::TrackRightLine: the detector was made without a right image");
+        if (!left || left != left_ || !right) throw std::runtime_error("LineDetector::TrackRightLine: TrackLeftLine(prev, left) first");
+        enqueue(left, right); collect();
+    }
+    const std::vector<dv_line_row>& Track(const FrameLines::Ptr& prev, const FrameLines::Ptr& left, const FrameLines::Ptr& right) {
+        if (!left) throw std::runtime_error("LineDetector::Track: null frame");
+        begin(prev);
+        enqueue(left, right);
+        return collect();
+    }
+    // on the ctx's stream; the FrameLines stay untouched until collect()
+    void enqueue(const FrameLines::Ptr& left, const FrameLines::Ptr& right) {
+        Check(*left, right.get());
+        detail::check(ctx_, dv_line_track_enqueue(ctx_, left->keylsd.data(), desc(*left), (int)left->keylsd.size(), right ? right->keylsd.data() : nullptr,
+                                                  right ? desc(*right) : nullptr, right ? (int)right->keylsd.size() : 0, DV_MEM_HOST), "LineDetector");
+        pend_left_ = left; pend_right_ = right;
+    }
+    const std::vector<dv_line_row>& collect() {
+        if (!pend_left_) throw std::runtime_error("LineDetector::collect: nothing enqueued");
+        rows_.resize(DV_LINE_MAX);
+        std::vector<uint32_t> lid(DV_LINE_MAX), rid(DV_LINE_MAX);
+        std::vector<int32_t> lsrc(DV_LINE_MAX), lcnt(DV_LINE_MAX), rsrc(DV_LINE_MAX);
+        int nrow = 0, nl = 0, nr = 0;
+        FrameLines::Ptr left = std::move(pend_left_), right = std::move(pend_right_);
+        pend_left_.reset(); pend_right_.reset();
+        detail::check(ctx_, dv_line_track_collect(ctx_, rows_.data(), (int)rows_.size(), &nrow, lid.data(), lsrc.data(), lcnt.data(), &nl, rid.data(), rsrc.data(), &nr), "LineDetector");
+        rows_.resize((size_t)nrow);
+        apply(*left, lid.data(), lsrc.data(), lcnt.data(), nl);
+        if (right) apply(*right, rid.data(), rsrc.data(), nullptr, nr);
+        last_ = left; left_.reset();
+        return rows_;
+    }
+    const std::vector<dv_line_row>& rows() const { return rows_; }
+
+private:
+    void begin(const FrameLines::Ptr& prev) {
+        if (!prev) reset();
+        else if (prev != last_) throw std::runtime_error("LineDetector: the previous frame is resident on the device: pass the FrameLines of the last frame, or nullptr to start over");
+    }
+    static const uint8_t* desc(const FrameLines& f) { return f.lbd_descr.empty() ? nullptr : f.lbd_descr[0].data(); }
+    // curr_keylsd = vecLine_tracked, curr_line_ids = lineID_tracked, curr_lbd = descr_tracked (line_detector.cpp:221-223,294-296); a count of 0 is "no entry"
+    static void apply(FrameLines& f, const uint32_t* ids, const int32_t* src, const int32_t* cnt, int n) {
+        std::vector<dv_key_line> k((size_t)n); std::vector<std::array<uint8_t, DV_LINE_DESC_BYTES>> d((size_t)n);
+        f.line_ids.assign(ids, ids + n); f.src.assign(src, src + n); f.track_cnt.clear();
+        for (int i = 0; i < n; ++i) {
+            k[i] = f.keylsd.at((size_t)src[i]); d[i] = f.lbd_descr.at((size_t)src[i]);
+            if (cnt && cnt[i] > 0) f.track_cnt.insert({ ids[i], cnt[i] });
+        }
+        f.keylsd.swap(k); f.lbd_descr.swap(d);
+    }
+    dv_ctx* ctx_; bool stereo_;
+    FrameLines::Ptr last_, left_, pend_left_, pend_right_;
+    std::vector<dv_line_row> rows_;
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 class FeatureTracker {
 public:
     using Ptr = std::shared_ptr<FeatureTracker>;
@@ -434,6 +534,22 @@ public:
         };
         put(left, 0);
         if (cfg_.stereo) put(right, 1);
+        return fb;
+    }
+    // the same with the line half on the device: the frame's UNMATCHED detections and their descriptors go through LineDetector (TrackLeftLine / TrackRightLine,
+    // SetLines, UndistortedLineEndPoints) on the tracker's own stream, enqueued in front of the point half and collected behind it; `left` / `right` come back as the
+    // reference leaves curr_lines / curr_lines_right.  first = true is the reference's bg.prev_lines == nullptr.  The tracker is the ctx's (see LineDetector): do not drive
+    // a LineDetector of your own on ctx() beside this overload.
+    FeatureBackground TrackImageLine(SemanticImage& img, const FrameLines::Ptr& left, const FrameLines::Ptr& right, bool first = false) {
+        if (!line_detector_) line_detector_ = std::make_shared<LineDetector>(ctx_, cfg_.stereo != 0);
+        if (first) line_detector_->reset();
+        line_detector_->enqueue(left, cfg_.stereo ? right : nullptr);
+        FeatureBackground fb;
+        try { fb = track(img, DV_MODE_RAW); } catch (...) { try { line_detector_->collect(); } catch (...) {} throw; }
+        for (const dv_line_row& r : line_detector_->collect()) {
+            fb.lines.insert({ r.id, { { 0, Line{ r.id, r.left[0], r.left[1], r.left[2], r.left[3] } } } });
+            if (r.has_right) fb.lines[r.id].push_back({ 1, Line{ r.id, r.right[0], r.right[1], r.right[2], r.right[3] } });
+        }
         return fb;
     }
     // two-phase form: lets the caller overlap the front end of frame k+1 with the back end of frame k
@@ -547,6 +663,7 @@ private:
     dv_ctx* ctx_ = nullptr;
     std::vector<dv_feat> rows_;
     int n_rows_ = 0;
+    LineDetector::Ptr line_detector_;      // TrackImageLine's device line half, made on first use
 };
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -779,6 +779,52 @@ int dv_est_get_lines(dv_ctx* ctx, dv_line_landmark* out, int cap, int* n_out);
 /* FrameLines::UndistortedLineEndPoints (front_end side of TrackImageLine, line_detector): end points (x1 y1 x2 y2 pixels) -> normalised, undistorted */
 int dv_undistort_lines(dv_ctx* ctx, const dv_cam* cam, const float* lines_xyxy, int n, double* out_xyxy);
 
+/* The LINE TRACKER on the device: a frame's detected key lines and their 32-byte LBD descriptors -> the frame's dv_line_rows, ready for dv_est_set_lines.  Reference:
+ * LineDetector::TrackLeftLine / TrackLine / TrackRightLine (line_detector/line_detector.cpp:101-297) behind LineDetector::Detect (:60-98) and in front of
+ * FrameLines::SetLines / UndistortedLineEndPoints (basic/frame_lines.cpp:15-45) and SetOutputFeats' `lines` map (front_end/background_tracker.cpp:167-189,373-389).
+ * LSD and the LBD descriptor themselves stay upstream.  The previous left frame's lines, ids, descriptors and track counts are resident; so is the id counter.
+ *   input        per line what Detect leaves (:82-96): KeyLine::startPointX/Y, endPointX/Y, angle, lineLength (dv_key_line, float32) and one descriptor row.
+ *   match        BinaryDescriptorMatcher::match(query, train) (thirdparty/line_descriptor/src/binary_descriptor_matcher.cpp:197-254) with Mihasher(256, 32), K = 1: a
+ *                multi-index hash search (:635-753) over 32 one-byte substrings (bitops_custom.hpp:99-123) whose buckets keep ascending train order (:926-947).  Below
+ *                distance 32 it never leaves search radius s = 0 and stops at substring k = the minimum distance, so it returns, among the train rows at the minimum
+ *                distance, the one least by (index of its first byte equal to the query's, train index).  Only distance < 30 is accepted downstream: the kernel
+ *                evaluates that closed form and reports "no match" from 30 on (above 128 the reference leaves its result unwritten).  Either side empty: no matches
+ *                (:201-205).
+ *   gate         distance < 30, serr . serr < 200 * 200, eerr . eerr < 200 * 200, abs(angle1 - angle2) < 0.1 (line_detector.cpp:116-124): serr = query start - train END,
+ *                eerr = query end - train END (sic), cv::Point2f arithmetic: float32 products and one float32 add, never fused; abs taken as the float overload.
+ *                A matched line takes the train line's id; several query lines may take one train line and so one id.  The "-1" id is 0xFFFFFFFF.
+ *   new ids      every unmatched line takes the next id of the counter in line order, the lines the quota then drops included (:146-158).
+ *   quota        unmatched lines are "h" when angle is in [3.14/4, 3*3.14/4] or [-3*3.14/4, -3.14/4] (double literals), else "v" (:164-176).  Output order: tracked lines
+ *                in their order, then the first 35 - h_tracked new h lines, then the first 35 - v_tracked new v lines (:190-223).
+ *   first frame  (no previous frame, :229-234) every line a fresh id, no quota, no counts.  A previous frame WITHOUT lines is not a first frame.
+ *   counts       curr[id] = prev[id] + 1 for matched ids (missing: 0); a v top-up gets 1, an h top-up NO entry (:128-139,218).  Reported: the map's value, 0 for none.
+ *   right        matched against the left set after the quota, same gate; only matched right lines are kept, in right order (:246-297).
+ *   rows         one per left id in ascending id (the std::map's order): the first left line of the id (map::insert, background_tracker.cpp:376-380) and, if any, the
+ *                FIRST right line of the id — vec_feat[1] is the only right entry FeatureManager::AddFeatureCheckParallax reads (estimator/feature_manager.cpp:127-128).
+ *                End points lifted with the ctx's cam0 / cam1 exactly as dv_undistort_lines lifts them.
+ * Differences, declared: one id counter per tracker, starting at 0 (the reference's global_line_id is a member of its one LineDetector); no match from distance 30 on.
+ * A ctx has ONE tracker: the resident previous frame and the id counter belong to the dv_ctx, so every caller of dv_line_track_* on a ctx (two LineDetector objects of
+ * the shim, say) feeds the same sequence of frames.  Two independent line streams take two ctxs.
+ * dv_line_track_check: the refusals of _enqueue without a device (more than DV_LINE_MAX lines in an image, null or misaligned pointers, unknown memory kind).
+ * dv_line_track_reset: no previous frame, counter back to 0.
+ * _enqueue: on the ctx's stream.  mem = DV_MEM_HOST (all four arrays staged; valid until the call returns) or DV_MEM_DEVICE / DV_MEM_PINNED (read in place until the
+ * collect; each pointer may be of either in-place kind).  right_lines = right_desc = NULL, n_right = 0: no right image.  n_left = 0, n_right = 0 are ordinary frames.  One
+ * frame may be in flight.  ONE launch; no host round trip between _enqueue and _collect: the frame's only device -> host traffic is the rows, the per-line words and a
+ * few counters through pinned memory.
+ * _collect: rows[min(cap, *n_rows)]; per surviving left line, in output order, its id, the index of the line in the enqueued array (*_src) and its track count; per
+ * surviving right line its id and index.  The per-line arrays hold DV_LINE_MAX entries or are NULL.
+ * dv_line_match: the match step alone, in operator form on host memory (nq, nt <= DV_LINE_MAX): train_idx[i] = the row BinaryDescriptorMatcher::match returns for query
+ * i and distance[i] its distance; -1 and 0 where the minimum distance is >= 30. */
+#define DV_LINE_MAX 512
+#define DV_LINE_DESC_BYTES 32
+typedef struct dv_key_line { float sx, sy, ex, ey, angle, length; } dv_key_line;
+int dv_line_track_check(const dv_key_line* left_lines, const uint8_t* left_desc, int n_left, const dv_key_line* right_lines, const uint8_t* right_desc, int n_right, int mem);
+int dv_line_track_reset(dv_ctx* ctx);
+int dv_line_track_enqueue(dv_ctx* ctx, const dv_key_line* left_lines, const uint8_t* left_desc, int n_left, const dv_key_line* right_lines, const uint8_t* right_desc, int n_right, int mem);
+int dv_line_track_collect(dv_ctx* ctx, dv_line_row* rows, int cap, int* n_rows, uint32_t* left_ids, int32_t* left_src, int32_t* left_cnt, int* n_left_out,
+                          uint32_t* right_ids, int32_t* right_src, int* n_right_out);
+int dv_line_match(dv_ctx* ctx, const uint8_t* query_desc, int nq, const uint8_t* train_desc, int nt, int32_t* train_idx, int32_t* distance);
+
 /* ---- the members of Estimator the callbacks and publishers use besides ProcessMeasurements (estimator/estimator.h:55-164) ---- */
 /* Estimator::ChangeSensorType (estimator.cpp:697-726; the /vins_imu_switch, /vins_cam_switch callbacks): switching the IMU on restarts the estimator
  * (ClearState + SetParameter), switching it off drops the prior.  use_stereo = 0 is refused (monocular initialisation is out of scope). */
