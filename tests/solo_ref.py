@@ -45,9 +45,10 @@ def matrix_nms(seg_masks, cate_labels, cate_scores, sum_mask, kernel, sigma):
     return cate_scores * coef
 
 
-def head(kernels, cates, feature, par, dtype):
+def head(kernels, cates, feature, par, dtype, stable=False):
     """GetSegTensor up to the second sort -> dict; every early return gives n = 0.  Inputs: numpy arrays or torch tensors; par["device"] (default "cpu") is where torch
-    evaluates it (tests/tools/solo_head_cost.py runs these same lines on the GPU)"""
+    evaluates it (tests/tools/solo_head_cost.py runs these same lines on the GPU).  stable = True makes both sorts stable — equal scores stay in candidate order, then in
+    first-sort order: the library's documented tie rule, which the reference's own unstable sort leaves open (the tie cases of tests/solo_cases.py)"""
     dev, lean = par.get("device", "cpu"), bool(par.get("lean"))          # lean: none of the diagnostic downloads below (the cost tool's timed runs)
     as_t = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(a)).to(dev, dtype)
     C = feature.shape[0]
@@ -80,7 +81,7 @@ def head(kernels, cates, feature, par, dtype):
     if not lean:
         out["seg_scores"] = (((seg * masks.to(dtype)).sum((1, 2)) / sums).cpu(), cand_idx.cpu())
     cate = cate * ((seg * masks.to(dtype)).sum((1, 2)) / sums)
-    order = torch.argsort(cate, -1, True)[: par["nms_pre"]]
+    order = torch.argsort(cate, dim=-1, descending=True, stable=stable)[: par["nms_pre"]]
     masks, seg, sums, cate, labels, cand_idx = masks[order], seg[order], sums[order], cate[order], labels[order], cand_idx[order]
     if not lean:
         out["sorted"] = (cand_idx.cpu().numpy().copy(), cate.cpu().numpy().copy())
@@ -92,7 +93,7 @@ def head(kernels, cates, feature, par, dtype):
     if int(keep.sum()) == 0:
         return out
     seg, scores, labels, cand_idx = seg[keep], scores[keep], labels[keep], cand_idx[keep]
-    order = torch.argsort(scores, -1, True)[: par["max_per_img"]]
+    order = torch.argsort(scores, dim=-1, descending=True, stable=stable)[: par["max_per_img"]]
     out.update(n=len(order), seg=seg[order], scores=scores[order].cpu().numpy().copy(), labels=labels[order].cpu().numpy().astype(np.int32), survivors=cand_idx[order].cpu().numpy().copy())
     return out
 
@@ -107,8 +108,8 @@ def resample(seg, par):
     return v.squeeze(0)
 
 
-def reference(inp, par, dtype):
-    out = head(inp["kernels"], inp["cates"], inp["feature"], par, dtype)
+def reference(inp, par, dtype, stable=False):
+    out = head(inp["kernels"], inp["cates"], inp["feature"], par, dtype, stable)
     if out["n"]:
         out["values"] = resample(out["seg"], par).cpu().numpy()
         out["planes"] = out["values"] > par["mask_thr"]

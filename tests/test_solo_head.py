@@ -7,10 +7,14 @@ computes from the reference alone: the float64 result (the yardstick) and delta,
                               plane may have more than 1 % of its pixels inside that band
   padding bytes               zero
   the stack                   fed to dv_inst_stack_frame_enqueue / _collect gives what tests/test_inst_stack.py's torch_reference / expected_dets give for the head's planes
-Shapes are the smallest where each kernel can go wrong: channels 128 / 12 (a K tail), feature 24 x 72 (whole waves, whole words) / 7 x 13 (word, wave and row tails), grids
-5 4 3 2 2 against num_grids 2 2 3 4 5 (boundaries inside a level) with a flat and a position-dependent stride table, 80 / 3 classes, three origins, both rect branches,
-candidate counts 1 / 63 / 65 / nms_pre + 4 / max_candidates, survivors 1 / max_per_img / max_per_img + 3, both NMS kernels, three memory kinds, two frames back to back,
-the three empty outcomes and one over-capacity frame."""
+What this module reaches: random blob masks (every IoU, decay chains of many candidates) from solo_ref.make_case, channels 128 / 12, feature 24 x 72 (whole waves, whole
+words) / 7 x 13 (word, wave and row tails), grids 5 4 3 2 2 against num_grids 2 2 3 4 5 (boundaries inside a level) with a flat and a position-dependent stride table,
+80 / 3 classes, three origins, both rect branches, candidate counts 1 / 63 / 65 / nms_pre + 4 / 72, survivors 1 / max_per_img / max_per_img + 3, both NMS kernels, three
+memory kinds, two frames back to back, the three empty outcomes, one over-capacity frame, and the stack handed on to the stack stage and the pipeline.
+What it does NOT reach, because make_case's random search finds no spaced scores beyond some 70 candidates: a second workgroup of cells or a second scan iteration (58
+cells), more than 1024 candidates in the sort, more than 64 mask words, more than 80 sorted candidates or 2 NMS waves, an odd channel count or 256 channels, an origin wider
+than 256, an upsampling second interpolation, a NaN, an exact tie, or the reference's own configuration.  Those are tests/test_solo_head_limits.py, on the constructed
+inputs of tests/solo_cases.py, through the same check_against."""
 import numpy as np
 import pytest
 
@@ -79,9 +83,14 @@ def planes_of(st, n, w, h):
 
 def check_frame(ctx, case, mem, keep):
     inp, par, r64, delta = case_ref(case)
+    return check_against(ctx, inp, par, r64, delta, mem, keep, f"case {CASES.index(case)}")[:2]
+
+
+def check_against(ctx, inp, par, r64, delta, mem, keep, tag):
+    """one frame on the device against a float64 reference and its delta: THE checks of this stage (tests/test_solo_head_limits.py runs its cases through them too)"""
     w, h = par["origin"]
     labels, scores, st, n_pass = ctx.solo_head(device_outputs(inp, mem, keep), to_params(par))
-    print(f"case {CASES.index(case)} {mem}: n {len(labels)} (ref {r64['n']}), cells over score_thr {n_pass}, delta {delta:.3g}")
+    print(f"{tag} {mem}: n {len(labels)} (ref {r64['n']}), cells over score_thr {n_pass}, delta {delta:.3g}")
     assert n_pass == r64["n_pass"] and len(labels) == r64["n"] and np.array_equal(labels, r64["labels"])
     rel = np.abs(scores.astype(np.float64) - r64["scores"]) / r64["scores"]
     print("  largest relative score deviation", rel.max())
@@ -93,7 +102,7 @@ def check_frame(ctx, case, mem, keep):
     print("  pixels in the band per plane (max)", frac.max(), "differing outside the band", int(((planes != 0) != r64["planes"])[~band].sum()))
     assert frac.max() <= 0.01, "more than 1 % of a plane's pixels lie within 4 delta of mask_thr"
     assert np.array_equal((planes != 0)[~band], r64["planes"][~band])
-    return planes, st
+    return planes, st, labels, scores
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"c{c[0]}_f{c[1][0]}x{c[1][1]}_k{c[2]}_o{c[3][0]}x{c[3][1]}_n{c[6]}_{c[8]}_{c[9]}")

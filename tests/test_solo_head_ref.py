@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import solo_ref
+from tests import solo_cases, solo_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRIDS = (5, 4, 3, 2, 2)
@@ -42,6 +42,35 @@ def test_float32_and_float64_reference_agree(case):
     delta = np.abs(r64["values"] - r32["values"].astype(np.float64)).max()
     differ = r64["planes"] != r32["planes"]
     assert delta < 1e-4 and (np.abs(r64["values"][differ] - par["mask_thr"]) < 1e-5).all()
+
+
+@pytest.mark.parametrize("name", list(solo_cases.BUILDERS))
+def test_constructed_case_stands_on_the_reference_alone(name):
+    """every case of tests/test_solo_head_limits.py, before a GPU sees it: the float32 and the float64 reference agree on n_pass, the candidates, the first sort, the
+    survivors and the labels; the logits are bit-equal; no plane has more than 1 % of its pixels within 4 delta of mask_thr; and the case's own premise (the cells, counts,
+    ranks, NaN, exact tie it exists for) holds — a case that stopped reaching its path fails here.  (The spacing conditions are asserted by solo_cases.tile_case.)"""
+    import torch
+    rec = solo_cases.get(name)
+    r64, r32, par = rec["r64"], rec["r32"], rec["par"]
+    assert torch.equal(r64["logits"], r32["logits"].double()) and not (r64["logits"] == 0).any(), "a logit is not exact in float32, or zero: the generator is wrong"
+    assert r64["n_pass"] == r32["n_pass"] and all(np.array_equal(a, b) for a, b in zip(r64["cand"], r32["cand"]))
+    assert r64["n_floor"] == r32["n_floor"] and r64["n_sorted"] == r32["n_sorted"] and np.array_equal(r64["sorted"][0], r32["sorted"][0])
+    assert np.array_equal(np.isnan(r64["updated"]), np.isnan(r32["updated"])) and np.array_equal(r64["updated"] >= par["update_thr"], r32["updated"] >= par["update_thr"])
+    assert r64["n"] == r32["n"] and np.array_equal(r64["survivors"], r32["survivors"]) and np.array_equal(r64["labels"], r32["labels"])
+    assert (np.abs(r32["scores"] - r64["scores"]) <= 1e-5 * r64["scores"]).all()          # a tenth of what the device is allowed against float64
+    band = np.abs(r64["values"] - par["mask_thr"]) < 4 * rec["delta"]
+    assert rec["delta"] < 1e-4 and band.reshape(r64["n"], -1).mean(1).max() <= 0.01, "more than 1 % of a plane's pixels lie within 4 delta of mask_thr"
+    assert np.array_equal(r64["planes"][~band], r32["planes"][~band])
+    rec["premise"](rec)
+
+
+def test_over_capacity_counts_on_the_reference_alone():
+    """the two over-capacity frames of the GPU module: one more candidate than the 4096 of `cap4096`, and every class of every cell of five 64 x 64 grids"""
+    import torch
+    inp, par = solo_cases.over_capacity_by_one()
+    assert solo_ref.head(inp["kernels"], inp["cates"], inp["feature"], dict(par, lean=True, nms_pre=1), torch.float32)["n_pass"] == 4097 == par["max_candidates"] + 1
+    inp, par, n_pass = solo_cases.every_cell_passes()
+    assert n_pass == 5 * 64 * 64 * 128 == 2621440 and all((c > np.float32(par["score_thr"])).all() for c in inp["cates"])
 
 
 def test_rect_equals_get_xywhs():
