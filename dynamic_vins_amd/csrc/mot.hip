@@ -4,6 +4,7 @@
 // reference evaluates them (include/dvins.h has the rule; the rules shared with the host are in mot_host.h).  Track table and galleries are resident; kernels, in stream order:
 //   mot_feat_kernel    a workgroup per gallery slot in use: (stored rows) x (detections) over feat_dim on v_mfma_f32_32x32x2_f32, a wave per 32 rows, and the minimum of
 //                      1 - g . f over the slot's VALID rows in the epilogue.  Rows at or past the ring's count are excluded by index: their A operand is never loaded.
+//                      The minimum carries a NaN as torch::min does (feature_metric.h:59-61): a NaN in ONE valid row makes the slot's distance a NaN, which is gated.
 //   mot_assoc_kernel   ONE workgroup: predict, remove_nan, both cost matrices and Munkres solves, miss / update with the filter's correct, births, the stable compaction of
 //                      the table, the ring writes and the answer.  Everything is decided in LDS and registers first; the table is written only when the frame fits
 //                      max_tracks, so a refused frame leaves it as it was.
@@ -33,6 +34,9 @@ struct MotDev {
 };
 
 __device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+
+// min that carries a NaN from either side (a plain `<` would skip one)
+__device__ __forceinline__ float nan_min(float c, float m) { return (c < m || c != c) ? c : m; }
 
 __global__ __launch_bounds__(256) void mot_feat_kernel(MotDev D) {
     __shared__ float smin[4][MD];
@@ -71,17 +75,17 @@ __global__ __launch_bounds__(256) void mot_feat_kernel(MotDev D) {
             const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
             if (row < cnt) {
                 const float c0 = 1.0f - acc0[r], c1 = 1.0f - acc1[r];
-                m0 = c0 < m0 ? c0 : m0; m1 = c1 < m1 ? c1 : m1;
+                m0 = nan_min(c0, m0); m1 = nan_min(c1, m1);
             }
         }
         const float o0 = __shfl_xor(m0, 32), o1 = __shfl_xor(m1, 32);
-        m0 = o0 < m0 ? o0 : m0; m1 = o1 < m1 ? o1 : m1;
+        m0 = nan_min(o0, m0); m1 = nan_min(o1, m1);
     }
     if (kh == 0) { smin[wv][li] = m0; smin[wv][32 + li] = m1; }
     __syncthreads();
     if (threadIdx.x < MD) {
         float m = smin[0][threadIdx.x];
-        for (int w = 1; w < 4; ++w) { const float o = smin[w][threadIdx.x]; m = o < m ? o : m; }
+        for (int w = 1; w < 4; ++w) { m = nan_min(smin[w][threadIdx.x], m); }
         D.featmin[(size_t)slot * MD + threadIdx.x] = m;
     }
 }

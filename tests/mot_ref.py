@@ -3,7 +3,11 @@ mot/kalman_tracker.cpp:20-96, mot/feature_bundle.h:40-50, mot/feature_metric.h:3
 dtype given (float32 as the reference, or float64); Munkres (mot/hungarian.cpp, restated step by step below) is always double.
 
 Kept as the reference computes it: AssociateDetectionsToTrackersIdx subtracts the assigned COLUMN INDICES from the detection ids (tracker_manager.cpp:62-68), which
-differ in stage 2 once stage 1 has matched something.  predict / correct are OpenCV 3.4's KalmanFilter from memory (include/dvins.h)."""
+differ in stage 2 once stage 1 has matched something.  predict / correct are OpenCV 3.4's KalmanFilter from memory (include/dvins.h).
+
+The library's declared rule (include/dvins.h) is applied in front of the Munkres call, which need not end on a NaN: a NaN appearance or IoU distance
+counts as gated in both stages.  torch::min carries a NaN (feature_metric.h:59-61), so one NaN row in a gallery makes that track's appearance distance a NaN for every
+detection.  MotRef(flip={...}) turns single comparisons from `>` into `>=` (`<` into `<=`): the mutants that tests/mot_hostile.py shows its cases to tell apart."""
 import copy
 
 import numpy as np
@@ -113,8 +117,14 @@ class Track:
 
 
 class MotRef:
-    def __init__(self, n_init=3, max_age=5, budget=100, feat_dim=512, max_tracks=128, dtype=np.float64):
+    FLIPS = ("iou1", "feat", "iou2", "invalid", "n_init", "max_age", "union")
+
+    def __init__(self, n_init=3, max_age=5, budget=100, feat_dim=512, max_tracks=128, dtype=np.float64, flip=()):
+        """flip: names out of FLIPS whose comparison is taken with equality on the other side (`a > b` becomes `a >= b`, the union's `un < eps` becomes `un <= eps`);
+        empty is the reference's behaviour"""
         self.n_init, self.max_age, self.budget, self.feat_dim, self.max_tracks, self.dt = n_init, max_age, budget, feat_dim, max_tracks, np.dtype(dtype).type
+        self.flip = frozenset(flip)
+        assert self.flip <= set(self.FLIPS), self.flip
         dt = self.dt
         self.A = np.eye(7, dtype=dt)
         self.A[0, 4] = self.A[1, 5] = self.A[2, 6] = 1
@@ -126,6 +136,11 @@ class MotRef:
     def reset(self):
         self.tracks, self.next_id = [], 1
         self.log = []          # per frame: dict of what happened (events, the Munkres problems, the gate distances)
+
+    def gt(self, name, a, b):
+        """a > b as the reference has it; a >= b when `name` is flipped"""
+        with np.errstate(invalid="ignore"):
+            return a >= b if name in self.flip else a > b
 
     # ---- KalmanTracker ----
     def rect(self, t):
@@ -150,9 +165,10 @@ class MotRef:
             w = h = dt(0)
         inter = w * h
         un = a[2] * a[3] + b[2] * b[3] - inter
-        if float(un) < DBL_EPSILON:
+        if float(un) < DBL_EPSILON or ("union" in self.flip and float(un) == DBL_EPSILON):
             return dt(1)
-        return dt(1) - inter / un
+        with np.errstate(all="ignore"):
+            return dt(1) - inter / un
 
     def _associate(self, cost, trks, dets, matched, info):
         """AssociateDetectionsToTrackersIdx: cost [len(trks), len(dets)] in the working dtype; trks / dets are updated in place as the reference leaves them"""
@@ -163,7 +179,7 @@ class MotRef:
         for i in range(len(assignment)):
             if assignment[i] == -1:
                 continue
-            if dist[i, assignment[i]] > INVALID_DIST / 10:
+            if self.gt("invalid", dist[i, assignment[i]], INVALID_DIST / 10):
                 assignment[i] = -1
             else:
                 matched.append((trks[i], dets[assignment[i]]))
@@ -179,7 +195,7 @@ class MotRef:
         rects = np.asarray(rects, dt).reshape(-1, 4)
         feats = np.asarray(feats, dt).reshape(len(rects), self.feat_dim)
         n = len(rects)
-        info = {"n": n, "events": set(), "problems": [], "gates": []}
+        info = {"n": n, "events": set(), "problems": [], "gates": [], "stages": []}
         self.log.append(info)
         if n == 0:
             return np.zeros(0, np.int64)
@@ -198,6 +214,7 @@ class MotRef:
         data[:] = keep
         trects = [self.rect(t) for t in data]
         iou = np.array([[self.iou_dist(tr, dr) for dr in rects] for tr in trects], dt).reshape(len(data), n)
+        info["iou"], info["trects"] = iou.copy(), np.array(trects, dt).reshape(len(data), 4)
         # stage 1
         trks = [i for i, t in enumerate(data) if t.state == CONFIRMED]
         dets = list(range(n))
@@ -206,9 +223,13 @@ class MotRef:
         for k, i in enumerate(trks):
             t = data[i]
             g = t.store if t.full else t.store[: t.next]
-            feat = (dt(1) - g @ feats.T).min(axis=0)
+            with np.errstate(all="ignore"):
+                feat = (dt(1) - g @ feats.T).min(axis=0)
             info["gates"] += [abs(float(v) - 0.2) for v in feat] + [abs(float(v) - 0.8) for v in iou[i]]
-            cost[k] = np.where((iou[i] > np.float32(0.8)) | (feat > np.float32(0.2)), dt(INVALID_DIST), feat)
+            gated = self.gt("iou1", iou[i], np.float32(0.8)) | self.gt("feat", feat, np.float32(0.2)) | np.isnan(iou[i]) | np.isnan(feat)      # NaN: the declared rule
+            cost[k] = np.where(gated, dt(INVALID_DIST), feat)
+            info.setdefault("feat", {})[i] = feat.copy()
+        info["stages"].append(dict(rows=list(trks), cols=list(dets), cost=cost.copy()))
         self._associate(cost, trks, dets, matched, info)
         n1 = len(matched)
         for (ti, dj) in matched:
@@ -220,8 +241,10 @@ class MotRef:
         for k, i in enumerate(trks):
             for c, j in enumerate(dets):
                 info["gates"].append(abs(float(iou[i, j]) - 0.7))
-                cost[k, c] = dt(INVALID_DIST) if iou[i, j] > np.float32(0.7) else iou[i, j]
+                cost[k, c] = dt(INVALID_DIST) if self.gt("iou2", iou[i, j], np.float32(0.7)) or np.isnan(iou[i, j]) else iou[i, j]
+        info["stages"].append(dict(rows=list(trks), cols=list(dets), cost=cost.copy()))
         self._associate(cost, trks, dets, matched, info)
+        info["born"] = list(dets)
         for (ti, dj) in matched[n1:]:
             if data[ti].state == CONFIRMED:
                 info["events"].add("stage2_confirmed")
@@ -231,7 +254,7 @@ class MotRef:
             if t.state == TENTATIVE:
                 t.state = DELETED
                 info["events"].add("tentative_death")
-            elif t.tsu > self.max_age:
+            elif self.gt("max_age", t.tsu, self.max_age):
                 t.state = DELETED
                 info["events"].add("death_by_age")
         # update
@@ -242,7 +265,7 @@ class MotRef:
                 info["events"].add("survived_gap")
             t.tsu = 0
             t.hits += 1
-            if t.state == TENTATIVE and t.hits > self.n_init:
+            if t.state == TENTATIVE and self.gt("n_init", t.hits, self.n_init):
                 t.state, t.id = CONFIRMED, next_id
                 next_id += 1
                 info["events"].add("confirmation")
