@@ -140,6 +140,11 @@ SIGNATURES = {
     "dv_line_track_enqueue": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "dv_line_track_collect": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "dv_line_match": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "dv_lbd_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "dv_lbd_num_pixels": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "dv_lbd_describe_enqueue": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float]),
+    "dv_lbd_describe_collect": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
+    "dv_lbd_debug": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dv_reid_check": (C.c_int, [C.c_size_t, C.c_int, C.c_int]),
     "dv_reid_load": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
     "dv_reid_extract_enqueue": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),

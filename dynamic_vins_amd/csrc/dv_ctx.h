@@ -183,6 +183,7 @@ void dv_solo_head_release(dv_ctx* ctx);     // solo_head.hip: the head's buffers
 void dv_mot_release(dv_ctx* ctx);           // mot.hip: the tracker's table and galleries (dv_destroy)
 void dv_reid_release(dv_ctx* ctx);          // reid.hip: the extractor's weights and activations (dv_destroy)
 void dv_line_track_release(dv_ctx* ctx);    // line_track.hip: the resident previous frame and the staging buffers (dv_destroy)
+void dv_lbd_release(dv_ctx* ctx);           // lbd.hip: both cams' gradient images, descriptors and staging buffers (dv_destroy)
 
 // One window sharded by landmark over several GPUs (be_shard.hip): the transport of the exchange vectors
 struct DvDist {
@@ -239,6 +240,8 @@ struct dv_ctx {
     struct ReidNet* reid = nullptr;
     // dv_line_track_*: the line tracker (key lines + LBD descriptors -> line ids and rows; line_track.hip, released by dv_line_track_release)
     struct LineTracker* line_track = nullptr;
+    // dv_lbd_*: the LBD descriptor in front of it (gray image + key lines -> selected lines and 32-byte rows on the device; lbd.hip, released by dv_lbd_release)
+    struct LbdStage* lbd = nullptr;
     DevBuf undist_buf[2]; bool undist[2] = { false, false }; int undist_w = 0, undist_h = 0;      // cfg::is_undistort_input: fixed-point maps per camera (map1 | map2)
     bool cam_switched = false; dv_cam cam_orig[2]{};      // dv_undistort_setup: cfg.cam0 / cam1 hold (newK, 0); the cameras the ctx was created with, restored when the maps are removed
     DevBuf out_buf; dv_feat* out_dev = nullptr; int* nout_dev = nullptr;

@@ -331,6 +331,7 @@ void dv_destroy(dv_ctx* ctx) {
     dv_mot_release(ctx);
     dv_reid_release(ctx);
     dv_line_track_release(ctx);
+    dv_lbd_release(ctx);
     if (ctx->done) (void)hipEventDestroy(ctx->done);
     if (ctx->ev_pyr) (void)hipEventDestroy(ctx->ev_pyr);
     if (ctx->ev_bg_select) (void)hipEventDestroy(ctx->ev_bg_select);

@@ -139,6 +139,38 @@ def line_track_check(left_lines, left_desc, n_left, right_lines=None, right_desc
         raise DvinsError(lib.dv_last_error(None).decode())
 
 
+def _host_lines(lines, num_pixels=None):
+    """host key lines ([n, 6] float32 or KEYLINE_DTYPE records) and optional num_pixels ([n] int32), contiguous -> (lines, num_pixels, n)"""
+    lines = np.asarray(lines)
+    lines = np.ascontiguousarray(lines.view(np.float32) if lines.dtype == KEYLINE_DTYPE else lines, np.float32).reshape(-1, 6)
+    if num_pixels is not None:
+        num_pixels = np.ascontiguousarray(num_pixels, np.int32).reshape(-1)
+        if len(num_pixels) != len(lines):
+            raise ValueError("one num_pixels per key line")
+    return lines, num_pixels, len(lines)
+
+
+def lbd_check(w, h, stride, lines, num_pixels=None, n=None, mem=DV_MEM_HOST, mask=None, mask_stride=0):
+    """the refusals of Context.lbd_describe_enqueue, without a device (host arrays, or pointers as int with n): raises DvinsError with the reason"""
+    lib = _abi.load()
+    if n is None:
+        lines, num_pixels, n = _host_lines(lines, num_pixels)
+    if isinstance(mask, np.ndarray) and not mask_stride:
+        mask_stride = mask.strides[0]
+    if lib.dv_lbd_check(int(w), int(h), int(stride), _ptr(lines), _ptr(num_pixels), int(n), int(mem), _ptr(mask), int(mask_stride)) != 0:
+        raise DvinsError(lib.dv_last_error(None).decode())
+
+
+def lbd_num_pixels(lines):
+    """KeyLine::numOfPixels by the library's rule, max(|rint(ex) - rint(sx)|, |rint(ey) - rint(sy)|) + 1, for host key lines -> [n] int32.  Host code: needs no GPU."""
+    lib = _abi.load()
+    lines, _, n = _host_lines(lines)
+    out = np.zeros(max(n, 1), np.int32)
+    if lib.dv_lbd_num_pixels(lines.ctypes.data if n else None, n, out.ctypes.data) != 0:
+        raise DvinsError(lib.dv_last_error(None).decode())
+    return out[:n].copy()
+
+
 def reid_check(n_floats, in_w=64, in_h=128):
     """the refusals of Context.reid_load, without a device: raises DvinsError with the reason"""
     lib = _abi.load()
@@ -497,6 +529,67 @@ class Context:
         idx, dist = np.full(max(len(q), 1), -1, np.int32), np.zeros(max(len(q), 1), np.int32)
         self._check(self.lib.dv_line_match(self.h, q.ctypes.data if len(q) else None, len(q), t.ctypes.data if len(t) else None, len(t), idx.ctypes.data, dist.ctypes.data))
         return idx[: len(q)].copy(), dist[: len(q)].copy()
+
+    # ---- the LBD descriptor (LineDetector::Detect behind LSD, line_detector/line_detector.cpp:78-97): gray image + key lines -> selected lines and 32-byte rows on the device ----
+    def lbd_describe_enqueue(self, cam, image, lines, num_pixels=None, mask=None, min_length=60.0, n=None, mem=DV_MEM_HOST, lines_mem=DV_MEM_HOST, size=None, stride=None,
+                             mask_stride=None):
+        """cam: 0 / 1, one buffer set each.  image / mask: [h, w] uint8 arrays (any row stride), or raw pointers (int) with mem, size = (w, h), stride and mask_stride.
+        lines ([n, 6] float32) / num_pixels ([n] int32 or None: the library's rule): host arrays, or raw pointers (int) with lines_mem and n."""
+        if isinstance(image, np.ndarray):
+            assert image.ndim == 2 and image.dtype == np.uint8 and image.strides[1] == 1
+            (h, w), stride = image.shape, image.strides[0]
+        else:
+            (w, h) = size
+        if isinstance(mask, np.ndarray):
+            assert mask.shape == (h, w) and mask.dtype == np.uint8 and mask.strides[1] == 1
+            mask_stride = mask.strides[0]
+        if lines_mem == DV_MEM_HOST and n is None:
+            lines, num_pixels, n = _host_lines(lines, num_pixels)
+        elif n is None:
+            raise ValueError("lbd_describe_enqueue: n is required with device or pinned lines")
+        self._lbd_keep = getattr(self, "_lbd_keep", {})
+        self._lbd_keep[cam] = (image, mask, lines, num_pixels)
+        self._check(self.lib.dv_lbd_describe_enqueue(self.h, int(cam), _ptr(image), int(stride), int(w), int(h), int(mem), _ptr(lines) if n else None,
+                                                     _ptr(num_pixels) if n else None, int(n), int(lines_mem), _ptr(mask), int(mask_stride or 0), float(min_length)))
+
+    def lbd_describe_collect(self, cam, host=True):
+        """-> dict: n, src (each survivor's index in the enqueued array), dev_lines / dev_desc (device pointers, valid until the next enqueue on cam: what
+        line_track_enqueue(..., mem=DV_MEM_DEVICE) takes) and, with host=True, lines [n, 6] float32 and desc [n, 32] uint8"""
+        nk, src = C.c_int(0), np.zeros(DV_LINE_MAX, np.int32)
+        dl, dd = C.c_void_p(0), C.c_void_p(0)
+        hl, hd = (np.zeros((DV_LINE_MAX, 6), np.float32), np.zeros((DV_LINE_MAX, DV_LINE_DESC_BYTES), np.uint8)) if host else (None, None)
+        if getattr(self, "_lbd_keep", None):
+            self._lbd_keep.pop(cam, None)
+        self._check(self.lib.dv_lbd_describe_collect(self.h, int(cam), C.byref(nk), src.ctypes.data, C.byref(dl), C.byref(dd), _ptr(hl), _ptr(hd)))
+        out = {"n": nk.value, "src": src[: nk.value].copy(), "dev_lines": dl.value or 0, "dev_desc": dd.value or 0}
+        if host:
+            out["lines"], out["desc"] = hl[: nk.value].copy(), hd[: nk.value].copy()
+        return out
+
+    def lbd_describe(self, image, lines, num_pixels=None, mask=None, cam=0, host=True, **kw):
+        """lbd_describe_enqueue + lbd_describe_collect"""
+        self.lbd_describe_enqueue(cam, image, lines, num_pixels, mask, **kw)
+        return self.lbd_describe_collect(cam, host=host)
+
+    def lbd_debug(self, cam, w, h, n):
+        """the last frame of cam, for tests: (dx [h, w] int16, dy [h, w] int16, the 72 floats of every enqueued line [n, 72] float32, before selection)"""
+        dx, dy, fd = np.zeros((h, w), np.int16), np.zeros((h, w), np.int16), np.zeros((max(n, 1), 72), np.float32)
+        self._check(self.lib.dv_lbd_debug(self.h, int(cam), dx.ctypes.data, dy.ctypes.data, fd.ctypes.data))
+        return dx, dy, fd[:n].copy()
+
+    def lbd_track(self, left, left_lines, right=None, right_lines=None, left_num_pixels=None, right_num_pixels=None, mask=None, min_length=60.0):
+        """Detect's second half and the tracker back to back, with no descriptor on the host: both images are described (cam 0 / 1 in flight together) and the device
+        buffers go to line_track_enqueue(..., mem=DV_MEM_DEVICE).  -> line_track_collect's dict plus left_kept / right_kept (the describe stage's src)"""
+        self.lbd_describe_enqueue(0, left, left_lines, left_num_pixels, mask, min_length)
+        if right is not None:
+            self.lbd_describe_enqueue(1, right, right_lines, right_num_pixels, None, min_length)
+        a = self.lbd_describe_collect(0, host=False)
+        b = self.lbd_describe_collect(1, host=False) if right is not None else None
+        self.line_track_enqueue(a["dev_lines"], a["dev_desc"], b["dev_lines"] if b else None, b["dev_desc"] if b else None, n_left=a["n"], n_right=b["n"] if b else 0,
+                                mem=DV_MEM_DEVICE)
+        out = self.line_track_collect()
+        out["left_kept"], out["right_kept"] = a["src"], (b["src"] if b else np.zeros(0, np.int32))
+        return out
 
     # ---- the ReID extractor (Extractor::extract, mot/extractor.cpp:31-52; ReIdNetImpl, mot/reid_net.cpp): colour image + rectangles -> [n, 512] embeddings on the device ----
     def reid_load(self, weights, in_w=64, in_h=128):

@@ -397,9 +397,14 @@ struct FrameLines {
     std::vector<unsigned int> line_ids;
     std::map<unsigned int, int> track_cnt;
     std::vector<int> src;
+    // LineDetector::Describe sets these: the frame's key lines and LBD rows lie in the library's device buffers of one cam slot (keylsd is their host mirror, src each
+    // line's index in the LSD output, lbd_descr stays empty unless a host copy was asked for) until that slot describes again.  The tracker reads them in place and
+    // clears the three fields: behind it keylsd / src are in the tracker's order, src still an index into the LSD output.
+    bool device = false; const dv_key_line* dev_lines = nullptr; const uint8_t* dev_desc = nullptr;
 };
 
-// LineDetector's tracking half (line_detector/line_detector.cpp:101-297) on the device: dv_line_track_enqueue / _collect.  LSD and the LBD descriptor stay with the caller.
+// LineDetector (line_detector/line_detector.cpp:60-297) on the device.  Describe() is the second half of Detect (:78-97): the key lines LSD left -> the selected lines
+// and their LBD rows, in device buffers (dv_lbd_describe_enqueue / _collect); the tracking half is dv_line_track_enqueue / _collect.  LSD itself stays with the caller.
 // The previous left frame lives on the device, so TrackLeftLine's `prev` only says whether there is one: nullptr resets the tracker (the reference's first frame),
 // anything else must be the FrameLines the last frame was tracked into.  The device tracks both images in ONE launch: with stereo = true TrackLeftLine only records the
 // left detections and TrackRightLine runs the frame and fills both; with stereo = false TrackLeftLine runs it.  So between the two calls `curr` is NOT yet what the
@@ -416,18 +421,55 @@ public:
     LineDetector& operator=(const LineDetector&) = delete;
     // the refusals of a frame without a device: throws with the library's reason
     static void Check(const FrameLines& left, const FrameLines* right = nullptr) {
-        if (left.keylsd.size() != left.lbd_descr.size() || (right && right->keylsd.size() != right->lbd_descr.size())) throw std::runtime_error("LineDetector: one descriptor row per key line");
+        if (right && right->device != left.device) throw std::runtime_error("LineDetector: both images' lines must be described on the device, or neither");
+        if (!left.device && (left.keylsd.size() != left.lbd_descr.size() || (right && right->keylsd.size() != right->lbd_descr.size()))) throw std::runtime_error("LineDetector: one descriptor row per key line");
         if (left.keylsd.size() > (size_t)INT32_MAX || (right && right->keylsd.size() > (size_t)INT32_MAX)) throw std::runtime_error("LineDetector: too many lines");
-        if (dv_line_track_check(left.keylsd.data(), desc(left), (int)left.keylsd.size(), right ? right->keylsd.data() : nullptr, right ? desc(*right) : nullptr,
-                                right ? (int)right->keylsd.size() : 0, DV_MEM_HOST) != 0)
+        if (dv_line_track_check(lines(left), desc(left), (int)left.keylsd.size(), right ? lines(*right) : nullptr, right ? desc(*right) : nullptr,
+                                right ? (int)right->keylsd.size() : 0, left.device ? DV_MEM_DEVICE : DV_MEM_HOST) != 0)
             throw std::runtime_error(std::string("LineDetector: ") + dv_last_error(nullptr));
+    }
+    // The second half of Detect (:78-97) on the device, in two phases so that both images of a stereo frame are in flight together (cam 0 / 1: one buffer set each).
+    // image: gray, host or device; keylines: LSD's octave-0 lines; num_pixels: KeyLine::numOfPixels per line, or nullptr for the library's rule; mask: w x h bytes of the
+    // image's memory kind, or nullptr.  The frame that comes back is on the device (FrameLines::device): hand it to TrackLeftLine / TrackRightLine / Track / enqueue
+    // BEFORE the same cam describes again.  host_copy = true also fills lbd_descr.
+    void DescribeEnqueue(int cam, const ImageView& image, const std::vector<dv_key_line>& keylines, const std::vector<int32_t>* num_pixels = nullptr, const ImageView* mask = nullptr,
+                         float min_length = 60.0f) {
+        if (cam != 0 && cam != 1) throw std::runtime_error("LineDetector::Describe: cam must be 0 or 1");
+        if (image.empty() || image.bgr) throw std::runtime_error("LineDetector::Describe: a gray image is required");
+        if (keylines.size() > (size_t)INT32_MAX || (num_pixels && num_pixels->size() != keylines.size())) throw std::runtime_error("LineDetector::Describe: one num_pixels per key line");
+        const bool has_mask = mask && !mask->empty();
+        if (has_mask && (mask->device != image.device || mask->width != image.width || mask->height != image.height)) throw std::runtime_error("LineDetector::Describe: the mask must have the image's size and memory kind");
+        detail::check(ctx_, dv_lbd_describe_enqueue(ctx_, cam, image.data, image.stride, image.width, image.height, image.device ? DV_MEM_DEVICE : DV_MEM_HOST,
+                                                    keylines.empty() ? nullptr : keylines.data(), num_pixels && !keylines.empty() ? num_pixels->data() : nullptr, (int)keylines.size(),
+                                                    DV_MEM_HOST, has_mask ? mask->data : nullptr, has_mask ? mask->stride : 0, min_length), "LineDetector::Describe");
+        desc_keys_[cam] = keylines; desc_pending_[cam] = true;
+    }
+    FrameLines::Ptr DescribeCollect(int cam, bool host_copy = false) {
+        if ((cam != 0 && cam != 1) || !desc_pending_[cam]) throw std::runtime_error("LineDetector::DescribeCollect: nothing enqueued on this cam");
+        desc_pending_[cam] = false;
+        auto fl = std::make_shared<FrameLines>();
+        std::vector<int32_t> src(DV_LINE_MAX);
+        if (host_copy) fl->lbd_descr.resize(DV_LINE_MAX);
+        int n = 0;
+        detail::check(ctx_, dv_lbd_describe_collect(ctx_, cam, &n, src.data(), &fl->dev_lines, &fl->dev_desc, nullptr, host_copy ? fl->lbd_descr[0].data() : nullptr), "LineDetector::Describe");
+        fl->device = true;
+        fl->keylsd.resize((size_t)n); fl->src.resize((size_t)n);
+        if (host_copy) fl->lbd_descr.resize((size_t)n);
+        for (int i = 0; i < n; ++i) { fl->keylsd[(size_t)i] = desc_keys_[cam].at((size_t)src[(size_t)i]); fl->src[(size_t)i] = src[(size_t)i]; }
+        return fl;
+    }
+    FrameLines::Ptr Describe(const ImageView& image, const std::vector<dv_key_line>& keylines, const std::vector<int32_t>* num_pixels = nullptr, const ImageView* mask = nullptr,
+                             int cam = 0, float min_length = 60.0f, bool host_copy = false) {
+        DescribeEnqueue(cam, image, keylines, num_pixels, mask, min_length);
+        return DescribeCollect(cam, host_copy);
     }
     void reset() { detail::check(ctx_, dv_line_track_reset(ctx_), "LineDetector::reset"); last_.reset(); left_.reset(); }
     void TrackLeftLine(const FrameLines::Ptr& prev, const FrameLines::Ptr& curr) {
         if (!curr) throw std::runtime_error("LineDetector::TrackLeftLine: null frame");
         begin(prev);
         left_ = curr;
-        curr->line_ids.clear(); curr->track_cnt.clear(); curr->src.clear();      // not tracked yet (stereo: until TrackRightLine)
+        curr->line_ids.clear(); curr->track_cnt.clear();                         // not tracked yet (stereo: until TrackRightLine)
+        if (!curr->device) curr->src.clear();                                    // (a described frame's src is Describe's: the tracker's is composed with it)
         if (!stereo_) { enqueue(curr, nullptr); collect(); }
     }
     void TrackRightLine(const FrameLines::Ptr& left, const FrameLines::Ptr& right) {
@@ -444,8 +486,8 @@ public:
     // on the ctx's stream; the FrameLines stay untouched until collect()
     void enqueue(const FrameLines::Ptr& left, const FrameLines::Ptr& right) {
         Check(*left, right.get());
-        detail::check(ctx_, dv_line_track_enqueue(ctx_, left->keylsd.data(), desc(*left), (int)left->keylsd.size(), right ? right->keylsd.data() : nullptr,
-                                                  right ? desc(*right) : nullptr, right ? (int)right->keylsd.size() : 0, DV_MEM_HOST), "LineDetector");
+        detail::check(ctx_, dv_line_track_enqueue(ctx_, lines(*left), desc(*left), (int)left->keylsd.size(), right ? lines(*right) : nullptr,
+                                                  right ? desc(*right) : nullptr, right ? (int)right->keylsd.size() : 0, left->device ? DV_MEM_DEVICE : DV_MEM_HOST), "LineDetector");
         pend_left_ = left; pend_right_ = right;
     }
     const std::vector<dv_line_row>& collect() {
@@ -470,19 +512,26 @@ private:
         if (!prev) reset();
         else if (prev != last_) throw std::runtime_error("LineDetector: the previous frame is resident on the device: pass the FrameLines of the last frame, or nullptr to start over");
     }
-    static const uint8_t* desc(const FrameLines& f) { return f.lbd_descr.empty() ? nullptr : f.lbd_descr[0].data(); }
+    static const uint8_t* desc(const FrameLines& f) { return f.keylsd.empty() ? nullptr : f.device ? f.dev_desc : f.lbd_descr.empty() ? nullptr : f.lbd_descr[0].data(); }
+    static const dv_key_line* lines(const FrameLines& f) { return f.keylsd.empty() ? nullptr : f.device ? f.dev_lines : f.keylsd.data(); }
     // curr_keylsd = vecLine_tracked, curr_line_ids = lineID_tracked, curr_lbd = descr_tracked (line_detector.cpp:221-223,294-296); a count of 0 is "no entry"
     static void apply(FrameLines& f, const uint32_t* ids, const int32_t* src, const int32_t* cnt, int n) {
-        std::vector<dv_key_line> k((size_t)n); std::vector<std::array<uint8_t, DV_LINE_DESC_BYTES>> d((size_t)n);
-        f.line_ids.assign(ids, ids + n); f.src.assign(src, src + n); f.track_cnt.clear();
+        const bool rows = !f.lbd_descr.empty() || !f.device;      // a described frame has host rows only if a copy was asked for
+        std::vector<dv_key_line> k((size_t)n); std::vector<std::array<uint8_t, DV_LINE_DESC_BYTES>> d(rows ? (size_t)n : 0);
+        std::vector<int> s(src, src + n);
+        if (f.device) for (int i = 0; i < n; ++i) s[(size_t)i] = f.src.at((size_t)src[i]);      // Describe's src under the tracker's: still an index into the LSD output
+        f.line_ids.assign(ids, ids + n); f.track_cnt.clear();
         for (int i = 0; i < n; ++i) {
-            k[i] = f.keylsd.at((size_t)src[i]); d[i] = f.lbd_descr.at((size_t)src[i]);
+            k[i] = f.keylsd.at((size_t)src[i]);
+            if (rows) d[i] = f.lbd_descr.at((size_t)src[i]);
             if (cnt && cnt[i] > 0) f.track_cnt.insert({ ids[i], cnt[i] });
         }
-        f.keylsd.swap(k); f.lbd_descr.swap(d);
+        f.keylsd.swap(k); f.lbd_descr.swap(d); f.src.swap(s);
+        f.device = false; f.dev_lines = nullptr; f.dev_desc = nullptr;      // the device buffers hold the described order, and only until the cam's next Describe
     }
     dv_ctx* ctx_; bool stereo_;
     FrameLines::Ptr last_, left_, pend_left_, pend_right_;
+    std::vector<dv_key_line> desc_keys_[2]; bool desc_pending_[2] = { false, false };
     std::vector<dv_line_row> rows_;
 };
 
@@ -550,6 +599,25 @@ public:
             fb.lines.insert({ r.id, { { 0, Line{ r.id, r.left[0], r.left[1], r.left[2], r.left[3] } } } });
             if (r.has_right) fb.lines[r.id].push_back({ 1, Line{ r.id, r.right[0], r.right[1], r.right[2], r.right[3] } });
         }
+        return fb;
+    }
+    // the same from UNDESCRIBED LSD output (octave-0 key lines of both images; num_pixels as in LineDetector::Describe): Detect's second half runs on the device for both
+    // images together (no mask, as FeatureTracker::TrackImageLine hands Detect none, background_tracker.cpp:210), the tracker reads the rows where they lie, and no
+    // descriptor visits the host.  Returns the tracked FrameLines through left_out / right_out when asked
+    FeatureBackground TrackImageLine(SemanticImage& img, const std::vector<dv_key_line>& left_keylines, const std::vector<dv_key_line>& right_keylines, bool first = false,
+                                     const std::vector<int32_t>* left_num_pixels = nullptr, const std::vector<int32_t>* right_num_pixels = nullptr, float min_length = 60.0f,
+                                     FrameLines::Ptr* left_out = nullptr, FrameLines::Ptr* right_out = nullptr) {
+        check_image(img);
+        if (!line_detector_) line_detector_ = std::make_shared<LineDetector>(ctx_, cfg_.stereo != 0);
+        line_detector_->DescribeEnqueue(0, img.gray0, left_keylines, left_num_pixels, nullptr, min_length);
+        FrameLines::Ptr left, right;
+        try { if (cfg_.stereo) line_detector_->DescribeEnqueue(1, img.gray1, right_keylines, right_num_pixels, nullptr, min_length); }
+        catch (...) { try { line_detector_->DescribeCollect(0); } catch (...) {} throw; }
+        left = line_detector_->DescribeCollect(0);
+        if (cfg_.stereo) right = line_detector_->DescribeCollect(1);
+        FeatureBackground fb = TrackImageLine(img, left, right, first);
+        if (left_out) *left_out = left;
+        if (right_out) *right_out = right;
         return fb;
     }
     // two-phase form: lets the caller overlap the front end of frame k+1 with the back end of frame k

@@ -825,6 +825,39 @@ int dv_line_track_collect(dv_ctx* ctx, dv_line_row* rows, int cap, int* n_rows, 
                           uint32_t* right_ids, int32_t* right_src, int* n_right_out);
 int dv_line_match(dv_ctx* ctx, const uint8_t* query_desc, int nq, const uint8_t* train_desc, int nt, int32_t* train_idx, int32_t* distance);
 
+/* The LBD DESCRIPTOR on the device: a gray image and the key lines LSD left -> the selected key lines and their 32-byte rows, in device buffers of the layout
+ * dv_line_track_enqueue(..., DV_MEM_DEVICE) takes: the second half of LineDetector::Detect (line_detector/line_detector.cpp:78-97).  LSD itself stays upstream.  Reference:
+ * BinaryDescriptor::compute -> computeImpl / computeSobel / computeLBD (thirdparty/line_descriptor/src/binary_descriptor_custom.cpp:350-398,539-687,1026-1372).
+ *   lines        every line is at octave 0 (Detect keeps no other; a caller drops the rest before the call), where sPointInOctave = startPoint: a dv_key_line plus
+ *                KeyLine::numOfPixels.  num_pixels = NULL: max(|rint(ex) - rint(sx)|, |rint(ey) - rint(sy)|) + 1, cv::LineIterator's count for a segment inside the image.
+ *   gradients    cv::GaussianBlur(img, Size(5, 5), 1) then cv::Sobel(CV_16SC1, 1, 0, 3) and (0, 1, 3), BORDER_REFLECT_101 both.  The blur is separable 8-bit fixed point,
+ *                weights 14 62 104 62 14 / 256, exact sums, one rounding at the end — a DECLARED CHOICE, not pinned against OpenCV.  The Sobel half is exact.
+ *   descriptor   computeLBD's float32 evaluation order, operation by operation, as an x86-64 build without FMA runs it: row starts and samples stepped by repeated
+ *                addition, (short) round() half away from zero, clamped; row sums in pixel order; band sums in row order; the tail (:1246-1340) as written; sqrt and
+ *                1 / sqrt correctly rounded.  dL = ((float)cos((double)angle), (float)sin((double)angle)), computed on the host per line — a DECLARED CHOICE of the overload.
+ *                NaN travels: a flat image gives 32 zero bytes.  Bit i of byte k is f1[i] > f2[i] over combinations[k].
+ *   selection    line i is kept iff length >= min_length (the reference: 60) and, with a mask (w x h bytes, the image's memory kind), the mask is non-zero at both end
+ *                points rounded like cv::Point(Point2f) (ties to even).  DEVIATION, declared: an end point that rounds outside the mask drops the line (the reference
+ *                reads outside the matrix).  Survivors keep the input order.
+ * dv_lbd_check: the refusals of _enqueue without a device: more than DV_LINE_MAX lines, null or misaligned pointers, unknown memory kind, stride < w, w or h above 32767
+ * (the descriptor's 16-bit coordinates), and — for lines the host can read — a non-finite coordinate or angle, num_pixels < 1 or > w + h.  Lines in device
+ * memory get the value checks at the enqueue.  dv_lbd_num_pixels: the library's rule for n host lines.
+ * _enqueue: on the ctx's stream.  cam = 0 / 1 selects one of two buffer sets, so both images of a stereo frame are in flight together; one frame per cam may be in
+ * flight.  image / mask: DV_MEM_HOST (staged), DV_MEM_DEVICE or DV_MEM_PINNED (read in place until the collect).  lines / num_pixels: any kind, valid until the call
+ * returns.  The directions are host work, so lines in DV_MEM_DEVICE are FETCHED first: that enqueue BLOCKS until the ctx's stream is idle — the other cam's frame in flight
+ * and whatever else is queued on the stream included — before it queues its own work; host and pinned lines do not block.  The mask has no memory kind of its own: it
+ * is read as the image's kind (a device image with a host mask takes a copy by the caller).  n = 0 is an ordinary empty frame.
+ * _collect: *n_kept and src[n_kept] (each survivor's index in the enqueued array; DV_LINE_MAX entries or NULL); *dev_lines / *dev_desc = the device buffers, valid
+ * until the next enqueue on that cam; host_lines / host_desc (DV_LINE_MAX entries, or NULL) ask for host copies.  Without them the frame's only device -> host
+ * traffic is the count and src.
+ * dv_lbd_debug: for tests — the gradient images (w x h int16 each) and the 72 floats of every ENQUEUED line, before selection, of the last frame of that cam. */
+int dv_lbd_check(int w, int h, int stride, const dv_key_line* lines, const int32_t* num_pixels, int n, int lines_mem, const uint8_t* mask, int mask_stride);
+int dv_lbd_num_pixels(const dv_key_line* lines, int n, int32_t* out);
+int dv_lbd_describe_enqueue(dv_ctx* ctx, int cam, const uint8_t* image, int stride, int w, int h, int image_mem, const dv_key_line* lines, const int32_t* num_pixels, int n,
+                            int lines_mem, const uint8_t* mask, int mask_stride, float min_length);
+int dv_lbd_describe_collect(dv_ctx* ctx, int cam, int* n_kept, int32_t* src, const dv_key_line** dev_lines, const uint8_t** dev_desc, dv_key_line* host_lines, uint8_t* host_desc);
+int dv_lbd_debug(dv_ctx* ctx, int cam, int16_t* dx_out, int16_t* dy_out, float* float_desc_out);
+
 /* ---- the members of Estimator the callbacks and publishers use besides ProcessMeasurements (estimator/estimator.h:55-164) ---- */
 /* Estimator::ChangeSensorType (estimator.cpp:697-726; the /vins_imu_switch, /vins_cam_switch callbacks): switching the IMU on restarts the estimator
  * (ClearState + SetParameter), switching it off drops the prior.  use_stereo = 0 is refused (monocular initialisation is out of scope). */
