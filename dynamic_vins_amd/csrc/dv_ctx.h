@@ -180,6 +180,7 @@ int dv_inst_wait_before_next_frame(dv_ctx* ctx, hipStream_t s, bool consume = tr
 int dv_stack_resolve(dv_ctx* ctx, const dv_mask_stack& st, struct DevBuf& own_buf, hipStream_t s, DvStackSrc* out);
 void dv_stack_frame_done(dv_ctx* ctx);      // dv_track_stereo_collect: the shared staging ends with the frame
 void dv_solo_head_release(dv_ctx* ctx);     // solo_head.hip: the head's buffers (dv_destroy)
+void dv_solo_input_release(dv_ctx* ctx);    // solo_input.hip: the input tensors and the staged frame (dv_destroy)
 void dv_mot_release(dv_ctx* ctx);           // mot.hip: the tracker's table and galleries (dv_destroy)
 void dv_reid_release(dv_ctx* ctx);          // reid.hip: the extractor's weights and activations (dv_destroy)
 void dv_line_track_release(dv_ctx* ctx);    // line_track.hip: the resident previous frame and the staging buffers (dv_destroy)
@@ -234,6 +235,8 @@ struct dv_ctx {
     struct InstStackFrame* istack = nullptr;      // (defined in dvins_api.hip, released by dv_destroy)
     // dv_solo_head_enqueue / _collect: the detector's head in front of that stage (network outputs -> mask stack; solo_head.hip, released by dv_solo_head_release)
     struct SoloHeadFrame* solo = nullptr;
+    // dv_solo_input_enqueue / _collect: the detector's input in front of the network (colour frame -> [3, model_h, model_w]; solo_input.hip, released by dv_solo_input_release)
+    struct SoloInputFrame* solo_in = nullptr;
     // dv_mot_*: the multi-object tracker behind that stage (detections + embeddings -> track ids; mot.hip, released by dv_mot_release)
     struct MotTracker* mot = nullptr;
     // dv_reid_*: the ReID extractor in front of it (colour image + rectangles -> embeddings; reid.hip, released by dv_reid_release)

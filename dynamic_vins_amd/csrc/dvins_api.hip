@@ -328,6 +328,7 @@ void dv_destroy(dv_ctx* ctx) {
     dv_viode_frame_release(ctx);
     dv_inst_stack_frame_release(ctx);
     dv_solo_head_release(ctx);
+    dv_solo_input_release(ctx);
     dv_mot_release(ctx);
     dv_reid_release(ctx);
     dv_line_track_release(ctx);

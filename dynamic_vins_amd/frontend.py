@@ -89,6 +89,43 @@ def solo_params(score_thr=0.1, mask_thr=0.5, update_thr=0.05, nms_pre=500, max_p
     return p
 
 
+class dv_solo_input_params(C.Structure):
+    _fields_ = [("model_w", C.c_int32), ("model_h", C.c_int32), ("mean", C.c_float * 3), ("std", C.c_float * 3)]
+
+
+SOLO_IMG_MEAN, SOLO_IMG_STD = (123.675, 116.28, 103.53), (58.395, 57.12, 57.375)      # kSoloImgMean / kSoloImgStd, RGB order (det2d/det2d_parameter.h:24-25)
+
+
+def solo_input_params(model_w, model_h, mean=SOLO_IMG_MEAN, std=SOLO_IMG_STD):
+    """dv_solo_input_params: the network's input size and the normalisation in RGB order; the defaults are the reference's (det2d/det2d_parameter.h:24-25)"""
+    p = dv_solo_input_params()
+    p.model_w, p.model_h = int(model_w), int(model_h)
+    for c in range(3):
+        p.mean[c], p.std[c] = float(mean[c]), float(std[c])
+    return p
+
+
+def solo_input_check(img_w, img_h, model_w, model_h, mean=SOLO_IMG_MEAN, std=SOLO_IMG_STD, stride=None):
+    """the refusals of Context.solo_input_enqueue for an img_w x img_h frame (stride: bytes per row, default 3 * img_w), without a device: raises DvinsError with the reason"""
+    lib = _abi.load()
+    p = solo_input_params(model_w, model_h, mean, std)
+    if lib.dv_solo_input_check(int(img_w), int(img_h), int(3 * img_w if stride is None else stride), C.addressof(p)) != 0:
+        raise DvinsError(lib.dv_last_error(None).decode())
+
+
+class _DeviceArray:
+    """a device pointer and a shape behind __cuda_array_interface__: what torch.as_tensor wraps without a copy"""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = dict(shape=tuple(int(v) for v in shape), typestr=typestr, data=(int(ptr), False), strides=None, version=2)
+
+
+def device_tensor(ptr, shape, typestr="<f4", device=0):
+    """a contiguous torch tensor on `device` over the library's (or the caller's) device memory at ptr: no copy, no ownership — valid as long as the memory is"""
+    import torch
+    return torch.as_tensor(_DeviceArray(ptr, shape, typestr), device="cuda:%d" % device)
+
+
 class dv_mot_params(C.Structure):
     _fields_ = [("n_init", C.c_int32), ("max_age", C.c_int32), ("budget", C.c_int32), ("feat_dim", C.c_int32), ("max_tracks", C.c_int32), ("reserved", C.c_int32 * 3)]
 
@@ -235,6 +272,7 @@ class Context:
         self._out = np.zeros(_abi.DV_MAX_FEATS, FEAT_DTYPE)
         self._mot_par, self._mot_n, self._mot_keep, self._mot_pin = None, 0, None, None
         self._reid_size, self._reid_n, self._reid_keep, self._reid_pin = None, 0, None, None
+        self._solo_in_keep, self._solo_in_shape = None, None
 
     def close(self):
         if getattr(self, "h", None):
@@ -414,6 +452,41 @@ class Context:
         n, nc, st = C.c_int(0), C.c_int(0), dv_mask_stack()
         self._check(self.lib.dv_solo_head_collect(self.h, labels.ctypes.data, scores.ctypes.data, 128, C.byref(n), C.byref(nc), C.addressof(st)))
         return labels[: n.value].copy(), scores[: n.value].copy(), st, nc.value
+
+    # ---- the detector's input (Pipeline::ImageToTensor + ProcessInput, det2d/pipeline.cpp:370-387,204-232): colour frame -> the network's [3, model_h, model_w] tensor ----
+    def solo_input_enqueue(self, bgr, model_w, model_h, mean=SOLO_IMG_MEAN, std=SOLO_IMG_STD, mem=DV_MEM_HOST, stride=None, dst=None):
+        """one frame on the ctx's stream.  mem = DV_MEM_HOST: bgr an (height, width, 3) uint8 array of the ctx's size (any row stride), staged.  DV_MEM_DEVICE /
+        DV_MEM_PINNED: bgr is a pointer (int) read in place until the collect, with the row stride in bytes — the caller keeps that memory alive; only a host array
+        is held here until the collect.  dst: None — the library's two alternating buffers — or a
+        device pointer (int) to 3 * model_h * model_w floats of the caller's, 4-byte aligned"""
+        if mem == DV_MEM_HOST:
+            if not (isinstance(bgr, np.ndarray) and bgr.dtype == np.uint8 and bgr.ndim == 3 and bgr.shape[2] == 3 and bgr.strides[2] == 1 and bgr.strides[1] == 3):
+                raise ValueError("solo_input_enqueue: bgr must be (height, width, 3) uint8 with packed pixels")
+            if bgr.shape[:2] != (self.cfg.height, self.cfg.width):
+                raise ValueError("solo_input_enqueue: the image must have the ctx's size")
+            stride = bgr.strides[0]
+        else:
+            if stride is None:
+                raise ValueError("solo_input_enqueue: stride is required with device or pinned pointers")
+            if not isinstance(bgr, (int, np.integer)):
+                raise ValueError("solo_input_enqueue: bgr must be a pointer (int) with device or pinned memory")
+        par = solo_input_params(model_w, model_h, mean, std)
+        self._solo_in_keep, self._solo_in_shape = (bgr if mem == DV_MEM_HOST else None), (3, int(model_h), int(model_w))
+        self._check(self.lib.dv_solo_input_enqueue(self.h, _ptr(bgr), int(stride), int(mem), C.addressof(par), _ptr(None if dst is None else int(dst))))
+
+    def solo_input_collect(self):
+        """waits for the stage -> (device pointer of the [3, model_h, model_w] float32 tensor, its shape, the image's rectangle (x, y, w, h) inside it).  A library-owned
+        tensor stays valid until the second enqueue after this collect; frontend.device_tensor(ptr, shape) wraps it for torch without a copy"""
+        p, r = C.c_void_p(0), [C.c_int(0) for _ in range(4)]
+        self._solo_in_keep = None
+        self._check(self.lib.dv_solo_input_collect(self.h, C.byref(p), *[C.byref(v) for v in r]))
+        return p.value, self._solo_in_shape, tuple(v.value for v in r)
+
+    def solo_input(self, bgr, model_w, model_h, mean=SOLO_IMG_MEAN, std=SOLO_IMG_STD, mem=DV_MEM_HOST, stride=None, dst=None):
+        """solo_input_enqueue + solo_input_collect -> (torch device tensor [3, model_h, model_w] over the stage's memory, no copy; rectangle)"""
+        self.solo_input_enqueue(bgr, model_w, model_h, mean, std, mem, stride, dst)
+        ptr, shape, rect = self.solo_input_collect()
+        return device_tensor(ptr, shape, device=self.cfg.device), rect
 
     # ---- the multi-object tracker (DeepSORT::update, mot/deep_sort.cpp:72-139): detections + embeddings -> track ids, table and galleries resident ----
     def mot_config(self, params=None, **kw):

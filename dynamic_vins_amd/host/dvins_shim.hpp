@@ -37,6 +37,7 @@
 #include <cstring>
 #include <deque>
 #include <fstream>
+#include <functional>
 #include <list>
 #include <map>
 #include <mutex>
@@ -844,7 +845,7 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------
-// The detector's head (det2d/solo_head.h, det2d/detector2d.h) on the device: the network's output tensors stay where TensorRT left them and become the instance-mask
+// The detector's head (det2d/solo_head.h, det2d/detector2d.h) and input (det2d/pipeline.h) on the device: the network's output tensors stay where TensorRT left them and become the instance-mask
 // stack there (dv_solo_head_enqueue / _collect).  ImageInfo = det2d/pipeline.h's; SetImageInfo restates Pipeline::GetXYWHS.
 struct ImageInfo { int origin_h = 0, origin_w = 0, rect_x = 0, rect_y = 0, rect_w = 0, rect_h = 0; };
 inline ImageInfo SetImageInfo(int model_w, int model_h, int img_w, int img_h) {
@@ -875,9 +876,42 @@ public:
 private:
     dv_ctx* ctx_; dv_solo_params para_;
 };
+// The detector's input (det2d/pipeline.h) on the device: Pipeline::ImageToTensor + Pipeline::ProcessInput (det2d/pipeline.cpp:370-387,204-232) as dv_solo_input_enqueue /
+// _collect — the 8-bit BGR frame of the ctx's size (host memory, or device memory with bgr.device) -> the network's [3, model_h, model_w] float32 tensor on the device.
+// dst = nullptr: the library's two alternating buffers (the pointer stays valid until the second ProcessInput after it); else the caller's device buffer, the network's
+// own binding.  image_info is what GetXYWHS leaves: filled by every ProcessInput from the frame's size.  mean / std: det2d_parameter.h:24-25, RGB order.
+class Pipeline {
+public:
+    using Ptr = std::shared_ptr<Pipeline>;
+    Pipeline(dv_ctx* ctx, int model_w, int model_h) : Pipeline(ctx, model_w, model_h, {123.675f, 116.28f, 103.53f}, {58.395f, 57.12f, 57.375f}) {}
+    Pipeline(dv_ctx* ctx, int model_w, int model_h, const std::array<float, 3>& mean, const std::array<float, 3>& std_dev) : ctx_(ctx) {
+        if (!ctx) throw std::runtime_error("Pipeline: a ctx is required (dv_create failed? " + std::string(dv_last_error(nullptr)) + ")");
+        par_.model_w = model_w; par_.model_h = model_h;
+        for (int c = 0; c < 3; ++c) { par_.mean[c] = mean[c]; par_.std[c] = std_dev[c]; }
+    }
+    ImageInfo image_info;
+    void ProcessInputEnqueue(const ImageView& bgr, float* dst = nullptr) {
+        if (bgr.empty() || !bgr.bgr) throw std::runtime_error("Pipeline::ProcessInput: an 8-bit BGR image is required");
+        if (dv_solo_input_check(bgr.width, bgr.height, bgr.stride, &par_) != 0) throw std::runtime_error(std::string("Pipeline::ProcessInput: ") + dv_last_error(nullptr));
+        detail::check(ctx_, dv_solo_input_enqueue(ctx_, bgr.data, bgr.stride, bgr.device ? DV_MEM_DEVICE : DV_MEM_HOST, &par_, dst), "Pipeline::ProcessInput");
+        origin_w_ = bgr.width; origin_h_ = bgr.height;
+    }
+    const float* ProcessInputCollect() {
+        const float* t = nullptr;
+        ImageInfo i; i.origin_w = origin_w_; i.origin_h = origin_h_;
+        detail::check(ctx_, dv_solo_input_collect(ctx_, &t, &i.rect_x, &i.rect_y, &i.rect_w, &i.rect_h), "Pipeline::ProcessInput");
+        image_info = i;
+        return t;
+    }
+    const float* ProcessInput(const ImageView& bgr, float* dst = nullptr) { ProcessInputEnqueue(bgr, dst); return ProcessInputCollect(); }
+    int model_w() const { return par_.model_w; } int model_h() const { return par_.model_h; }
+private:
+    dv_ctx* ctx_; dv_solo_input_params par_{}; int origin_w_ = 0, origin_h_ = 0;
+};
 class Detector2D {
 public:
-    Detector2D(dv_ctx* ctx, const dv_solo_params& para, int model_w, int model_h, int img_w, int img_h) : solo_(ctx, para), info_(SetImageInfo(model_w, model_h, img_w, img_h)) {}
+    Detector2D(dv_ctx* ctx, const dv_solo_params& para, int model_w, int model_h, int img_w, int img_h)
+        : solo_(ctx, para), info_(SetImageInfo(model_w, model_h, img_w, img_h)), ctx_(ctx), model_w_(model_w), model_h_(model_h) {}
     // Detector2D::ForwardTensor behind the network (det2d/detector2d.cpp:273-278): the head, then thread T1's stage on its stack — BuildBoxes2D's rectangles come back from
     // insts.StackFrameCollect(); a frame without instances enqueues no stage (false).  The COCO -> KITTI naming of BuildBoxes2D stays with the caller: seg.cate_labels
     bool ForwardHead(const dv_solo_outputs& outputs, InstsFeatManager& insts, SoloSeg* seg_out = nullptr) {
@@ -887,9 +921,16 @@ public:
         if (seg_out) *seg_out = std::move(s);
         return any;
     }
+    // Detector2D::ForwardTensor as a whole (det2d/detector2d.cpp:245-280): pipeline_->ProcessInput(img), the caller's network on the input tensor (net: device pointer of
+    // the [3, model_h, model_w] floats -> its eleven output tensors; the network's stream is the caller's to order), then ForwardHead on them
+    bool ForwardTensor(const ImageView& bgr, const std::function<dv_solo_outputs(const float*)>& net, InstsFeatManager& insts, SoloSeg* seg_out = nullptr) {
+        if (!pipeline_) pipeline_ = std::make_unique<Pipeline>(ctx_, model_w_, model_h_);
+        const float* input = pipeline_->ProcessInput(bgr);
+        return ForwardHead(net(input), insts, seg_out);
+    }
     const ImageInfo& image_info() const { return info_; }
 private:
-    Solov2 solo_; ImageInfo info_;
+    Solov2 solo_; ImageInfo info_; dv_ctx* ctx_; int model_w_, model_h_; std::unique_ptr<Pipeline> pipeline_;
 };
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -215,7 +215,7 @@ class DynamicPipeline(Pipeline):
 
     def __init__(self, seq: DynamicSequence, max_cnt=250, min_dist=25, max_iters=10, device=0, use_imu=1, max_dynamic_cnt=50, min_dynamic_dist=5, use_det3d=1,
                  static_inst_threshold=1.0, mask_morphology_size=0, segments=None, est_kw=None, extra_from_disparity=True, ba_stride=1,
-                 static_as_background=False, live_masks=False, mask_stack=False, solo_head=None, mot=None):
+                 static_as_background=False, live_masks=False, mask_stack=False, solo_head=None, mot=None, solo_input=None):
         from .frontend import DV_MODE_SEMANTIC
         # live_masks: `seq` carries label images (a viode.ViodeSequence: seg0, seg1, dyn_keys) and thread T1's stage runs per frame on the device (viode_frame_enqueue /
         # _collect + the key-image entries) instead of reading the sequence's pre-computed masks, detections and key images; same results, bit for bit
@@ -227,12 +227,23 @@ class DynamicPipeline(Pipeline):
         # solo_head: the detector's head in front of that stack — a callable k -> (dv_solo_outputs, dv_solo_params, ids) supplies the network's eleven output tensors of
         # frame k (frontend.solo_outputs / solo_params) and ids(labels, scores, stack) -> (track ids, class ids) per plane, the upstream multi-object tracker's answer
         # (-1 drops a plane).  Context.solo_head_enqueue / _collect fill the stack, which goes down the mask-stack path unchanged; the head of frame k + 1 is enqueued
-        # behind the tracking of frame k.  Refused together with live_masks (and with mask_stack: the head IS the source of the stack)
+        # behind the tracking of frame k.  Refused together with live_masks (and with mask_stack: the head IS the source of the stack).  With solo_input (below) the
+        # callable is called as (k, input) -> the same triple
         if solo_head is not None and (live_masks or mask_stack):
             raise ValueError("DynamicPipeline: solo_head cannot be combined with live_masks or mask_stack")
         if solo_head is not None and not callable(solo_head):
-            raise ValueError("DynamicPipeline: solo_head must be a callable k -> (outputs, params, ids)")
+            raise ValueError("DynamicPipeline: solo_head must be a callable k -> (outputs, params, ids), or (k, input) -> the same with solo_input")
         self.solo_head, self._solo_enq, self._solo_ids, self._solo_blank = solo_head, None, None, None
+        # solo_input: the detector's input in front of the caller's network — (model_w, model_h[, mean, std]), the keywords of Context.solo_input_enqueue.  The callable
+        # is then called as solo_head(k, input): input = the [3, model_h, model_w] float32 device tensor built from reid_image(k) by Pipeline::ImageToTensor + ProcessInput's
+        # rule (det2d/pipeline.cpp:370-387,204-232), in the library's memory (the two alternating buffers: frame k's stays intact while frame k + 1's is built).  Only
+        # together with solo_head
+        if solo_input is not None:
+            if solo_head is None:
+                raise ValueError("DynamicPipeline: solo_input needs solo_head, the callable that takes the input")
+            if not (isinstance(solo_input, (tuple, list)) and len(solo_input) in (2, 4)):
+                raise ValueError("DynamicPipeline: solo_input must be (model_w, model_h) or (model_w, model_h, mean, std)")
+        self.solo_input = None if solo_input is None else tuple(solo_input)
         # mot: the multi-object tracker on the device (DeepSORT::update, mot/deep_sort.cpp:72-139) behind the stack stage — (feats, params): feats(k, dets, stack) ->
         # the caller's ReID network on the frame's crops, an [n, feat_dim] float32 device tensor (or a device pointer) with L2-normalised rows, one per detection the
         # stack stage reports after the class filter, in that order; params = the keywords of frontend.mot_params.  Track ids then come from Context.mot_update_* in place
@@ -367,7 +378,15 @@ class DynamicPipeline(Pipeline):
             self._live_enq = k + 1
 
     def _solo_enqueue_head(self, k):
-        o, p, ids = self.solo_head(k)
+        if self.solo_input is not None:          # the network's input of frame k from the resident colour frame, then the caller's network on it
+            import torch
+            from .frontend import DV_MEM_DEVICE as DEV
+            img = self.reid_image(k)
+            torch.cuda.current_stream().synchronize()
+            inp, _ = self.ctx.solo_input(img.data_ptr(), *self.solo_input, mem=DEV, stride=img.stride(0))
+            o, p, ids = self.solo_head(k, inp)
+        else:
+            o, p, ids = self.solo_head(k)
         self.ctx.solo_head_enqueue(o, p)
         self._solo_enq, self._solo_ids = k, ids
 

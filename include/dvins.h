@@ -266,6 +266,32 @@ int dv_solo_rect(int model_w, int model_h, int img_w, int img_h, int* rect_x, in
 int dv_solo_check(const dv_solo_outputs* out, const dv_solo_params* par);
 int dv_solo_head_enqueue(dv_ctx* ctx, const dv_solo_outputs* out, const dv_solo_params* par);
 int dv_solo_head_collect(dv_ctx* ctx, int32_t* labels, float* scores, int cap, int* n, int* n_candidates, dv_mask_stack* stack);
+/* The detector's INPUT for ONE frame: the colour frame -> the network's normalised, resized, zero-padded [3, model_h, model_w] float32 tensor, on the device.  It restates
+ * Pipeline::ImageToTensor (det2d/pipeline.cpp:370-387, called at image_process/image_process.cpp:138) followed by Pipeline::ProcessInput (det2d/pipeline.cpp:204-232,
+ * called at det2d/detector2d.cpp:249), the step in front of the network; the network itself stays with the caller.  The frame is the ctx's width x height, 8-bit BGR with
+ * `stride` bytes per row, as ImageToTensor receives it (where the reference undistorts, the frame after its remap: dv_remap).  In this order:
+ *   swap         plane c of the tensor reads byte 2 - c of a pixel (BGR -> RGB), as float.
+ *   normalise    (v - mean[c]) / std[c] in float32, IEEE division; mean / std in RGB order (det2d/det2d_parameter.h:24-25: 123.675, 116.28, 103.53 / 58.395, 57.12, 57.375).
+ *   resample     bilinear, align_corners = true, to rect_h x rect_w of dv_solo_rect, by upsample_bilinear2d's float32 rule: per axis scale = float(in - 1) / float(out - 1),
+ *                r = scale * dst, i0 = int(r), i1 = i0 + (i0 < in - 1), l1 = r - i0, l0 = 1 - l1; value = lh0 (lw0 p00 + lw1 p01) + lh1 (lw0 p10 + lw1 p11).  A declared
+ *                choice of evaluation: float32 nested differences, top = p00 + lw1 (p01 - p00), bot likewise, top + lh1 (bot - top) — the same value within 1.6e-6 of
+ *                its exact evaluation (derivation: csrc/solo_input_host.h), and the form in which an upper weight of 0 returns the sample's bits and an image of
+ *                constant colour returns the constant's bits (the sum of products with a rounded 1 - l1 leaves such an image up to one ulp off, as the tensor
+ *                library's own kernels do).
+ *   pad          +0.0 everywhere outside the rectangle (the reference pads with zeros, not with the mean colour).
+ * Refused, each with its own dv_last_error text: non-positive sizes (sides above 16384 too); an image or rectangle side under 2; a zero std, a non-finite mean or std; a
+ * stride under 3 * width; a rectangle with model_h - rect_h or model_w - rect_w odd — there the reference concatenates two pads of (model - rect) / 2 and hands the network
+ * a tensor one row or column short (the rectangle's side is even, so that is every odd model side in the padded direction); an unknown memory kind.
+ * dv_solo_input_check: those refusals without a device (0, or < 0 with dv_last_error(NULL)).
+ * _enqueue: ONE kernel on the ctx's stream writes EVERY element of the tensor (nothing relies on an earlier clear).  mem = DV_MEM_HOST (the frame is staged) or
+ * DV_MEM_DEVICE / DV_MEM_PINNED (read in place, any base alignment, valid until the collect).  dst_dev = NULL: one of two library-owned buffers used alternately — the
+ * pointer _collect returns stays valid until the SECOND enqueue after it (as long as the model size does not grow), so frame k + 1's input is built while the caller's
+ * network still reads frame k's.  dst_dev != NULL: a caller-owned device buffer of 3 * model_h * model_w floats (the network's own binding), 4-byte aligned, no more.
+ * One frame may be in flight.  _collect waits for the stage and returns the tensor's device pointer and the rectangle (any of the five may be NULL). */
+typedef struct dv_solo_input_params { int32_t model_w, model_h; float mean[3], std[3]; } dv_solo_input_params;
+int dv_solo_input_check(int img_w, int img_h, int stride, const dv_solo_input_params* par);
+int dv_solo_input_enqueue(dv_ctx* ctx, const uint8_t* bgr, int stride, int mem, const dv_solo_input_params* par, float* dst_dev);
+int dv_solo_input_collect(dv_ctx* ctx, const float** input_dev, int* rect_x, int* rect_y, int* rect_w, int* rect_h);
 /* The MULTI-OBJECT TRACKER between the detector and the object tracker: a frame's detection rectangles and appearance embeddings -> a track id per detection, as
  * InstsFeatManager::AddInstancesByTracking (front_end/dynamic_tracker.cpp:791-828) gets them from DeepSORT::update (mot/deep_sort.cpp:72-139).  Track table and appearance
  * galleries stay in HBM between frames.  The ReID network (mot/reid_net.cpp, mot/extractor.cpp) stays with the caller: feats is its output, [n, feat_dim] float32 rows
