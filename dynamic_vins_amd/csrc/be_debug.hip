@@ -65,17 +65,17 @@ int dv_ba_debug_slot_log(dv_ctx* ctx, unsigned long long* vals, long long cap_va
     return 0;
 }
 
-// the linearisation buffers as the device holds them (include/dvins.h; tests/test_eval_chain.py compares them bit for bit with records of an earlier library)
+// the linearisation buffers as the device holds them (include/dvins.h; tests/test_eval_chain.py and tests/test_reduce_chain.py compare them bit for bit with records of an earlier library)
 int dv_ba_debug_buffer(dv_ctx* ctx, int which, int set, void* host, long long bytes) {
     if (!ctx) return -1;
-    if (which < 0 || which > 7 || set < 0 || set > 1) DV_FAIL("dv_ba_debug_buffer: bad buffer");
+    if (which < 0 || which > 8 || set < 0 || set > 1) DV_FAIL("dv_ba_debug_buffer: bad buffer");
     if (ctx->be.pend->active) DV_FAIL("dv_ba_debug_buffer: a solve is in flight");
     DV_CHECK(hipSetDevice(ctx->cfg.device));
     if (be_ensure(ctx, 0)) return -1;
     BeWork& w = ctx->be;
     const size_t n = BE_MAX_STATE;
-    void* const ptr[8] = { w.packets[set], w.imu_out[set], w.prior_out[set], w.cand_cost, w.lm_obs, w.Hd[set], w.Sc[set], w.gvec[set] };
-    const size_t cap[8] = { 8 * (size_t)BE_PK_SIZE * BE_PK_STRIDE, 8 * (size_t)BE_WIN * IMU_OUT_STRIDE, 8 * (BE_MAX_PRIOR + 1), 8 * (BE_MAX_LM + BE_WIN + 1), 4 * BE_MAX_LM, 8 * n * n, 8 * n * n, 8 * 2 * n };
+    void* const ptr[9] = { w.packets[set], w.imu_out[set], w.prior_out[set], w.cand_cost, w.lm_obs, w.Hd[set], w.Sc[set], w.gvec[set], w.scale_l };
+    const size_t cap[9] = { 8 * (size_t)BE_PK_SIZE * BE_PK_STRIDE, 8 * (size_t)BE_WIN * IMU_OUT_STRIDE, 8 * (BE_MAX_PRIOR + 1), 8 * (BE_MAX_LM + BE_WIN + 1), 4 * BE_MAX_LM, 8 * n * n, 8 * n * n, 8 * 2 * n, 8 * (size_t)BE_MAX_LM };
     DV_CHECK(hipStreamSynchronize(ctx->be_stream));
     if (!host) { DV_CHECK(hipMemset(ptr[which], 0xFF, cap[which])); return 0; }
     if (bytes < 0 || (size_t)bytes > cap[which]) DV_FAIL("dv_ba_debug_buffer: more bytes than the buffer holds");

@@ -137,13 +137,192 @@ __device__ __forceinline__ double wave_sum(double v) { return wave_sum_f64(v); }
 // blocks [0, 121): pose block (fi, fj) of the reduced system — landmark sums read the transposed packets coalesced
 //                  (lane = landmark), wave-tree reduced; blocks [121, ..): every entry that has no landmark term.
 #define DV_CONSTANT __attribute__((address_space(4)))
-template <bool SHARD, class ARGS>
+// The pair block of the single-window kernel (be_reduce_body<false, true>): the same sums as the shared form below, without its list barrier.  There wave 2
+// compacts the pair's landmarks for everybody and the tables of wave 6 are staged by other waves, so all seven waves stand at a workgroup barrier for one
+// wave's round trips.  Here every row wave requests lm_obs itself (the same addresses: L1 / L2 hits), only the chunks that exist, and compacts by the same
+// ballot / prefix-count rule into an LDS slice of its own: entry idx names the same landmark, so lane and trip of every landmark, and with them every partial
+// sum, are what they were.  Wave 6 fetches the IMU frames, the prior's header and its prior columns itself and starts its index chains at once.  The operands
+// of a lane's first RED_OWN_TRIPS trips are requested together (the direct terms one round trip behind them: their address depends on the landmark's anchor),
+// the additions follow in ascending idx order, and the general loop takes what lies behind (more than 64 * RED_OWN_TRIPS landmarks common to a pair).
+// The one workgroup barrier left stands in front of the stores; the returns ahead of it depend on the pair and the window alone.
+#ifndef RED_OWN_TRIPS
+#define RED_OWN_TRIPS 2
+#endif
+template <class ARGS>
+__device__ __forceinline__ void be_reduce_pair_own(const ARGS& a, const BeCtl& c, int set, double mu, int bx) {
+    int fi, fj; red_pair(bx, fi, fj);
+    if (bx == 0) RTS(4);
+    if (fi >= a.dims.nframes || fj >= a.dims.nframes) return;
+    const int ci0 = a.dims.pose_col[fi], cj0 = a.dims.pose_col[fj];
+    if (ci0 < 0 || cj0 < 0) return;
+    const int n = a.dims.nstate, nlm = a.dims.nlm;
+    const double* pk = a.packets[set];
+    const int ci = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const bool diag = fi == fj;
+    __shared__ double s_dh[36], s_dg[6];
+    __shared__ int s_ifi[BE_WIN + 1], s_ifj[BE_WIN + 1];
+    __shared__ unsigned short s_lists[6][BE_MAX_LM];
+    double S[6] = {0, 0, 0, 0, 0, 0}, H[6] = {0, 0, 0, 0, 0, 0}, G = 0, GS = 0;
+    if (ci == 6) {
+        // the frames of the IMU factors go through LDS words only this wave touches (the wave's own LDS order, no workgroup barrier); the prior's header and this
+        // lane's prior columns are requested in the same round trip
+        const int pv = a.prior->valid, pn = a.prior->n;
+        const int pi = a.prior_col[ci0 + (lane < 36 ? lane / 6 : lane < 42 ? lane - 36 : 0)], pj = a.prior_col[cj0 + (lane < 36 ? lane % 6 : 0)];
+        if (lane < a.dims.nimu) { s_ifi[lane] = a.imu[lane].fi; s_ifj[lane] = a.imu[lane].fj; }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+        const RedCtx rc{ s_ifi, s_ifj, pv, pn };
+#ifdef BE_RED_TS
+        if (bx == 0 && lane == 0) be_red_ts[16] = wall_clock64();
+#endif
+        if (lane < 36) s_dh[lane] = red_dense_h_pose(a, rc, a.imu_out[set], fi, lane / 6, fj, lane % 6, pi, pj);
+        else if (diag && lane < 42) s_dg[lane - 36] = red_dense_g_pose(a, rc, a.imu_out[set], a.prior_out[set], fi, lane - 36, pi);
+#ifdef BE_RED_TS
+        if (bx == 0 && lane == 0) be_red_ts[17] = wall_clock64();
+#endif
+    } else {
+        unsigned short* const list = s_lists[ci];
+        constexpr int NCH = (BE_MAX_LM + 63) / 64;
+        int obv[NCH];
+#pragma unroll
+        for (int u = 0; u < NCH; ++u) { const int l = 64 * u + lane; obv[u] = 64 * u < nlm ? a.lm_obs[l < nlm ? l : 0] : 0; }
+        int cnt = 0;
+#pragma unroll
+        for (int u = 0; u < NCH; ++u) {
+            const int c0 = 64 * u;
+            if (c0 >= nlm) break;
+            const int l = c0 + lane;
+            const int ob = l < nlm ? obv[u] : 0;
+            const bool m = ((ob >> fi) & 1) && ((ob >> fj) & 1);
+            const unsigned long long bal = __ballot(m);
+            if (m) list[cnt + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned short)l;
+            cnt += __popcll(bal);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+        if (bx == 0) RTS(0);
+        const int e_wi = BE_PK_W + fi * 6 + ci, e_wj = BE_PK_W + fj * 6;
+        const int e_dd = BE_PK_DD + fi * 36 + ci * 6;
+        const int e_da_i = BE_PK_DA + fj * 36 + ci * 6;                 // anchor == fi : row ci of block (anchor, fj)
+        const int e_da_j = BE_PK_DA + fi * 36 + ci;                     // anchor == fj : column ci of the transposed block
+        constexpr int T = RED_OWN_TRIPS, TA = T > 0 ? T : 1;
+        if (T > 0) {
+            bool lv[TA]; int ll[TA], anc[TA]; double h[TA], sc[TA], wi[TA], wj[TA][6], dt[TA][6], gp[TA], gg[TA];
+#pragma unroll
+            for (int t = 0; t < T; ++t) { lv[t] = lane + 64 * t < cnt; ll[t] = lv[t] ? list[lane + 64 * t] : 0; }
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                anc[t] = -1; h[t] = 0; sc[t] = 0; wi[t] = 0; gp[t] = 0; gg[t] = 0;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) { wj[t][q] = 0; dt[t][q] = 0; }
+                if (lv[t]) {
+                    const int l = ll[t];
+                    if (!diag) anc[t] = a.lm[l].anchor;
+                    h[t] = BE_PK(pk, BE_PK_H, l);
+                    if (!c.first) sc[t] = a.scale_l[l];
+                    wi[t] = BE_PK(pk, e_wi, l);
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) wj[t][q] = BE_PK(pk, e_wj + q, l);
+                    if (diag) {
+#pragma unroll
+                        for (int q = 0; q < 6; ++q) dt[t][q] = BE_PK(pk, e_dd + q, l);
+                        gp[t] = BE_PK(pk, BE_PK_GP + fi * 6 + ci, l);
+                        gg[t] = BE_PK(pk, BE_PK_G, l);
+                    }
+                }
+            }
+            if (!diag) {
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    if (lv[t] && anc[t] == fi) {
+#pragma unroll
+                        for (int q = 0; q < 6; ++q) dt[t][q] = BE_PK(pk, e_da_i + q, ll[t]);
+                    } else if (lv[t] && anc[t] == fj) {
+#pragma unroll
+                        for (int q = 0; q < 6; ++q) dt[t][q] = BE_PK(pk, e_da_j + q * 6, ll[t]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                if (!lv[t]) continue;
+                const double s = c.first ? 1.0 / (1.0 + sqrt(h[t])) : sc[t];
+                double d2 = h[t] * s * s; d2 = fmin(fmax(d2, 1e-6), 1e32);
+                const double rho = 1.0 / (h[t] + mu * d2 / (s * s));
+#pragma unroll
+                for (int q = 0; q < 6; ++q) S[q] += rho * (wi[t] * wj[t][q]);      // rho * (wi * wj): bitwise symmetric
+                if (diag) {
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) H[q] += dt[t][q];
+                    G += gp[t];
+                    GS += rho * (wi[t] * gg[t]);
+                } else if (anc[t] == fi || anc[t] == fj) {
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) H[q] += dt[t][q];
+                }
+            }
+        }
+        for (int idx = lane + 64 * T; idx < cnt; idx += 64) {
+            const int l = list[idx];
+            const double h = BE_PK(pk, BE_PK_H, l);
+            const double s = c.first ? 1.0 / (1.0 + sqrt(h)) : a.scale_l[l];
+            double d2 = h * s * s; d2 = fmin(fmax(d2, 1e-6), 1e32);
+            const double rho = 1.0 / (h + mu * d2 / (s * s));
+            const double wi = BE_PK(pk, e_wi, l);
+#pragma unroll
+            for (int q = 0; q < 6; ++q) S[q] += rho * (wi * BE_PK(pk, e_wj + q, l));
+            if (diag) {
+#pragma unroll
+                for (int q = 0; q < 6; ++q) H[q] += BE_PK(pk, e_dd + q, l);
+                G += BE_PK(pk, BE_PK_GP + fi * 6 + ci, l);
+                GS += rho * (wi * BE_PK(pk, BE_PK_G, l));
+            } else {
+                const int anc = a.lm[l].anchor;
+                if (anc == fi) {
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) H[q] += BE_PK(pk, e_da_i + q, l);
+                } else if (anc == fj) {
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) H[q] += BE_PK(pk, e_da_j + q * 6, l);
+                }
+            }
+        }
+        if (bx == 0) RTS(1);
+#pragma unroll
+        for (int q = 0; q < 6; ++q) { S[q] = wave_sum(S[q]); H[q] = wave_sum(H[q]); }
+        if (diag) { G = wave_sum(G); GS = wave_sum(GS); }
+    }
+    __syncthreads();
+    if (bx == 0) RTS(2);
+    if (ci == 6) return;
+    if (lane < 6) {
+        double sv = S[0], hv = H[0];
+#pragma unroll
+        for (int q = 1; q < 6; ++q) if (lane == q) { sv = S[q]; hv = H[q]; }
+        const int i = ci0 + ci, j = cj0 + lane;
+        const double hd = hv + s_dh[ci * 6 + lane];
+        a.Hd[set][(size_t)i * n + j] = hd;
+        if ((j >> 2) <= (i >> 2)) a.Sc[set][blk_pos(i, j, (n + 3) >> 2)] = hd - sv;
+        if (!diag) {                                  // the mirrored entry, as in the shared form
+            a.Hd[set][(size_t)j * n + i] = hd;
+            if ((i >> 2) <= (j >> 2)) a.Sc[set][blk_pos(j, i, (n + 3) >> 2)] = hd - sv;
+        }
+    } else if (diag && lane == 6) {
+        const int i = ci0 + ci;
+        a.gvec[set][i] = G + s_dg[ci];
+        a.gvec[set][n + i] = GS;
+    }
+    if (bx == 0) RTS(3);
+}
+
+// OWN: the pair blocks in the form above (the single-window kernel); the batched and the sharded kernels keep the shared form
+template <bool SHARD, bool OWN, class ARGS>
 __device__ __forceinline__ void be_reduce_body(const ARGS& a, int spec, int bx) {
     const BeCtl c = *a.ctl;
     if (c.done) return;
     int set = c.cur; double mu = c.mu;
     if (spec && c.pending) { set ^= 1; mu = fmax(1e-8, 2.0 * c.mu / 10.0); }      // the candidate's set, with the mu be_accept leaves behind an accepted step
     else if (!c.need_eval && !c.chol_fail) return;                                // Hd/Sc are still valid when the last step was rejected
+    if constexpr (OWN && !SHARD) { if (bx < RED_PAIRS) { be_reduce_pair_own(a, c, set, mu, bx); return; } }
+    if (bx == 0) RTS(4);      // (stamped builds: a pair block's entry, ahead of the tables and the list)
     const int n = a.dims.nstate, nlm = a.dims.nlm;
     const double* pk = a.packets[set];
     double* const Hd = a.Hd[set]; double* const Sc = a.Sc[set]; double* const gvec = a.gvec[set];
@@ -359,13 +538,13 @@ __device__ __forceinline__ void be_reduce_body(const ARGS& a, int spec, int bx) 
     if (bx == RED_PAIRS + 3) RTS(9);
 }
 
-__global__ __launch_bounds__(RED_THREADS) void be_reduce_kernel(BeSolveArgs a, int spec) { be_reduce_body<false>(a, spec, blockIdx.x); }
-__global__ __launch_bounds__(RED_THREADS) void be_reduce_shard_kernel(BeSolveArgs a, int spec) { be_reduce_body<true>(a, spec, blockIdx.x); }
+__global__ __launch_bounds__(RED_THREADS) void be_reduce_kernel(BeSolveArgs a, int spec) { be_reduce_body<false, true>(a, spec, blockIdx.x); }
+__global__ __launch_bounds__(RED_THREADS) void be_reduce_shard_kernel(BeSolveArgs a, int spec) { be_reduce_body<true, false>(a, spec, blockIdx.x); }
 __global__ __launch_bounds__(RED_THREADS) void be_reduce_batch_kernel(const BeSolveArgs* __restrict__ tab, int spec) {      // blockIdx.y = window
     const DV_CONSTANT BeSolveArgs& a = *reinterpret_cast<const DV_CONSTANT BeSolveArgs*>(reinterpret_cast<uintptr_t>(tab + blockIdx.y));      // the table through the constant (scalar, invariant) path
     const int n = a.dims.nstate;
     if ((int)blockIdx.x >= RED_PAIRS + (n * n + n + RED_THREADS - 1) / RED_THREADS) return;
-    be_reduce_body<false>(a, spec, blockIdx.x);
+    be_reduce_body<false, false>(a, spec, blockIdx.x);
 }
 // the same body capped at 80 VGPRs (5 of them spilled, 24 B of scratch per lane): THREE 7-wave workgroups per CU instead of two — 16 windows are 2048 workgroups against 512
 // resident at 96 VGPRs (four occupancy rounds of ~15 us: what the launch's 66 us were in round 5), 768 with the cap.  Used from 12 windows per launch on (be_launch_reduce_batch).
@@ -373,7 +552,7 @@ __global__ __launch_bounds__(RED_THREADS) __attribute__((amdgpu_waves_per_eu(6, 
     const DV_CONSTANT BeSolveArgs& a = *reinterpret_cast<const DV_CONSTANT BeSolveArgs*>(reinterpret_cast<uintptr_t>(tab + blockIdx.y));
     const int n = a.dims.nstate;
     if ((int)blockIdx.x >= RED_PAIRS + (n * n + n + RED_THREADS - 1) / RED_THREADS) return;
-    be_reduce_body<false>(a, spec, blockIdx.x);
+    be_reduce_body<false, false>(a, spec, blockIdx.x);
 }
 void be_launch_reduce_batch(const BeSolveArgs* tab_dev, int n_win, int max_n, int spec, hipStream_t s) {
     // measured (round 6, one box): 64 sequences (groups of 16 windows) 10167 / 10547 -> 10458 / 11121 frames/s with the cap; 16 sequences (groups of 4: 512 workgroups, one round either

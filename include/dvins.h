@@ -767,8 +767,8 @@ int dv_ba_debug_dev_log(dv_ctx* ctx, unsigned long long* rows7, int cap, int* n_
 /* and per LAUNCH of the round: for every fused solve 16 slots x 5 launch kinds (head evaluation, head reduce, solve, candidate evaluation, candidate reduce) x 16 hashed buffers */
 int dv_ba_debug_slot_log(dv_ctx* ctx, unsigned long long* vals, long long cap_vals, long long* n_vals, int* row_len);
 /* the linearisation buffers of the window solve as the device holds them (bit comparisons of the evaluation across library versions): which = 0 packets
- * [928][1024] doubles, 1 imu_out [10][936], 2 prior_out [193], 3 cand_cost [1011], 4 lm_obs [1000] int32, 5 Hd [178][178], 6 Sc [178 * 178], 7 gvec [356]; set = 0 / 1
- * (ignored for 3, 4).  host != NULL: the first `bytes` bytes of the buffer, after the BA stream has drained; host == NULL: the whole buffer is filled with 0xFF bytes, so
+ * [928][1024] doubles, 1 imu_out [10][936], 2 prior_out [193], 3 cand_cost [1011], 4 lm_obs [1000] int32, 5 Hd [178][178], 6 Sc [178 * 178], 7 gvec [356], 8 scale_l [1000] (the
+ * landmarks' Jacobi scales, written by the reduce of a first iteration); set = 0 / 1 (ignored for 3, 4, 8).  host != NULL: the first `bytes` bytes of the buffer, after the BA stream has drained; host == NULL: the whole buffer is filled with 0xFF bytes, so
  * that what a later launch does not write shows.  -1: bad argument or `bytes` beyond the buffer */
 int dv_ba_debug_buffer(dv_ctx* ctx, int which, int set, void* host, long long bytes);
 /* the mask bytes the dynamic front end's kernels wrote, for tests, after the frame was collected: which = 0 the background tracker's working mask of the last frame that
