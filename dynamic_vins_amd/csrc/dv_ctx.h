@@ -1,6 +1,7 @@
 // dv_ctx.h — private context definition shared by the front-end and back-end ABI implementations.
 #pragma once
 #include "dv_internal.h"
+#include "dv_mem.h"
 #include "be_types.h"
 #include "be_kernels.h"
 #include <cmath>
@@ -174,11 +175,13 @@ void dv_est_destroy_internal(dv_estimator* e);
 struct dv_inst_tracker;
 void dv_inst_destroy_internal(dv_inst_tracker* t);
 int dv_inst_wait_before_next_frame(dv_ctx* ctx, hipStream_t s, bool consume = true);
-// A dv_mask_stack as the kernels read it (dvins_api.hip).  st: a descriptor dv_stack_check passed, strides filled in.  Device / pinned stacks are read in place.  A host
+// A dv_mask_stack as the kernels read it (mask_frame.hip).  st: a descriptor dv_stack_check passed, strides filled in.  Device / pinned stacks are read in place.  A host
 // stack is taken from the copy the frame's dv_inst_stack_frame_enqueue staged when st equals that stack's descriptor and the frame has been collected (one staging per
 // frame); any other host stack is staged into own_buf, tightly packed, on s
 int dv_stack_resolve(dv_ctx* ctx, const dv_mask_stack& st, struct DevBuf& own_buf, hipStream_t s, DvStackSrc* out);
 void dv_stack_frame_done(dv_ctx* ctx);      // dv_track_stereo_collect: the shared staging ends with the frame
+void dv_viode_frame_release(dv_ctx* ctx);   // mask_frame.hip: the label-image stage's buffer sets (dv_destroy)
+void dv_inst_stack_frame_release(dv_ctx* ctx);      // mask_frame.hip: the mask-stack stage's buffer sets (dv_destroy)
 void dv_solo_head_release(dv_ctx* ctx);     // solo_head.hip: the head's buffers (dv_destroy)
 void dv_solo_input_release(dv_ctx* ctx);    // solo_input.hip: the input tensors and the staged frame (dv_destroy)
 void dv_mot_release(dv_ctx* ctx);           // mot.hip: the tracker's table and galleries (dv_destroy)
@@ -230,9 +233,9 @@ struct dv_ctx {
     std::vector<UnmaskRect> unmask; UnmaskSrc unmask_src; void* unmask_pinned = nullptr; size_t unmask_pinned_bytes = 0; DevBuf unmask_src_buf;
     // dv_viode_frame_enqueue / _collect: thread T1's per-frame stage (label images -> inverse merged mask, key images, boxes) on the ctx's stream.  Two buffer sets
     // used alternately: set[cur] belongs to the frame enqueued last; the key images of the frame before stay intact while its objects are tracked
-    struct ViodeFrame* viode = nullptr;      // (defined in dvins_api.hip, released by dv_destroy)
+    struct ViodeFrame* viode = nullptr;      // (defined in mask_frame.hip, released by dv_destroy)
     // dv_inst_stack_frame_enqueue / _collect: the same stage from a detector's mask stack (merged mask, inverse, boxes; a DV_MEM_HOST stack staged once per frame)
-    struct InstStackFrame* istack = nullptr;      // (defined in dvins_api.hip, released by dv_destroy)
+    struct InstStackFrame* istack = nullptr;      // (defined in mask_frame.hip, released by dv_destroy)
     // dv_solo_head_enqueue / _collect: the detector's head in front of that stage (network outputs -> mask stack; solo_head.hip, released by dv_solo_head_release)
     struct SoloHeadFrame* solo = nullptr;
     // dv_solo_input_enqueue / _collect: the detector's input in front of the network (colour frame -> [3, model_h, model_w]; solo_input.hip, released by dv_solo_input_release)
@@ -285,6 +288,25 @@ void dv_set_error(dv_ctx* ctx, const std::string& msg);
     } while (0)
 #define DV_FAIL(msg) do { dv_set_error(ctx, msg); return -1; } while (0)
 
+// ---- The staging rule: a caller's 2-D array as the kernels read it, and a pitched result on its way back.  Every entry that takes an image goes through these two. ----
+// h rows of row_bytes bytes at src, stride_bytes apart.  in_place: the caller's pointer and stride — the site says which memory kinds it reads where they lie with
+// dv_in_place_device(mem) or dv_in_place_device_or_pinned(mem) (dv_mem.h; DESIGN.md lists every entry's policy).  Otherwise `own` grows to h rows of
+// align_up(row_bytes, 16) bytes (+ slack, for a kernel's aligned over-reads) and takes the rows in one host-to-device copy on s
+struct DvRows { const uint8_t* p; int pitch; };
+static inline int dv_stage_rows(dv_ctx* ctx, DevBuf& own, const void* src, size_t row_bytes, int h, size_t stride_bytes, bool in_place, hipStream_t s, DvRows* out, size_t slack = 0) {
+    if (in_place) { *out = DvRows{ (const uint8_t*)src, (int)stride_bytes }; return 0; }
+    const int pitch = align_up((int)row_bytes, 16);
+    DV_CHECK(own.ensure((size_t)pitch * h + slack));
+    DV_CHECK(hipMemcpy2DAsync(own.p, pitch, src, stride_bytes, row_bytes, h, hipMemcpyHostToDevice, s));
+    *out = DvRows{ (const uint8_t*)own.p, pitch };
+    return 0;
+}
+// h rows of row_bytes bytes of a pitched device buffer to the caller's rows (memory kind mem: device-to-device or device-to-host) on s
+static inline int dv_unstage_rows(dv_ctx* ctx, void* dst, size_t dst_stride, const void* src, size_t pitch, size_t row_bytes, int h, int mem, hipStream_t s) {
+    DV_CHECK(hipMemcpy2DAsync(dst, dst_stride, src, pitch, row_bytes, h, mem == DV_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
 StageTimer* dv_timer_for(dv_ctx* ctx, const char* name);
 struct StageScope {
     dv_ctx* c; StageTimer* t = nullptr; hipStream_t s; size_t slot = 0;
@@ -311,7 +333,7 @@ struct HostScope {
     ~HostScope() { if (t) { const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); std::lock_guard<std::mutex> lk(c->timer_mu); t->total_ms += ms; t->count++; } }
 };
 void dv_harvest_timers(dv_ctx* ctx, hipStream_t synced);      // harvests the timers recorded on `synced` (must be idle)
-// ---- host helpers of dvins_api.hip that the tracker entries (front_track.hip) share with the operator-level entries ----
+// ---- host helpers of dv_context.hip and pyr_plan.hip that the tracker entries (front_track.hip) share with the operator-level entries (dv_ops.hip) ----
 int dv_ensure_hw(dv_ctx* ctx, int radius);         // the disc half widths of `radius` in hw_buf
 size_t dv_unmask_tab_bytes(size_t n);             // front_track.hip: the head of unmask_pinned that holds the tables of n rectangles
 void circle_half_widths(int radius, std::vector<uint8_t>& hw);      // hw[0..radius] of cv::circle's midpoint rasteriser (drawing.cpp Circle(), fill = true)
@@ -326,3 +348,5 @@ struct CudaPyrPlan { int levels; DvPyrJob down[DV_MAX_LEVELS - 1]; };
 int dv_plan_cuda_pyramids(dv_ctx* ctx, PyrSet& C0, PyrSet* C1, const DvPyr& a0, const DvPyr* b0, int w, int h, int max_level, CudaPyrPlan& P);
 void dv_launch_cuda_pyramids(const CudaPyrPlan& P, hipStream_t s);
 int dv_build_cuda_pyramids(dv_ctx* ctx, PyrSet& C0, PyrSet* C1, const DvPyr& a0, const DvPyr* b0, int w, int h, int max_level);
+// the pyramids of one image (P1, img1 == nullptr) or of a pair in shared launches on ctx->stream: the operator-level entries' form (no maps)
+int dv_build_pyramids(dv_ctx* ctx, PyrSet& P0, PyrSet* P1, const uint8_t* img0, const uint8_t* img1, int w, int h, int stride, int mem, int max_level);

@@ -76,10 +76,10 @@ static int front_unmask_tables(dv_ctx* ctx, const FrontPlan& P, hipStream_t s, i
     const int w = ctx->cfg.width, h = ctx->cfg.height, mp = align_up(w, 16);
     const uint32_t* kimg = U.key_img; int kstride = U.key_stride;
     DvStackSrc S{};
-    if (U.form == dv_ctx::UNMASK_KEYS && U.key_mem == DV_MEM_HOST) {
-        DV_CHECK(ctx->unmask_src_buf.ensure((size_t)4 * w * h));
-        DV_CHECK(hipMemcpy2DAsync(ctx->unmask_src_buf.p, (size_t)4 * w, kimg, (size_t)kstride, (size_t)4 * w, h, hipMemcpyHostToDevice, s));
-        kimg = (const uint32_t*)ctx->unmask_src_buf.p; kstride = 4 * w;
+    if (U.form == dv_ctx::UNMASK_KEYS) {
+        DvRows k;
+        if (dv_stage_rows(ctx, ctx->unmask_src_buf, kimg, (size_t)4 * w, h, kstride, dv_in_place_device_or_pinned(U.key_mem), s, &k)) return -1;
+        kimg = (const uint32_t*)k.p; kstride = k.pitch;
     }
     if (U.form == dv_ctx::UNMASK_PLANES && dv_stack_resolve(ctx, U.stack, ctx->unmask_src_buf, s, &S)) return -1;
     uint8_t* own = (uint8_t*)ctx->mask_buf.p;
@@ -111,8 +111,8 @@ static int front_plan(dv_ctx* ctx, const dv_track_job& j, hipStream_t s, FrontPl
     const bool stereo = c.stereo && j.gray1;
     const int mode = j.mode;
     int mem = j.mem;
-    if ((mem & 0xff) == DV_MEM_PINNED) mem = (mem & ~0xff) | DV_MEM_DEVICE;      // pinned + mapped host memory is device-addressable: the kernels read it in place
-    if ((mem & 0xff) != DV_MEM_HOST && (mem & 0xff) != DV_MEM_DEVICE) DV_FAIL("dv_track_stereo: unknown memory kind");
+    if (!dv_mem_known(mem & 0xff)) DV_FAIL("dv_track_stereo: unknown memory kind");
+    if ((mem & 0xff) == DV_MEM_PINNED) mem = (mem & ~0xff) | DV_MEM_DEVICE;      // pinned + mapped host memory is device-addressable: the kernels read it in place ("device or pinned")
     if (ctx->undist[0]) {      // cfg::is_undistort_input.  (The size check cannot fire today — dv_set_undistort_maps / dv_undistort_setup take the config's size only — and is kept, once, because include/dvins.h promises it)
         if (w != ctx->undist_w || h != ctx->undist_h) DV_FAIL("dv_track_stereo: undistortion maps were installed for another image size");
         if (stereo && !ctx->undist[1]) DV_FAIL("dv_track_stereo: undistortion maps installed for camera 0 but not for camera 1");
@@ -162,18 +162,9 @@ static int front_plan(dv_ctx* ctx, const dv_track_job& j, hipStream_t s, FrontPl
     q.w = w; q.h = h; q.quality = 0.01; q.min_dist = (double)c.min_dist; q.max_n_host = 0; q.n_feat = tr.n_feat; q.max_cnt = c.max_cnt; q.min_new = min_new;
     q.out_xy = nullptr; q.n_out = nullptr; q.tr = tr; q.has_tr = 1; q.err_flag = ctx->err_flag; q.rule = gftt_rule;
     // the mask: device-addressable jobs are read in place, host jobs staged into the ctx's own mask_buf on s.  The mask of a BGR job has one channel: rows of w bytes
-    const uint8_t* mask_dev = nullptr; int mask_pitch = 0;
-    if (j.mask) {
-        const int mstride = (mem & DV_FMT_BGR) ? w : job_stride(j, w);
-        if (P.dev) { mask_dev = j.mask; mask_pitch = mstride; }
-        else {
-            mask_pitch = align_up(w, 16);
-            DV_CHECK(ctx->mask_buf.ensure((size_t)mask_pitch * h));
-            DV_CHECK(hipMemcpy2DAsync(ctx->mask_buf.p, mask_pitch, j.mask, mstride, w, h, hipMemcpyHostToDevice, s));
-            mask_dev = (const uint8_t*)ctx->mask_buf.p;
-        }
-    }
-    if (front_plan_mask(ctx, mode, mask_dev, mask_pitch, P)) return -1;
+    DvRows mk{};
+    if (j.mask && dv_stage_rows(ctx, ctx->mask_buf, j.mask, w, h, (mem & DV_FMT_BGR) ? w : job_stride(j, w), P.dev, s, &mk)) return -1;
+    if (front_plan_mask(ctx, mode, mk.p, mk.pitch, P)) return -1;
     // the rows, their count and the device error flags go straight into the pinned buffer (three copy dispatches behind the kernel before: ~20 us of the
     // tracker's latency per frame)
     DvFinalizeJob& f = P.fin; f = DvFinalizeJob{};
@@ -300,7 +291,7 @@ int dv_track_unmask_static_keys(dv_ctx* ctx, const dv_inst_det* dets, int n_dets
     if (n_static <= 0 || n_dets <= 0) return 0;
     if (!dets || !static_ids) DV_FAIL("dv_track_unmask_static_keys: null argument");
     if (!key_image) DV_FAIL("dv_track_unmask_static_keys: null key image");
-    if (mem != DV_MEM_HOST && mem != DV_MEM_DEVICE && mem != DV_MEM_PINNED) DV_FAIL("dv_track_unmask_static_keys: unknown memory kind");
+    if (!dv_mem_known(mem)) DV_FAIL("dv_track_unmask_static_keys: unknown memory kind");
     if (stride_bytes == 0) stride_bytes = 4 * ctx->cfg.width;
     if (stride_bytes < 4 * ctx->cfg.width || (stride_bytes & 3)) DV_FAIL("dv_track_unmask_static_keys: bad stride");
     if (ctx->pending) DV_FAIL("dv_track_unmask_static_keys: call it before dv_track_stereo_enqueue of the frame it belongs to");

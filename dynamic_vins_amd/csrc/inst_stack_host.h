@@ -4,7 +4,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
-#include "../../include/dvins.h"
+#include "dv_mem.h"
 #include "pix_src.h"
 
 // the membership rule of a stack element: written once, in pix_src.h
@@ -40,7 +40,7 @@ static inline const char* dv_stack_check(const dv_mask_stack* s, int w, int h, D
     if (!s || !s->data) return "null stack";
     if (s->n_planes < 1 || s->n_planes > DV_STACK_MAX_PLANES) return "1..64 planes";
     if (s->kind != DV_STACK_U8 && s->kind != DV_STACK_F32) return "unknown element kind";
-    if (s->mem != DV_MEM_HOST && s->mem != DV_MEM_DEVICE && s->mem != DV_MEM_PINNED) return "unknown memory kind";
+    if (!dv_mem_known(s->mem)) return "unknown memory kind";
     const int es = s->kind == DV_STACK_F32 ? 4 : 1;
     const long long row = s->row_stride ? (long long)s->row_stride : (long long)w * es;
     if (s->row_stride < 0 || row < (long long)w * es || row > 0x7fffffff) return "row stride below the row";

@@ -377,10 +377,10 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
         DvRoiMaskJob* h_mj = (DvRoiMaskJob*)((uint8_t*)T.arena_pinned + mj_off); int roi_P = 0, roi_Hm = 0;
         const uint32_t* kimg0 = ms ? ms->key_img : nullptr; int kstride0 = ms ? ms->key_stride : 0;
         DvStackSrc psrc{};
-        if (ms && na > 0 && ms->key_img && ms->key_mem == DV_MEM_HOST) {
-            DV_CHECK(T.src_buf.ensure((size_t)W * H * 4));
-            DV_CHECK(hipMemcpy2DAsync(T.src_buf.p, (size_t)W * 4, ms->key_img, (size_t)ms->key_stride, (size_t)W * 4, H, hipMemcpyHostToDevice, s));
-            kimg0 = (const uint32_t*)T.src_buf.p; kstride0 = 4 * W;
+        if (ms && na > 0 && ms->key_img) {
+            DvRows k;
+            if (dv_stage_rows(ctx, T.src_buf, ms->key_img, (size_t)W * 4, H, ms->key_stride, dv_in_place_device_or_pinned(ms->key_mem), s, &k)) return -1;
+            kimg0 = (const uint32_t*)k.p; kstride0 = k.pitch;
         }
         if (ms && na > 0 && !ms->key_img && dv_stack_resolve(ctx, *ms->st, T.src_buf, s, &psrc)) return -1;
         int ero_W = 0, ero_H = 0, nj = 0;
@@ -466,12 +466,9 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
                 // the reference starts a thread for this (dynamic_tracker.cpp:378): a side stream behind the mask + table uploads; the objects' tracking goes on meanwhile
                 DV_CHECK(hipEventRecord(T.ev_xin, s));
                 DV_CHECK(hipStreamWaitEvent(T.xstream, T.ev_xin, 0));
-                const float* dmap = T.disp_user; int dpitch = T.disp_stride / 4;
-                if (T.disp_mem != DV_MEM_DEVICE) {
-                    DV_CHECK(T.disp_buf.ensure((size_t)W * H * 4));
-                    DV_CHECK(hipMemcpy2DAsync(T.disp_buf.p, (size_t)W * 4, T.disp_user, (size_t)T.disp_stride, (size_t)W * 4, H, hipMemcpyHostToDevice, T.xstream));
-                    dmap = (const float*)T.disp_buf.p; dpitch = W;
-                }
+                DvRows dm;
+                if (dv_stage_rows(ctx, T.disp_buf, T.disp_user, (size_t)W * 4, H, T.disp_stride, dv_in_place_device(T.disp_mem), T.xstream, &dm)) return -1;
+                const float* dmap = (const float*)dm.p; const int dpitch = dm.pitch / 4;
                 if (T.xp_pool.bytes < dv_extra_points_scratch_bytes(n_xp)) { DV_CHECK(hipStreamSynchronize(T.xstream)); DV_CHECK(T.xp_pool.ensure(dv_extra_points_scratch_bytes(std::max(8, 2 * n_xp)))); }
                 DvExtraArgs xa{ dmap, dpitch, W, H, (float)ctx->cfg.cam0.fx, (float)ctx->cfg.cam0.fy, (float)ctx->cfg.cam0.cx, (float)ctx->cfg.cam0.cy, (float)T.disp_baseline, T.xerr_flag, 0, (uint8_t*)T.xp_pool.p };
                 StageScope scx(ctx, "inst_extra_points", T.xstream);
@@ -505,13 +502,9 @@ static int inst_track_enqueue_impl(dv_ctx* ctx, double t, const dv_inst_det* det
         // ---- stage D ----
         if (stereo) dv_launch_lk_track_multi((const DvLkJob*)T.jobs.p + n_temporal, na, T.max_cnt, ctx->cfg.flow_back, 0.5f, s);
         if (stereo && T.keys_next && na > 0) {          // cfg::dataset == kViode: the segmentation-key test of TrackRightByPad (instance_feature.cpp:263-268)
-            const uint32_t* kimg = T.keys_user; int kpitch = T.keys_stride / 4;
-            if (T.keys_mem != DV_MEM_DEVICE && T.keys_mem != DV_MEM_PINNED) {
-                DV_CHECK(T.keys_buf.ensure((size_t)W * H * 4));
-                DV_CHECK(hipMemcpy2DAsync(T.keys_buf.p, (size_t)W * 4, T.keys_user, (size_t)T.keys_stride, (size_t)W * 4, H, hipMemcpyHostToDevice, s));
-                kimg = (const uint32_t*)T.keys_buf.p; kpitch = W;
-            }
-            dv_launch_right_key_check((const DvLkJob*)T.jobs.p + n_temporal, na, kimg, kpitch, W, H, s);
+            DvRows k;
+            if (dv_stage_rows(ctx, T.keys_buf, T.keys_user, (size_t)W * 4, H, T.keys_stride, dv_in_place_device_or_pinned(T.keys_mem), s, &k)) return -1;
+            dv_launch_right_key_check((const DvLkJob*)T.jobs.p + n_temporal, na, (const uint32_t*)k.p, k.pitch / 4, W, H, s);
         }
         // ---- stage E: UndistortedPointsWithAddOffset + PtsVelocity + RightUndistortedPts + RightPtsVelocity + PostProcess -> rows ----
         if (na > 0) dv_launch_finalize_multi((const DvFinalizeJob*)((const uint8_t*)T.arena.p + fj_off), na, T.max_cnt, s);
@@ -548,7 +541,7 @@ int dv_inst_track_enqueue(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_
 int dv_inst_track_enqueue_keys(dv_ctx* ctx, double t, const dv_inst_det* dets, int n_dets, const uint32_t* key_image, int stride_bytes, int mem, const dv_box3d* boxes3d, int n_boxes3d) {
     if (!ctx) return -1;
     if (!key_image) DV_FAIL("dv_inst_track_enqueue_keys: null key image");
-    if (mem != DV_MEM_HOST && mem != DV_MEM_DEVICE && mem != DV_MEM_PINNED) DV_FAIL("dv_inst_track_enqueue_keys: unknown memory kind");
+    if (!dv_mem_known(mem)) DV_FAIL("dv_inst_track_enqueue_keys: unknown memory kind");
     if (stride_bytes == 0) stride_bytes = 4 * ctx->cfg.width;
     if (stride_bytes < 4 * ctx->cfg.width || (stride_bytes & 3)) DV_FAIL("dv_inst_track_enqueue_keys: bad stride");
     for (int i = 0; i < n_dets && dets; ++i) {          // (checked again by the common part; here for the entry's own message)
@@ -609,12 +602,9 @@ int dv_extra_points(dv_ctx* ctx, const uint8_t* mask, int x, int y, int w, int h
     const int mp = align_up(w, 16);
     DV_CHECK(ctx->s0.ensure((size_t)mp * h));
     DV_CHECK(hipMemcpy2DAsync(ctx->s0.p, mp, mask, w, w, h, hipMemcpyHostToDevice, s));
-    const float* dmap = disp; int dpitch = stride_bytes / 4;
-    if (mem != DV_MEM_DEVICE) {
-        DV_CHECK(ctx->s1.ensure((size_t)W * H * 4));
-        DV_CHECK(hipMemcpy2DAsync(ctx->s1.p, (size_t)W * 4, disp, (size_t)stride_bytes, (size_t)W * 4, H, hipMemcpyHostToDevice, s));
-        dmap = (const float*)ctx->s1.p; dpitch = W;
-    }
+    DvRows dm;
+    if (dv_stage_rows(ctx, ctx->s1, disp, (size_t)W * 4, H, stride_bytes, dv_in_place_device(mem), s, &dm)) return -1;
+    const float* dmap = (const float*)dm.p; const int dpitch = dm.pitch / 4;
     const size_t out_bytes = 64 + (size_t)3 * DV_XP_CAP * sizeof(double);
     DV_CHECK(ctx->s2.ensure(out_bytes + sizeof(DvExtraJob) + 256));
     uint8_t* ob = (uint8_t*)ctx->s2.p;

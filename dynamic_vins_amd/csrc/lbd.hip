@@ -171,16 +171,6 @@ static int lbd_ensure(dv_ctx* ctx, LbdSet& b, int w, int h) {
     return 0;
 }
 
-// a caller's w x h bytes as the kernels read them: device and pinned memory in place, pageable memory through the set's own buffer
-static int lbd_stage_bytes(dv_ctx* ctx, DevBuf& own, const uint8_t* src, int stride, int w, int h, int mem, const uint8_t** out, int* pitch) {
-    if (mem != DV_MEM_HOST) { *out = src; *pitch = stride; return 0; }
-    const int p = align_up(w, 16);
-    DV_CHECK(own.ensure((size_t)p * h));
-    DV_CHECK(hipMemcpy2DAsync(own.p, p, src, stride, w, h, hipMemcpyHostToDevice, ctx->stream));
-    *out = (const uint8_t*)own.p; *pitch = p;
-    return 0;
-}
-
 extern "C" {
 
 int dv_lbd_check(int w, int h, int stride, const dv_key_line* lines, const int32_t* num_pixels, int n, int lines_mem, const uint8_t* mask, int mask_stride) {
@@ -201,7 +191,7 @@ int dv_lbd_describe_enqueue(dv_ctx* ctx, int cam, const uint8_t* image, int stri
     if (!ctx) return -1;
     if (cam != 0 && cam != 1) DV_FAIL("dv_lbd_describe_enqueue: cam must be 0 or 1");
     if (!image) DV_FAIL("dv_lbd_describe_enqueue: null image");
-    if (!dv_lbd_mem_ok(image_mem)) DV_FAIL("dv_lbd_describe_enqueue: unknown memory kind");
+    if (!dv_mem_known(image_mem)) DV_FAIL("dv_lbd_describe_enqueue: unknown memory kind");
     if (const char* why = dv_lbd_check_host(w, h, stride, lines, num_pixels, n, lines_mem, mask, mask_stride)) DV_FAIL(std::string("dv_lbd_describe_enqueue: ") + why);
     if (!(min_length == min_length)) DV_FAIL("dv_lbd_describe_enqueue: min_length is NaN");
     if (!ctx->lbd) ctx->lbd = new LbdStage();
@@ -224,18 +214,18 @@ int dv_lbd_describe_enqueue(dv_ctx* ctx, int cam, const uint8_t* image, int stri
     }
     DvLbdLine* pl = (DvLbdLine*)b.pinned_in;
     for (int i = 0; i < n; ++i) pl[i] = dv_lbd_line(hk[i], hn ? hn[i] : dv_lbd_npix(hk[i].sx, hk[i].sy, hk[i].ex, hk[i].ey));
-    const uint8_t *d_img = nullptr, *d_mask = nullptr; int pitch = 0, mpitch = 0;
-    if (lbd_stage_bytes(ctx, b.img, image, stride, w, h, image_mem, &d_img, &pitch)) return -1;
-    if (mask && lbd_stage_bytes(ctx, b.mask, mask, mask_stride, w, h, image_mem, &d_mask, &mpitch)) return -1;
+    DvRows im, mk{};          // device and pinned memory in place, pageable memory through the set's own buffers
+    if (dv_stage_rows(ctx, b.img, image, w, h, stride, dv_in_place_device_or_pinned(image_mem), s, &im)) return -1;
+    if (mask && dv_stage_rows(ctx, b.mask, mask, w, h, mask_stride, dv_in_place_device_or_pinned(image_mem), s, &mk)) return -1;
     int16_t* dx = (int16_t*)b.grad.p; int16_t* dy = dx + (size_t)w * h;
     hipError_t e;
     {
         StageScope sc_t(ctx, "lbd_describe");
         e = n > 0 ? dv_copy_async(b.lines.p, b.pinned_in, (size_t)n * sizeof(DvLbdLine), s) : hipSuccess;
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(lbd_grad_kernel, dim3((w + GT_W - 1) / GT_W, (h + GT_H - 1) / GT_H), dim3(256), 0, s, d_img, pitch, w, h, dx, dy);
+            hipLaunchKernelGGL(lbd_grad_kernel, dim3((w + GT_W - 1) / GT_W, (h + GT_H - 1) / GT_H), dim3(256), 0, s, im.p, im.pitch, w, h, dx, dy);
             if (n > 0) hipLaunchKernelGGL(lbd_describe_kernel, dim3(n), dim3(64), 0, s, dx, dy, w, h, (const DvLbdLine*)b.lines.p, n, S.tabs, (float*)b.fdesc.p, (uint8_t*)b.desc.p);
-            hipLaunchKernelGGL(lbd_select_kernel, dim3(1), dim3(SEL_THREADS), 0, s, (const DvLbdLine*)b.lines.p, (const uint32_t*)b.desc.p, n, min_length, d_mask, mpitch, w, h,
+            hipLaunchKernelGGL(lbd_select_kernel, dim3(1), dim3(SEL_THREADS), 0, s, (const DvLbdLine*)b.lines.p, (const uint32_t*)b.desc.p, n, min_length, mk.p, mk.pitch, w, h,
                                (dv_key_line*)b.o_line.p, (uint32_t*)b.o_desc.p, (int*)b.o_hdr.p);
             e = hipGetLastError();
         }

@@ -6,7 +6,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
-#include "../../include/dvins.h"
+#include "dv_mem.h"
 
 #ifdef __HIPCC__
 #define DV_LBD_HD __host__ __device__
@@ -141,7 +141,6 @@ static inline DvLbdLine dv_lbd_line(const dv_key_line& k, int npix) {
     return L;
 }
 
-static inline bool dv_lbd_mem_ok(int mem) { return mem == DV_MEM_HOST || mem == DV_MEM_DEVICE || mem == DV_MEM_PINNED; }
 // the reason the VALUES of n lines are refused, or nullptr.  num_pixels may be NULL (the library's rule)
 static inline const char* dv_lbd_values_check_host(int w, int h, const dv_key_line* lines, const int32_t* num_pixels, int n) {
     for (int i = 0; i < n; ++i) {
@@ -155,7 +154,7 @@ static inline const char* dv_lbd_values_check_host(int w, int h, const dv_key_li
 }
 // the reason a frame is refused, or nullptr.  Lines in device memory cannot be read here: their values are checked by the enqueue, which fetches them anyway
 static inline const char* dv_lbd_check_host(int w, int h, int stride, const dv_key_line* lines, const int32_t* num_pixels, int n, int lines_mem, const uint8_t* mask, int mask_stride) {
-    if (!dv_lbd_mem_ok(lines_mem)) return "unknown memory kind";
+    if (!dv_mem_known(lines_mem)) return "unknown memory kind";
     if (w < 1 || h < 1) return "empty image";
     if (w > DV_LBD_MAX_DIM || h > DV_LBD_MAX_DIM) return "image wider or higher than 32767 (the descriptor's coordinates are 16-bit)";
     if (stride < w) return "stride below the width";

@@ -7,7 +7,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
-#include "../../include/dvins.h"
+#include "dv_mem.h"
 
 #ifdef __HIPCC__
 #define DV_LT_HD __host__ __device__
@@ -20,7 +20,6 @@ constexpr int DV_LT_QUOTA = 35;                 // 35 - h_line, 35 - v_line (lin
 constexpr int DV_LT_DESC_WORDS = DV_LINE_DESC_BYTES / 4;
 constexpr uint32_t DV_LT_NO_ID = 0xFFFFFFFFu;   // line_ids.push_back(-1) into a vector<unsigned int> (line_detector.cpp:237,248)
 
-static inline bool dv_lt_mem_ok(int mem) { return mem == DV_MEM_HOST || mem == DV_MEM_DEVICE || mem == DV_MEM_PINNED; }
 // the reason one image's lines are refused, or nullptr (n = 0 is an ordinary frame: the pointers are not looked at)
 static inline const char* dv_line_side_check_host(const dv_key_line* lines, const uint8_t* desc, int n) {
     if (n < 0) return "negative line count";
@@ -32,7 +31,7 @@ static inline const char* dv_line_side_check_host(const dv_key_line* lines, cons
 }
 // the reason a frame is refused, or nullptr
 static inline const char* dv_line_frame_check_host(const dv_key_line* left, const uint8_t* left_desc, int n_left, const dv_key_line* right, const uint8_t* right_desc, int n_right, int mem) {
-    if (!dv_lt_mem_ok(mem)) return "unknown memory kind";
+    if (!dv_mem_known(mem)) return "unknown memory kind";
     if (const char* why = dv_line_side_check_host(left, left_desc, n_left)) return why;
     if (!right && !right_desc && n_right == 0) return nullptr;      // no right image
     return dv_line_side_check_host(right, right_desc, n_right);

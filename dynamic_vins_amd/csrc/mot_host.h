@@ -7,7 +7,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
-#include "../../include/dvins.h"
+#include "dv_mem.h"
 
 #ifdef __HIPCC__
 #define DV_MOT_HD __host__ __device__
@@ -32,7 +32,7 @@ static inline const char* dv_mot_check_host(const dv_mot_params* p) {
 // the reason a frame is refused, or nullptr (n = 0 is the reference's "no detections: the tracker is not called", front_end/dynamic_tracker.cpp:795-796)
 static inline const char* dv_mot_frame_check_host(const float* rects, const float* feats, int n, int mem) {
     if (n < 0 || n > DV_STACK_MAX_PLANES) return "0..64 detections";
-    if (mem != DV_MEM_HOST && mem != DV_MEM_DEVICE && mem != DV_MEM_PINNED) return "unknown memory kind";
+    if (!dv_mem_known(mem)) return "unknown memory kind";
     if (n == 0) return nullptr;
     if (!rects || !feats) return "null rectangles or embeddings";
     if (((uintptr_t)rects | (uintptr_t)feats) & 3) return "rectangles and embeddings must be 4-byte aligned";

@@ -264,13 +264,14 @@ int dv_reid_extract_enqueue(dv_ctx* ctx, const uint8_t* bgr, int stride, const f
     DV_CHECK(hipSetDevice(ctx->cfg.device));
     hipStream_t s = ctx->stream;
     CropArgs ca{};
-    if (mem == DV_MEM_HOST) {
-        const int sp = align_up(3 * W, 16);
-        DV_CHECK(R.img.ensure((size_t)sp * H)); DV_CHECK(R.rects.ensure(MC * 16));
-        DV_CHECK(hipMemcpy2DAsync(R.img.p, sp, bgr, stride, (size_t)3 * W, H, hipMemcpyHostToDevice, s));
+    DvRows im;          // the rectangles travel with the image: both in place, or both copied
+    if (dv_stage_rows(ctx, R.img, bgr, (size_t)3 * W, H, stride, dv_in_place_device_or_pinned(mem), s, &im)) return -1;
+    ca.bgr = im.p; ca.stride = im.pitch; ca.rects = rects_xywh;
+    if (!dv_in_place_device_or_pinned(mem)) {
+        DV_CHECK(R.rects.ensure(MC * 16));
         DV_CHECK(hipMemcpyAsync(R.rects.p, rects_xywh, (size_t)n * 16, hipMemcpyHostToDevice, s));
-        ca.bgr = (const uint8_t*)R.img.p; ca.stride = sp; ca.rects = (const float*)R.rects.p;
-    } else { ca.bgr = bgr; ca.stride = stride; ca.rects = rects_xywh; }
+        ca.rects = (const float*)R.rects.p;
+    }
     ca.img_w = W; ca.img_h = H; ca.lut = (const float*)R.lut.p; ca.out = (float*)R.input.p; ca.flags = (int*)R.flags.p; ca.in_w = R.in_w; ca.in_h = R.in_h;
     const float* wts = (const float*)R.weights.p; const float* bn = (const float*)R.bn.p;
     float* A = (float*)R.act[0].p; float* B = (float*)R.act[1].p; float* C = (float*)R.act[2].p;

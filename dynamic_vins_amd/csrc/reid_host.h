@@ -7,7 +7,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
-#include "../../include/dvins.h"
+#include "dv_mem.h"
 
 #ifdef __HIPCC__
 #define DV_REID_HD __host__ __device__
@@ -63,7 +63,7 @@ static inline const char* dv_reid_check_host(size_t n_floats, int in_w, int in_h
 // the reason a frame is refused at the enqueue, or nullptr (n = 0: Extractor::extract returns an empty tensor, mot/extractor.cpp:32-34)
 static inline const char* dv_reid_frame_check_host(const uint8_t* bgr, int img_w, int stride, const float* rects, int n, int mem) {
     if (n < 0 || n > DV_REID_MAX_CROPS) return "0..64 rectangles";
-    if (mem != DV_MEM_HOST && mem != DV_MEM_DEVICE && mem != DV_MEM_PINNED) return "unknown memory kind";
+    if (!dv_mem_known(mem)) return "unknown memory kind";
     if (n == 0) return nullptr;
     if (!bgr || !rects) return "null image or rectangles";
     if (stride < 3 * img_w) return "row stride below 3 * width";

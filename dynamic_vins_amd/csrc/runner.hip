@@ -667,7 +667,7 @@ int dv_runner_set_viode(dv_runner* R, int seq, const dv_seq_viode* v) {
     if (!dv_viode_frame_enqueue || !dv_viode_frame_collect || !dv_track_unmask_static_keys || !dv_inst_track_enqueue_keys) return set_err(R, "dv_runner_set_viode: the label-image entries are not linked into this build");
     if (!s.ctx->inst) return set_err(R, "dv_runner_set_viode: call dv_inst_config on the sequence's context first");
     if (!v->seg0 || !v->dyn_keys || v->nkeys < 1 || v->nkeys > 64) return set_err(R, "dv_runner_set_viode: label images and 1..64 dynamic keys are needed");
-    if (v->mem != DV_MEM_HOST && v->mem != DV_MEM_DEVICE && v->mem != DV_MEM_PINNED) return set_err(R, "dv_runner_set_viode: unknown memory kind of the label images");
+    if (!dv_mem_known(v->mem)) return set_err(R, "dv_runner_set_viode: unknown memory kind of the label images");
     if (s.in.mem != DV_MEM_DEVICE && s.in.mem != DV_MEM_PINNED) return set_err(R, "dv_runner_set_viode: the frames must be DV_MEM_DEVICE or DV_MEM_PINNED (the inverse mask stays on the device and travels with them)");
     if (s.stride != s.w) return set_err(R, "dv_runner_set_viode: the frames' row stride must equal the width (the inverse mask is tightly packed)");
     dv_seq_dynamic d{};          // what the stage does not produce per frame travels as in a dynamic sequence (track_input)
@@ -687,7 +687,7 @@ int dv_runner_set_inst_stack(dv_runner* R, int seq, const dv_seq_stack* q) {
     if (!s.ctx->inst) return set_err(R, "dv_runner_set_inst_stack: call dv_inst_config on the sequence's context first");
     if (!q->stack || !q->n_planes || !q->track_id) return set_err(R, "dv_runner_set_inst_stack: per frame a stack, its number of planes and the planes' track ids are needed");
     if (q->kind != DV_STACK_U8 && q->kind != DV_STACK_F32) return set_err(R, "dv_runner_set_inst_stack: unknown element kind");
-    if (q->mem != DV_MEM_HOST && q->mem != DV_MEM_DEVICE && q->mem != DV_MEM_PINNED) return set_err(R, "dv_runner_set_inst_stack: unknown memory kind of the stacks");
+    if (!dv_mem_known(q->mem)) return set_err(R, "dv_runner_set_inst_stack: unknown memory kind of the stacks");
     for (int k = 0; k < s.in.n_frames; ++k)
         if (!q->stack[k] || !q->track_id[k] || q->n_planes[k] < 1 || q->n_planes[k] > DV_STACK_MAX_PLANES) return set_err(R, "dv_runner_set_inst_stack: every frame needs a stack of 1..64 planes and their track ids (a frame without instances: one empty plane)");
     if (s.in.mem != DV_MEM_DEVICE && s.in.mem != DV_MEM_PINNED) return set_err(R, "dv_runner_set_inst_stack: the frames must be DV_MEM_DEVICE or DV_MEM_PINNED (the inverse mask stays on the device and travels with them)");

@@ -4,7 +4,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
-#include "../../include/dvins.h"
+#include "dv_mem.h"
 
 constexpr int DV_SOLO_MAX_CHANNELS = 256, DV_SOLO_MAX_CLASSES = 128, DV_SOLO_MAX_GRID = 64, DV_SOLO_MAX_PIXELS = 1 << 20;
 
@@ -55,7 +55,7 @@ static inline const char* dv_solo_check_host(const dv_solo_outputs* o, const dv_
     if (o->n_levels < 1 || o->n_levels > DV_SOLO_MAX_LEVELS) return "1..5 levels";
     if (o->channels < 1 || o->channels > DV_SOLO_MAX_CHANNELS) return "1..256 channels";
     if (o->n_classes < 1 || o->n_classes > DV_SOLO_MAX_CLASSES) return "1..128 classes";
-    if (o->mem != DV_MEM_HOST && o->mem != DV_MEM_DEVICE && o->mem != DV_MEM_PINNED) return "unknown memory kind";
+    if (!dv_mem_known(o->mem)) return "unknown memory kind";
     for (int l = 0; l < o->n_levels; ++l) {
         if (o->grid[l] < 1 || o->grid[l] > DV_SOLO_MAX_GRID) return "level grid outside 1..64";
         if (!o->kernel[l] || !o->cate[l]) return "null level tensor";

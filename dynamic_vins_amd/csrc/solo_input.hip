@@ -97,7 +97,7 @@ int dv_solo_input_enqueue(dv_ctx* ctx, const uint8_t* bgr, int stride, int mem, 
     SoloInputArgs a{};
     if (const char* why = dv_solo_input_check_host(W, H, stride, par, &a.rx, &a.ry, &a.rw, &a.rh)) DV_FAIL(std::string("dv_solo_input_enqueue: ") + why);
     if (!bgr) DV_FAIL("dv_solo_input_enqueue: null image");
-    if (mem != DV_MEM_HOST && mem != DV_MEM_DEVICE && mem != DV_MEM_PINNED) DV_FAIL("dv_solo_input_enqueue: unknown memory kind");
+    if (!dv_mem_known(mem)) DV_FAIL("dv_solo_input_enqueue: unknown memory kind");
     if ((uintptr_t)dst_dev & 3) DV_FAIL("dv_solo_input_enqueue: dst_dev must be 4-byte aligned");
     if (ctx->solo_in && ctx->solo_in->pending) DV_FAIL("dv_solo_input_enqueue: previous frame not collected");
     DV_CHECK(hipSetDevice(ctx->cfg.device));
@@ -106,12 +106,9 @@ int dv_solo_input_enqueue(dv_ctx* ctx, const uint8_t* bgr, int stride, int mem, 
     SoloInputFrame& V = *ctx->solo_in;
     if (!V.ev) DV_CHECK(hipEventCreateWithFlags(&V.ev, hipEventDisableTiming));
 
-    if (mem == DV_MEM_HOST) {
-        const int sp = align_up(3 * W, 16);
-        DV_CHECK(V.staged.ensure((size_t)sp * H));
-        DV_CHECK(hipMemcpy2DAsync(V.staged.p, sp, bgr, stride, (size_t)3 * W, H, hipMemcpyHostToDevice, s));
-        a.bgr = (const uint8_t*)V.staged.p; a.stride = sp;
-    } else { a.bgr = bgr; a.stride = stride; }
+    DvRows im;
+    if (dv_stage_rows(ctx, V.staged, bgr, (size_t)3 * W, H, stride, dv_in_place_device_or_pinned(mem), s, &im)) return -1;
+    a.bgr = im.p; a.stride = im.pitch;
     a.iw = W; a.ih = H; a.mw = par->model_w; a.mh = par->model_h;
     a.sx = dv_solo_scale(W, a.rw); a.sy = dv_solo_scale(H, a.rh);
     for (int c = 0; c < 3; ++c) { a.mean[c] = par->mean[c]; a.sd[c] = par->std[c]; }

@@ -159,6 +159,33 @@ int dv_undistort_setup(dv_ctx* ctx, double alpha, dv_cam* new_cam0, dv_cam* new_
     return 0;
 }
 
+int dv_set_undistort_maps(dv_ctx* ctx, int cam, const int16_t* map1_xy, const uint16_t* map2, int w, int h) {
+    if (!ctx) return -1;
+    if (cam < 0 || cam > 1) DV_FAIL("dv_set_undistort_maps: cam must be 0 or 1");
+    DV_CHECK(hipSetDevice(ctx->cfg.device));
+    if (ctx->pending) DV_FAIL("dv_set_undistort_maps: a frame is in flight");
+    if (!map1_xy) {
+        ctx->undist[cam] = false; if (cam == 0) ctx->undist[1] = false;
+        if (ctx->cam_switched) {      // dv_undistort_setup re-parameterised the cameras for the undistorted frames: without the maps the original ones hold again
+            ctx->cfg.cam1 = ctx->cam_orig[1];
+            if (cam == 0) { ctx->cfg.cam0 = ctx->cam_orig[0]; ctx->cam_switched = false; }
+        }
+        return 0;
+    }
+    if (!map2 || w != ctx->cfg.width || h != ctx->cfg.height) DV_FAIL("dv_set_undistort_maps: maps must be width x height of the config");
+    if (cam == 1 && !ctx->undist[0]) DV_FAIL("dv_set_undistort_maps: install camera 0 first");
+    const size_t npx = (size_t)w * h;
+    DV_CHECK(ctx->undist_buf[cam].ensure(6 * npx));
+    DV_CHECK(hipMemcpyAsync(ctx->undist_buf[cam].p, map1_xy, 4 * npx, hipMemcpyHostToDevice, ctx->stream));
+    DV_CHECK(hipMemcpyAsync((uint8_t*)ctx->undist_buf[cam].p + 4 * npx, map2, 2 * npx, hipMemcpyHostToDevice, ctx->stream));
+    DV_CHECK(hipStreamSynchronize(ctx->stream));
+    ctx->undist[cam] = true; ctx->undist_w = w; ctx->undist_h = h;
+    if (ctx->cam_switched) {      // the caller's own maps replace those of dv_undistort_setup: its (newK, 0) no longer describes this camera's frames — the camera the ctx was created with holds again
+        if (cam == 0) ctx->cfg.cam0 = ctx->cam_orig[0]; else ctx->cfg.cam1 = ctx->cam_orig[1];
+    }
+    return 0;
+}
+
 int dv_get_undistort_maps(dv_ctx* ctx, int cam, int16_t* map1_xy, uint16_t* map2, int mem) {
     if (!ctx) return -1;
     if (cam < 0 || cam > 1 || !map1_xy || !map2 || (mem != DV_MEM_HOST && mem != DV_MEM_DEVICE)) DV_FAIL("dv_get_undistort_maps: bad argument");

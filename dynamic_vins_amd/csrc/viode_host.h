@@ -5,6 +5,11 @@
 #include <cstdint>
 #include "../../include/dvins.h"
 
+// what the box buffers of viode_mask_kernel and inst_stack_kernel hold before a frame: (row_min, row_max, col_min, col_max) = (max, -1, max, -1) for each of 64 boxes
+static inline void dv_boxes_init(int32_t* init /* [256] */) {
+    for (int k = 0; k < 64; ++k) { init[4 * k] = 0x7fffffff; init[4 * k + 1] = -1; init[4 * k + 2] = 0x7fffffff; init[4 * k + 3] = -1; }
+}
+
 // boxes[k] = row_min, row_max, col_min, col_max of keys[k]'s pixels (row_max < row_min: key absent).  One detection per key present, in ASCENDING key (the reference walks
 // an unordered_map; the object tracker visits its instances in ascending id either way): rect = cv::Rect(min_pt, max_pt), i.e. the max row / column excluded;
 // track_id = key, class 0, mask / points NULL.  A rectangle under min_size pixels on a side (and any empty one) is dropped — the rule dvins_node and

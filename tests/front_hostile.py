@@ -3,7 +3,7 @@ dense feature fields, tiny pyramids, wrong initial flows, aperture-problem and n
 conditions are asserted on the ORACLE ALONE (or on the numpy restatements below where the oracle's own behaviour is the question) and prove that a case reaches the
 branch it is named for.  If a seed fails a condition, take another seed, never loosen the condition (the pattern of tests/mot_cases.py).
 
-Device limits restated here (csrc/gftt.hip, csrc/dvins_api.hip dv_ensure_cand; documented beside dv_gftt in include/dvins.h)."""
+Device limits restated here (csrc/gftt.hip, csrc/dv_context.hip dv_ensure_cand; documented beside dv_gftt in include/dvins.h)."""
 import numpy as np
 
 from dynamic_vins_amd import synth

@@ -163,3 +163,26 @@ def test_hip_extra_points_empty_and_degenerate(gpu_ctx_factory, oracle):
     o = oracle.process_extra_points(oracle.detect_extra_points(mask, xy, far, CAM, BASE))
     d = ctx.extra_points(mask, xy, far, BASE, stage=0)
     assert np.array_equal(d, o.astype(np.float64))
+
+
+@pytest.mark.gpu
+def test_device_disparity_with_a_row_stride_equals_tight_host_memory(gpu_ctx_factory):
+    """dv_extra_points reads a DV_MEM_DEVICE disparity map in place under the caller's row stride.  A 33 x 17 map (a padded row, a ragged last 16-byte block): once from
+    tight host memory, once from device memory with rows of width + 5 floats (the padding holds NaN); both stages give bit-equal points."""
+    import ctypes as C
+    import torch
+    from dynamic_vins_amd.frontend import DV_MEM_DEVICE, make_cam
+    w, h, pad = 33, 17, 5
+    ctx = gpu_ctx_factory(width=w, height=h, max_cnt=50, min_dist=10, cam0=make_cam(*CAM, 0, 0, 0, 0), cam1=make_cam(*CAM, 0, 0, 0, 0))
+    rng = np.random.default_rng(4)
+    mask, xy = np.full((12, 24), 255, np.uint8), (4, 2)
+    depth = 8.0 + 0.02 * np.arange(w)[None, :] + rng.normal(0, 0.03, (h, w))
+    disp = (np.float32(CAM[0]) * np.float32(BASE) / depth.astype(np.float32)).astype(np.float32)
+    disp[5, 9] = np.nan; disp[7, 20] = 0.0
+    rows = np.full((h, w + pad), np.nan, np.float32); rows[:, :w] = disp
+    t = torch.from_numpy(rows).cuda()
+    for stage in (1, 0):
+        want = ctx.extra_points(mask, xy, disp, BASE, stage=stage)
+        out = np.zeros((4096, 3), np.float64); n = C.c_int(0)
+        ctx._check(ctx.lib.dv_extra_points(ctx.h, mask.ctypes.data, xy[0], xy[1], 24, 12, t.data_ptr(), rows.strides[0], DV_MEM_DEVICE, BASE, stage, out.ctypes.data, len(out), C.byref(n)))
+        assert len(want) > 10 and n.value == len(want) and np.array_equal(out[: n.value].view(np.uint64), want.view(np.uint64))

@@ -519,3 +519,76 @@ def test_viode_mask_bit_exact(gpu_ctx_factory, oracle):
     assert np.array_equal(inv, 255 - merge) and merge[40:90, 100:180].all() and not merge[0, 0]
     assert list(boxes[0]) == [40, 89, 100, 179] and list(boxes[2]) == [5, 8, 300, 332] and list(boxes[3]) == [-1, -1, -1, -1]
     assert kimg[45, 120] == 0 and kimg[130, 20] == 255 * 1000000 + 255 * 1000 * 255          # key = r*1e6 + g*1000*b (sic)
+
+
+OPERATOR_ENTRIES = ["pyr_down", "pyr_down_cuda", "min_eigen", "min_eigen_cuda", "gftt", "gftt_cuda", "erode", "circle_mask", "bgr2gray", "remap_gray", "remap_bgr"]
+
+
+@pytest.mark.parametrize("entry", OPERATOR_ENTRIES)
+def test_operator_entry_from_padded_device_memory_equals_tight_host_memory(ctx, entry):
+    """The operator entries take DV_MEM_DEVICE arrays in place, under the caller's row stride.  A 33 x 17 image (a padded row, a ragged last 16-byte block): once from
+    tight host memory, once from device memory with a row stride of width + 5 pixels (the padding holds 0xAB); the results are bit-equal."""
+    import ctypes as C
+    import torch
+    from dynamic_vins_amd.frontend import DV_MEM_DEVICE, _ptr
+    w, h, pad = 33, 17, 5
+    rng = np.random.default_rng(len(entry))
+    lib, H = ctx.lib, ctx.h
+
+    def padded(a):      # a's rows in device memory, width + 5 pixels apart -> (tensor, row stride in bytes)
+        rows = np.full((a.shape[0], a.shape[1] + pad) + a.shape[2:], 0xAB, a.dtype)
+        rows[:, : a.shape[1]] = a
+        return torch.from_numpy(rows).cuda(), rows.strides[0]
+
+    dev = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device="cuda")
+    img = _img(h, w, 5)
+    if entry.startswith("pyr_down"):
+        want = getattr(ctx, entry)(img)
+        t, stride = padded(img); out = dev(want.shape, torch.uint8)
+        ctx._check(getattr(lib, "dv_" + entry)(H, _ptr(t.data_ptr()), w, h, stride, _ptr(out.data_ptr()), DV_MEM_DEVICE))
+        got = out.cpu().numpy()
+    elif entry.startswith("min_eigen"):
+        rule = "cuda" if entry.endswith("cuda") else "cpu"
+        want = ctx.min_eigen(img, rule)
+        t, stride = padded(img); out = dev((h, w), torch.float32)
+        ctx._check(getattr(lib, "dv_" + entry)(H, _ptr(t.data_ptr()), w, h, stride, _ptr(out.data_ptr()), DV_MEM_DEVICE))
+        got, want = out.cpu().numpy().view(np.uint32), want.view(np.uint32)
+    elif entry.startswith("gftt"):
+        rule = "cuda" if entry.endswith("cuda") else "cpu"
+        mask = np.full((h, w), 255, np.uint8); mask[:, :4] = 0
+        want = ctx.gftt(img, 20, 0.01, 3, mask, rule)
+        assert len(want) > 3
+        t, stride = padded(img); m, _ = padded(mask); out = dev((1024, 2), torch.float32); n = C.c_int(0)
+        ctx._check(getattr(lib, "dv_" + entry)(H, _ptr(t.data_ptr()), _ptr(m.data_ptr()), w, h, stride, 20, 0.01, 3.0, _ptr(out.data_ptr()), C.byref(n), DV_MEM_DEVICE))
+        got, want = out.cpu().numpy()[: n.value].view(np.uint32), want.view(np.uint32)
+    elif entry == "erode":
+        mask = (rng.uniform(0, 1, (h, w)) > 0.05).astype(np.uint8) * 255
+        want = ctx.erode(mask, 3)
+        t, stride = padded(mask); out, _ = padded(np.zeros((h, w), np.uint8))      # a device destination has the source's stride
+        ctx._check(lib.dv_erode(H, _ptr(t.data_ptr()), w, h, stride, 3, _ptr(out.data_ptr()), DV_MEM_DEVICE))
+        got = out.cpu().numpy()
+        assert (got[:, w:] == 0xAB).all()
+        got = got[:, :w]
+    elif entry == "circle_mask":
+        mask = np.full((h, w), 255, np.uint8)
+        pts = rng.uniform([-3, -3], [w + 3, h + 3], (6, 2)).astype(np.float32)
+        want = ctx.circle_mask(mask, pts, 4)
+        t, stride = padded(mask); p = torch.from_numpy(pts).cuda()
+        ctx._check(lib.dv_circle_mask(H, _ptr(t.data_ptr()), w, h, stride, _ptr(p.data_ptr()), len(pts), 4, DV_MEM_DEVICE))
+        got = t.cpu().numpy()
+        assert (got[:, w:] == 0xAB).all()
+        got = got[:, :w]
+    elif entry == "bgr2gray":
+        bgr = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        want = ctx.bgr2gray(bgr)
+        t, stride = padded(bgr); out = dev((h, w), torch.uint8)
+        ctx._check(lib.dv_bgr2gray(H, _ptr(t.data_ptr()), w, h, stride, _ptr(out.data_ptr()), DV_MEM_DEVICE))
+        got = out.cpu().numpy()
+    else:
+        src = rng.integers(0, 256, (h, w, 3) if entry == "remap_bgr" else (h, w), dtype=np.uint8)
+        m1, m2 = _rand_maps(rng, w, h)
+        want = ctx.remap(src, m1, m2)
+        t, stride = padded(src); out = dev(src.shape, torch.uint8)
+        ctx._check(lib.dv_remap(H, _ptr(t.data_ptr()), w, h, stride, src.ndim == 3 and 3 or 1, m1.ctypes.data, m2.ctypes.data, _ptr(out.data_ptr()), DV_MEM_DEVICE))
+        got = out.cpu().numpy()
+    assert got.shape == want.shape and np.array_equal(got, want)
