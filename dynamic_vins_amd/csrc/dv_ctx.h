@@ -14,6 +14,10 @@
 #include <string>
 #include <vector>
 
+// DevBuf frees in its destructor, so whoever constructs a dv_ctx refers to hipFree.  The host-only builds of this header (tests/host: runner.hip as plain C++ on a stand-in
+// C ABI, linked without a HIP runtime) construct contexts whose buffers stay empty: the reference is weak so that they link; the library resolves it from the runtime it
+// is linked against, like every other HIP call
+extern "C" hipError_t hipFree(void* ptr) __attribute__((weak));
 struct DevBuf {
     void* p = nullptr; size_t bytes = 0;
     hipError_t ensure(size_t n) {
@@ -25,6 +29,28 @@ struct DevBuf {
         return e;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }      // (inst_track.hip emplaces a temporary Slot into its map)
+    ~DevBuf() { release(); }
+};
+// the pinned twin: host memory the device reads and writes in place
+struct PinBuf {
+    uint8_t* p = nullptr; size_t bytes = 0;
+    hipError_t ensure(size_t n) {
+        if (n <= bytes) return hipSuccess;
+        release();
+        void* q = nullptr;
+        hipError_t e = hipHostMalloc(&q, n, hipHostMallocDefault);
+        if (e == hipSuccess) { p = (uint8_t*)q; bytes = n; }
+        return e;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; bytes = 0; }
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() { release(); }
 };
 
 static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
@@ -180,14 +206,6 @@ int dv_inst_wait_before_next_frame(dv_ctx* ctx, hipStream_t s, bool consume = tr
 // frame); any other host stack is staged into own_buf, tightly packed, on s
 int dv_stack_resolve(dv_ctx* ctx, const dv_mask_stack& st, struct DevBuf& own_buf, hipStream_t s, DvStackSrc* out);
 void dv_stack_frame_done(dv_ctx* ctx);      // dv_track_stereo_collect: the shared staging ends with the frame
-void dv_viode_frame_release(dv_ctx* ctx);   // mask_frame.hip: the label-image stage's buffer sets (dv_destroy)
-void dv_inst_stack_frame_release(dv_ctx* ctx);      // mask_frame.hip: the mask-stack stage's buffer sets (dv_destroy)
-void dv_solo_head_release(dv_ctx* ctx);     // solo_head.hip: the head's buffers (dv_destroy)
-void dv_solo_input_release(dv_ctx* ctx);    // solo_input.hip: the input tensors and the staged frame (dv_destroy)
-void dv_mot_release(dv_ctx* ctx);           // mot.hip: the tracker's table and galleries (dv_destroy)
-void dv_reid_release(dv_ctx* ctx);          // reid.hip: the extractor's weights and activations (dv_destroy)
-void dv_line_track_release(dv_ctx* ctx);    // line_track.hip: the resident previous frame and the staging buffers (dv_destroy)
-void dv_lbd_release(dv_ctx* ctx);           // lbd.hip: both cams' gradient images, descriptors and staging buffers (dv_destroy)
 
 // One window sharded by landmark over several GPUs (be_shard.hip): the transport of the exchange vectors
 struct DvDist {
@@ -233,20 +251,20 @@ struct dv_ctx {
     std::vector<UnmaskRect> unmask; UnmaskSrc unmask_src; void* unmask_pinned = nullptr; size_t unmask_pinned_bytes = 0; DevBuf unmask_src_buf;
     // dv_viode_frame_enqueue / _collect: thread T1's per-frame stage (label images -> inverse merged mask, key images, boxes) on the ctx's stream.  Two buffer sets
     // used alternately: set[cur] belongs to the frame enqueued last; the key images of the frame before stay intact while its objects are tracked
-    struct ViodeFrame* viode = nullptr;      // (defined in mask_frame.hip, released by dv_destroy)
+    struct ViodeFrame* viode = nullptr;      // (defined in mask_frame.hip, deleted by dv_destroy)
     // dv_inst_stack_frame_enqueue / _collect: the same stage from a detector's mask stack (merged mask, inverse, boxes; a DV_MEM_HOST stack staged once per frame)
-    struct InstStackFrame* istack = nullptr;      // (defined in mask_frame.hip, released by dv_destroy)
-    // dv_solo_head_enqueue / _collect: the detector's head in front of that stage (network outputs -> mask stack; solo_head.hip, released by dv_solo_head_release)
+    struct InstStackFrame* istack = nullptr;      // (defined in mask_frame.hip, deleted by dv_destroy)
+    // dv_solo_head_enqueue / _collect: the detector's head in front of that stage (network outputs -> mask stack; solo_head.hip)
     struct SoloHeadFrame* solo = nullptr;
-    // dv_solo_input_enqueue / _collect: the detector's input in front of the network (colour frame -> [3, model_h, model_w]; solo_input.hip, released by dv_solo_input_release)
+    // dv_solo_input_enqueue / _collect: the detector's input in front of the network (colour frame -> [3, model_h, model_w]; solo_input.hip)
     struct SoloInputFrame* solo_in = nullptr;
-    // dv_mot_*: the multi-object tracker behind that stage (detections + embeddings -> track ids; mot.hip, released by dv_mot_release)
+    // dv_mot_*: the multi-object tracker behind that stage (detections + embeddings -> track ids; mot.hip)
     struct MotTracker* mot = nullptr;
-    // dv_reid_*: the ReID extractor in front of it (colour image + rectangles -> embeddings; reid.hip, released by dv_reid_release)
+    // dv_reid_*: the ReID extractor in front of it (colour image + rectangles -> embeddings; reid.hip)
     struct ReidNet* reid = nullptr;
-    // dv_line_track_*: the line tracker (key lines + LBD descriptors -> line ids and rows; line_track.hip, released by dv_line_track_release)
+    // dv_line_track_*: the line tracker (key lines + LBD descriptors -> line ids and rows; line_track.hip)
     struct LineTracker* line_track = nullptr;
-    // dv_lbd_*: the LBD descriptor in front of it (gray image + key lines -> selected lines and 32-byte rows on the device; lbd.hip, released by dv_lbd_release)
+    // dv_lbd_*: the LBD descriptor in front of it (gray image + key lines -> selected lines and 32-byte rows on the device; lbd.hip)
     struct LbdStage* lbd = nullptr;
     DevBuf undist_buf[2]; bool undist[2] = { false, false }; int undist_w = 0, undist_h = 0;      // cfg::is_undistort_input: fixed-point maps per camera (map1 | map2)
     bool cam_switched = false; dv_cam cam_orig[2]{};      // dv_undistort_setup: cfg.cam0 / cam1 hold (newK, 0); the cameras the ctx was created with, restored when the maps are removed
@@ -287,6 +305,40 @@ void dv_set_error(dv_ctx* ctx, const std::string& msg);
         }                                                                                \
     } while (0)
 #define DV_FAIL(msg) do { dv_set_error(ctx, msg); return -1; } while (0)
+
+// ---- The stage protocol: one frame in flight per slot, enqueue = open .. close, collect = wait.  Every per-frame stage of the ctx (below) holds one. ----
+struct StageSlot {
+    hipEvent_t ev = nullptr; bool pending = false, recorded = false;      // recorded: the frame in flight ends with ev (an empty frame is pending without it)
+    // enqueue, before its first HIP call: refuses (the stage's own text) while a frame is in flight, selects the ctx's device, creates the event on first use
+    int open(dv_ctx* ctx, const char* refusal) {
+        if (pending) DV_FAIL(refusal);
+        DV_CHECK(hipSetDevice(ctx->cfg.device));
+        if (!ev) DV_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        return 0;
+    }
+    // enqueue, last: e = the first error since the first launch on s (hipGetLastError, the download to pinned memory).  Kernels may be reading the caller's arrays or the
+    // stage's pinned block in place, so a frame that failed is "not pending" only once s is idle: the stream is drained before the entry returns -1
+    int close(dv_ctx* ctx, hipError_t e, hipStream_t s) {
+        if (e == hipSuccess) e = hipEventRecord(ev, s);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(s); DV_CHECK(e); }
+        pending = recorded = true;
+        return 0;
+    }
+    void close_empty() { pending = true; recorded = false; }      // a frame with nothing to do: no launch, no event, collect does not wait
+    // collect, behind its own refusal ("nothing enqueued" is a `pending` test at the call: the stage may not exist yet, and it precedes the entry's argument checks)
+    int wait(dv_ctx* ctx) {
+        if (recorded) DV_CHECK(hipEventSynchronize(ev));
+        pending = false;
+        return 0;
+    }
+    StageSlot() = default;
+    StageSlot(const StageSlot&) = delete;
+    StageSlot& operator=(const StageSlot&) = delete;
+    ~StageSlot() { if (ev) (void)hipEventDestroy(ev); }
+};
+// The stages are defined in their own files, each beside its one-line deleter; dv_destroy deletes all eight once the streams are idle
+void dv_stage_delete(ViodeFrame* p); void dv_stage_delete(InstStackFrame* p); void dv_stage_delete(SoloHeadFrame* p); void dv_stage_delete(SoloInputFrame* p);
+void dv_stage_delete(MotTracker* p); void dv_stage_delete(ReidNet* p); void dv_stage_delete(LineTracker* p); void dv_stage_delete(LbdStage* p);
 
 // ---- The staging rule: a caller's 2-D array as the kernels read it, and a pitched result on its way back.  Every entry that takes an image goes through these two. ----
 // h rows of row_bytes bytes at src, stride_bytes apart.  in_place: the caller's pointer and stride — the site says which memory kinds it reads where they lie with

@@ -135,32 +135,21 @@ __global__ __launch_bounds__(SEL_THREADS) void lbd_select_kernel(const DvLbdLine
 
 struct LbdSet {      // one image's buffers: cam 0 / 1
     DevBuf img, mask, grad, lines, fdesc, desc, o_line, o_desc, o_hdr;
-    uint8_t* pinned_in = nullptr;       // DvLbdLine[DV_LINE_MAX], then the fetched key lines and num_pixels of a DV_MEM_DEVICE frame
-    uint8_t* pinned_out = nullptr;      // DV_LBD_OUT_BYTES
-    hipEvent_t ev = nullptr;
+    PinBuf pinned_in;       // DvLbdLine[DV_LINE_MAX], then the fetched key lines and num_pixels of a DV_MEM_DEVICE frame
+    PinBuf pinned_out;      // DV_LBD_OUT_BYTES
+    StageSlot slot;
     int w = 0, h = 0, n = 0;
-    bool pending = false, have = false;
+    bool have = false;
 };
 static constexpr size_t PIN_LINES = (size_t)LM * sizeof(DvLbdLine), PIN_KEYS = (size_t)LM * sizeof(dv_key_line), PIN_IN = PIN_LINES + PIN_KEYS + (size_t)LM * 4;
 
 struct LbdStage { LbdSet set[2]; DvLbdTabs tabs{}; bool tabs_ready = false; };
 
-void dv_lbd_release(dv_ctx* ctx) {
-    LbdStage* S = ctx->lbd;
-    if (!S) return;
-    for (LbdSet& b : S->set) {
-        b.img.release(); b.mask.release(); b.grad.release(); b.lines.release(); b.fdesc.release(); b.desc.release(); b.o_line.release(); b.o_desc.release(); b.o_hdr.release();
-        if (b.pinned_in) (void)hipHostFree(b.pinned_in);
-        if (b.pinned_out) (void)hipHostFree(b.pinned_out);
-        if (b.ev) (void)hipEventDestroy(b.ev);
-    }
-    delete S; ctx->lbd = nullptr;
-}
+void dv_stage_delete(LbdStage* p) { delete p; }
 
 static int lbd_ensure(dv_ctx* ctx, LbdSet& b, int w, int h) {
-    if (!b.ev) DV_CHECK(hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
-    if (!b.pinned_in) { void* p = nullptr; DV_CHECK(hipHostMalloc(&p, PIN_IN, hipHostMallocDefault)); b.pinned_in = (uint8_t*)p; }
-    if (!b.pinned_out) { void* p = nullptr; DV_CHECK(hipHostMalloc(&p, DV_LBD_OUT_BYTES, hipHostMallocDefault)); b.pinned_out = (uint8_t*)p; }
+    DV_CHECK(b.pinned_in.ensure(PIN_IN));
+    DV_CHECK(b.pinned_out.ensure(DV_LBD_OUT_BYTES));
     DV_CHECK(b.grad.ensure((size_t)w * h * 4));                     // dx | dy, int16, rows of w
     DV_CHECK(b.lines.ensure(PIN_LINES));
     DV_CHECK(b.fdesc.ensure((size_t)LM * DV_LBD_FLOATS * 4));
@@ -197,22 +186,21 @@ int dv_lbd_describe_enqueue(dv_ctx* ctx, int cam, const uint8_t* image, int stri
     if (!ctx->lbd) ctx->lbd = new LbdStage();
     LbdStage& S = *ctx->lbd;
     LbdSet& b = S.set[cam];
-    if (b.pending) DV_FAIL("dv_lbd_describe_enqueue: previous frame of this cam not collected");
+    if (b.slot.open(ctx, "dv_lbd_describe_enqueue: previous frame of this cam not collected")) return -1;
     if (!S.tabs_ready) { dv_lbd_tables(&S.tabs); S.tabs_ready = true; }
-    DV_CHECK(hipSetDevice(ctx->cfg.device));
     if (lbd_ensure(ctx, b, w, h)) return -1;
     hipStream_t s = ctx->stream;
     // the lines: dL is computed on the host, so a frame whose lines are in device memory is fetched first (<= 14 KB); its values are checked here
     const dv_key_line* hk = lines; const int32_t* hn = num_pixels;
     if (n > 0 && lines_mem == DV_MEM_DEVICE) {
-        dv_key_line* fk = (dv_key_line*)(b.pinned_in + PIN_LINES); int32_t* fn = (int32_t*)(b.pinned_in + PIN_LINES + PIN_KEYS);
+        dv_key_line* fk = (dv_key_line*)(b.pinned_in.p + PIN_LINES); int32_t* fn = (int32_t*)(b.pinned_in.p + PIN_LINES + PIN_KEYS);
         DV_CHECK(hipMemcpyAsync(fk, lines, (size_t)n * sizeof(dv_key_line), hipMemcpyDeviceToHost, s));
         if (num_pixels) DV_CHECK(hipMemcpyAsync(fn, num_pixels, (size_t)n * 4, hipMemcpyDeviceToHost, s));
         DV_CHECK(hipStreamSynchronize(s));
         hk = fk; hn = num_pixels ? fn : nullptr;
         if (const char* why = dv_lbd_values_check_host(w, h, hk, hn, n)) DV_FAIL(std::string("dv_lbd_describe_enqueue: ") + why);
     }
-    DvLbdLine* pl = (DvLbdLine*)b.pinned_in;
+    DvLbdLine* pl = (DvLbdLine*)b.pinned_in.p;
     for (int i = 0; i < n; ++i) pl[i] = dv_lbd_line(hk[i], hn ? hn[i] : dv_lbd_npix(hk[i].sx, hk[i].sy, hk[i].ex, hk[i].ey));
     DvRows im, mk{};          // device and pinned memory in place, pageable memory through the set's own buffers
     if (dv_stage_rows(ctx, b.img, image, w, h, stride, dv_in_place_device_or_pinned(image_mem), s, &im)) return -1;
@@ -221,7 +209,7 @@ int dv_lbd_describe_enqueue(dv_ctx* ctx, int cam, const uint8_t* image, int stri
     hipError_t e;
     {
         StageScope sc_t(ctx, "lbd_describe");
-        e = n > 0 ? dv_copy_async(b.lines.p, b.pinned_in, (size_t)n * sizeof(DvLbdLine), s) : hipSuccess;
+        e = n > 0 ? dv_copy_async(b.lines.p, b.pinned_in.p, (size_t)n * sizeof(DvLbdLine), s) : hipSuccess;
         if (e == hipSuccess) {
             hipLaunchKernelGGL(lbd_grad_kernel, dim3((w + GT_W - 1) / GT_W, (h + GT_H - 1) / GT_H), dim3(256), 0, s, im.p, im.pitch, w, h, dx, dy);
             if (n > 0) hipLaunchKernelGGL(lbd_describe_kernel, dim3(n), dim3(64), 0, s, dx, dy, w, h, (const DvLbdLine*)b.lines.p, n, S.tabs, (float*)b.fdesc.p, (uint8_t*)b.desc.p);
@@ -229,14 +217,10 @@ int dv_lbd_describe_enqueue(dv_ctx* ctx, int cam, const uint8_t* image, int stri
                                (dv_key_line*)b.o_line.p, (uint32_t*)b.o_desc.p, (int*)b.o_hdr.p);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = dv_copy_async(b.pinned_out, b.o_hdr.p, (size_t)(DV_LBD_O_WORDS + n) * 4, s);      // the count and at most n indices
+        if (e == hipSuccess) e = dv_copy_async(b.pinned_out.p, b.o_hdr.p, (size_t)(DV_LBD_O_WORDS + n) * 4, s);      // the count and at most n indices
     }
-    if (e == hipSuccess) e = hipEventRecord(b.ev, s);
-    if (e != hipSuccess) {                           // kernels may be running on the caller's arrays: nothing is pending only once the stream is idle
-        (void)hipStreamSynchronize(s);
-        DV_CHECK(e);
-    }
-    b.w = w; b.h = h; b.n = n; b.pending = true; b.have = true;
+    if (b.slot.close(ctx, e, s)) return -1;          // (kernels read the caller's arrays in place)
+    b.w = w; b.h = h; b.n = n; b.have = true;
     return 0;
 }
 
@@ -244,11 +228,10 @@ int dv_lbd_describe_collect(dv_ctx* ctx, int cam, int* n_kept, int32_t* src, con
     if (!ctx) return -1;
     if (cam != 0 && cam != 1) DV_FAIL("dv_lbd_describe_collect: cam must be 0 or 1");
     if (!n_kept) DV_FAIL("dv_lbd_describe_collect: null n_kept");
-    if (!ctx->lbd || !ctx->lbd->set[cam].pending) DV_FAIL("dv_lbd_describe_collect: nothing enqueued on this cam");
+    if (!ctx->lbd || !ctx->lbd->set[cam].slot.pending) DV_FAIL("dv_lbd_describe_collect: nothing enqueued on this cam");
     LbdSet& b = ctx->lbd->set[cam];
-    DV_CHECK(hipEventSynchronize(b.ev));
-    b.pending = false;
-    const int32_t* o = (const int32_t*)b.pinned_out;
+    if (b.slot.wait(ctx)) return -1;
+    const int32_t* o = (const int32_t*)b.pinned_out.p;
     const int nk = o[DV_LBD_O_NKEPT];
     if (nk < 0 || nk > b.n) DV_FAIL("dv_lbd_describe_collect: corrupt counter");
     *n_kept = nk;
@@ -261,7 +244,7 @@ int dv_lbd_describe_collect(dv_ctx* ctx, int cam, int* n_kept, int32_t* src, con
         if (host_desc) DV_CHECK(hipMemcpyAsync(host_desc, b.o_desc.p, (size_t)nk * DV_LINE_DESC_BYTES, hipMemcpyDeviceToHost, ctx->stream));
         DV_CHECK(hipStreamSynchronize(ctx->stream));
     }
-    if (ctx->timing && !ctx->lbd->set[cam ^ 1].pending) dv_harvest_timers(ctx, ctx->stream);      // (the stream is idle only when the other cam has nothing in flight)
+    if (ctx->timing && !ctx->lbd->set[cam ^ 1].slot.pending) dv_harvest_timers(ctx, ctx->stream);      // (the stream is idle only when the other cam has nothing in flight)
     return 0;
 }
 

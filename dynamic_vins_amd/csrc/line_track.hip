@@ -183,21 +183,13 @@ constexpr size_t IN_LINES = (size_t)LM * sizeof(dv_key_line), IN_DESC = (size_t)
 struct LineTracker {
     DvLineLayout L{}; DvLineOut O{};
     DevBuf table, out, op;
-    uint8_t* pinned_out = nullptr;      // O.bytes
-    uint8_t* pinned_in = nullptr;       // DV_MEM_HOST frames: left lines | left descriptors | right lines | right descriptors, read in place by the kernel
-    hipEvent_t ev = nullptr;
-    bool ready = false, pending = false;
+    PinBuf pinned_out;      // O.bytes
+    PinBuf pinned_in;       // DV_MEM_HOST frames: left lines | left descriptors | right lines | right descriptors, read in place by the kernel
+    StageSlot slot;
+    bool ready = false;
 };
 
-void dv_line_track_release(dv_ctx* ctx) {
-    LineTracker* T = ctx->line_track;
-    if (!T) return;
-    T->table.release(); T->out.release(); T->op.release();
-    if (T->pinned_out) (void)hipHostFree(T->pinned_out);
-    if (T->pinned_in) (void)hipHostFree(T->pinned_in);
-    if (T->ev) (void)hipEventDestroy(T->ev);
-    delete T; ctx->line_track = nullptr;
-}
+void dv_stage_delete(LineTracker* p) { delete p; }
 
 // the tracker's buffers, once; the resident table starts as dv_line_track_reset leaves it
 static int line_ensure(dv_ctx* ctx) {
@@ -206,9 +198,8 @@ static int line_ensure(dv_ctx* ctx) {
     if (T.ready) return 0;
     DV_CHECK(hipSetDevice(ctx->cfg.device));
     T.L = dv_line_layout(); T.O = dv_line_out_layout();
-    if (!T.ev) DV_CHECK(hipEventCreateWithFlags(&T.ev, hipEventDisableTiming));
-    if (!T.pinned_out) { void* p = nullptr; DV_CHECK(hipHostMalloc(&p, T.O.bytes, hipHostMallocDefault)); T.pinned_out = (uint8_t*)p; }
-    if (!T.pinned_in) { void* p = nullptr; DV_CHECK(hipHostMalloc(&p, IN_BYTES, hipHostMallocDefault)); T.pinned_in = (uint8_t*)p; }
+    DV_CHECK(T.pinned_out.ensure(T.O.bytes));
+    DV_CHECK(T.pinned_in.ensure(IN_BYTES));
     DV_CHECK(T.table.ensure(T.L.bytes));
     DV_CHECK(T.out.ensure(T.O.bytes));
     DV_CHECK(hipMemsetAsync(T.table.p, 0, T.L.bytes, ctx->stream));
@@ -227,7 +218,7 @@ int dv_line_track_check(const dv_key_line* left_lines, const uint8_t* left_desc,
 
 int dv_line_track_reset(dv_ctx* ctx) {
     if (!ctx) return -1;
-    if (ctx->line_track && ctx->line_track->pending) DV_FAIL("dv_line_track_reset: a frame is in flight");
+    if (ctx->line_track && ctx->line_track->slot.pending) DV_FAIL("dv_line_track_reset: a frame is in flight");
     if (line_ensure(ctx)) return -1;
     DV_CHECK(hipSetDevice(ctx->cfg.device));
     hipLaunchKernelGGL(line_reset_kernel, dim3(1), dim3(64), 0, ctx->stream, (int*)((uint8_t*)ctx->line_track->table.p + ctx->line_track->L.hdr));
@@ -238,10 +229,10 @@ int dv_line_track_reset(dv_ctx* ctx) {
 int dv_line_track_enqueue(dv_ctx* ctx, const dv_key_line* left_lines, const uint8_t* left_desc, int n_left, const dv_key_line* right_lines, const uint8_t* right_desc, int n_right, int mem) {
     if (!ctx) return -1;
     if (const char* why = dv_line_frame_check_host(left_lines, left_desc, n_left, right_lines, right_desc, n_right, mem)) DV_FAIL(std::string("dv_line_track_enqueue: ") + why);
-    if (ctx->line_track && ctx->line_track->pending) DV_FAIL("dv_line_track_enqueue: previous frame not collected");
-    if (line_ensure(ctx)) return -1;
+    if (!ctx->line_track) ctx->line_track = new LineTracker();
     LineTracker& T = *ctx->line_track;
-    DV_CHECK(hipSetDevice(ctx->cfg.device));
+    if (T.slot.open(ctx, "dv_line_track_enqueue: previous frame not collected")) return -1;
+    if (line_ensure(ctx)) return -1;
     hipStream_t s = ctx->stream;
     uint8_t* tb = (uint8_t*)T.table.p;
     LineDev D{};
@@ -250,7 +241,7 @@ int dv_line_track_enqueue(dv_ctx* ctx, const dv_key_line* left_lines, const uint
     D.n_left = n_left; D.n_right = (right_lines && right_desc) ? n_right : 0;
     D.cam0 = ctx->cfg.cam0; D.cam1 = ctx->cfg.cam1;
     if (mem == DV_MEM_HOST) {                        // the caller's memory may be pageable: into the library's pinned block, which the kernel reads in place
-        uint8_t* p = T.pinned_in;
+        uint8_t* p = T.pinned_in.p;
         if (n_left > 0) { std::memcpy(p, left_lines, (size_t)n_left * sizeof(dv_key_line)); std::memcpy(p + IN_LINES, left_desc, (size_t)n_left * DV_LINE_DESC_BYTES); }
         if (D.n_right > 0) { std::memcpy(p + IN_LINES + IN_DESC, right_lines, (size_t)n_right * sizeof(dv_key_line)); std::memcpy(p + 2 * IN_LINES + IN_DESC, right_desc, (size_t)n_right * DV_LINE_DESC_BYTES); }
         D.l_line = (const dv_key_line*)p; D.l_desc = (const uint32_t*)(p + IN_LINES);
@@ -263,37 +254,31 @@ int dv_line_track_enqueue(dv_ctx* ctx, const dv_key_line* left_lines, const uint
         StageScope sc_t(ctx, "line_track");
         hipLaunchKernelGGL(line_track_kernel, dim3(1), dim3(LT_THREADS), 0, s, D);
         e = hipGetLastError();
-        if (e == hipSuccess) e = dv_copy_async(T.pinned_out, T.out.p, T.O.rows + (size_t)n_left * sizeof(dv_line_row), s);      // counters, per-line words and at most n_left rows
+        if (e == hipSuccess) e = dv_copy_async(T.pinned_out.p, T.out.p, T.O.rows + (size_t)n_left * sizeof(dv_line_row), s);      // counters, per-line words and at most n_left rows
     }
-    if (e == hipSuccess) e = hipEventRecord(T.ev, s);
-    if (e != hipSuccess) {                           // the kernel may be running and reads pinned_in / the caller's arrays in place: nothing is pending only once it is done
-        (void)hipStreamSynchronize(s);
-        DV_CHECK(e);
-    }
-    T.pending = true;
-    return 0;
+    return T.slot.close(ctx, e, s);                  // (the kernel reads pinned_in / the caller's arrays in place)
 }
 
 int dv_line_track_collect(dv_ctx* ctx, dv_line_row* rows, int cap, int* n_rows, uint32_t* left_ids, int32_t* left_src, int32_t* left_cnt, int* n_left_out,
                           uint32_t* right_ids, int32_t* right_src, int* n_right_out) {
     if (!ctx) return -1;
-    if (!ctx->line_track || !ctx->line_track->pending) DV_FAIL("dv_line_track_collect: nothing enqueued");
+    if (!ctx->line_track || !ctx->line_track->slot.pending) DV_FAIL("dv_line_track_collect: nothing enqueued");
     if (const char* why = dv_line_collect_check_host(rows, cap, n_rows)) DV_FAIL(std::string("dv_line_track_collect: ") + why);
     LineTracker& T = *ctx->line_track;
-    DV_CHECK(hipEventSynchronize(T.ev));
+    if (T.slot.wait(ctx)) return -1;
     if (ctx->timing) dv_harvest_timers(ctx, ctx->stream);
-    T.pending = false;
-    const int32_t* o = (const int32_t*)T.pinned_out;
+    const uint8_t* po = T.pinned_out.p;
+    const int32_t* o = (const int32_t*)po;
     const int nr = o[DV_LT_O_NROWS], nl = o[DV_LT_O_NLEFT], nrt = o[DV_LT_O_NRIGHT];
     if (nr < 0 || nl < 0 || nrt < 0 || nl > DV_LINE_MAX || nrt > DV_LINE_MAX || nr > nl) DV_FAIL("dv_line_track_collect: corrupt counters");
     *n_rows = nr;
-    if (rows && cap > 0 && nr > 0) std::memcpy(rows, T.pinned_out + T.O.rows, (size_t)(nr < cap ? nr : cap) * sizeof(dv_line_row));
-    if (left_ids) std::memcpy(left_ids, T.pinned_out + T.O.left_ids, (size_t)nl * 4);
-    if (left_src) std::memcpy(left_src, T.pinned_out + T.O.left_src, (size_t)nl * 4);
-    if (left_cnt) std::memcpy(left_cnt, T.pinned_out + T.O.left_cnt, (size_t)nl * 4);
+    if (rows && cap > 0 && nr > 0) std::memcpy(rows, po + T.O.rows, (size_t)(nr < cap ? nr : cap) * sizeof(dv_line_row));
+    if (left_ids) std::memcpy(left_ids, po + T.O.left_ids, (size_t)nl * 4);
+    if (left_src) std::memcpy(left_src, po + T.O.left_src, (size_t)nl * 4);
+    if (left_cnt) std::memcpy(left_cnt, po + T.O.left_cnt, (size_t)nl * 4);
     if (n_left_out) *n_left_out = nl;
-    if (right_ids) std::memcpy(right_ids, T.pinned_out + T.O.right_ids, (size_t)nrt * 4);
-    if (right_src) std::memcpy(right_src, T.pinned_out + T.O.right_src, (size_t)nrt * 4);
+    if (right_ids) std::memcpy(right_ids, po + T.O.right_ids, (size_t)nrt * 4);
+    if (right_src) std::memcpy(right_src, po + T.O.right_src, (size_t)nrt * 4);
     if (n_right_out) *n_right_out = nrt;
     return 0;
 }

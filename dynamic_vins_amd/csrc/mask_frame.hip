@@ -10,18 +10,10 @@ struct ViodeFrame {
     struct Set { DevBuf inv, keys0, keys1; } set[2];
     int cur = 1;
     DevBuf seg[2], scratch /* planes nobody reads: the merged mask, the right image's two masks */, small /* keys (256 B) | boxes left (1024 B) | boxes right (1024 B) */;
-    uint8_t* pinned = nullptr;      // box initialiser (1024 B) | keys (256 B) | the frame's boxes (1024 B)
-    hipEvent_t ev = nullptr; bool pending = false, has_right = false; int nkeys = 0, keys_on_dev = 0; uint32_t keys[64] = { 0 };
+    PinBuf pinned;      // box initialiser (1024 B) | keys (256 B) | the frame's boxes (1024 B)
+    StageSlot slot; bool has_right = false; int nkeys = 0, keys_on_dev = 0; uint32_t keys[64] = { 0 };
 };
-void dv_viode_frame_release(dv_ctx* ctx) {
-    ViodeFrame* V = ctx->viode;
-    if (!V) return;
-    for (ViodeFrame::Set& q : V->set) { q.inv.release(); q.keys0.release(); q.keys1.release(); }
-    V->seg[0].release(); V->seg[1].release(); V->scratch.release(); V->small.release();
-    if (V->pinned) (void)hipHostFree(V->pinned);
-    if (V->ev) (void)hipEventDestroy(V->ev);
-    delete V; ctx->viode = nullptr;
-}
+void dv_stage_delete(ViodeFrame* p) { delete p; }
 
 // dv_inst_stack_frame_enqueue / _collect: the same stage from a detector's mask stack.  Two buffer sets used alternately, as above: set[cur] belongs to the frame enqueued
 // last.  A DV_MEM_HOST stack is staged into its set (tightly packed) and `from` remembers its descriptor: the *_planes entries of the frame find the copy there.
@@ -29,18 +21,10 @@ struct InstStackFrame {
     struct Set { DevBuf merge, inv, staged; dv_mask_stack from{}; bool has_staged = false; } set[2];
     int cur = 1;
     DevBuf small /* boxes (1024 B) */, scratch /* DV_STACK_REMAP_MERGED: the merged mask before the remap | the remapped one, pitched */;
-    uint8_t* pinned = nullptr;      // box initialiser (1024 B) | the frame's boxes (1024 B)
-    hipEvent_t ev = nullptr; bool pending = false; int n_planes = 0;
+    PinBuf pinned;      // box initialiser (1024 B) | the frame's boxes (1024 B)
+    StageSlot slot; int n_planes = 0;
 };
-void dv_inst_stack_frame_release(dv_ctx* ctx) {
-    InstStackFrame* V = ctx->istack;
-    if (!V) return;
-    for (InstStackFrame::Set& q : V->set) { q.merge.release(); q.inv.release(); q.staged.release(); }
-    V->small.release(); V->scratch.release();
-    if (V->pinned) (void)hipHostFree(V->pinned);
-    if (V->ev) (void)hipEventDestroy(V->ev);
-    delete V; ctx->istack = nullptr;
-}
+void dv_stage_delete(InstStackFrame* p) { delete p; }
 static bool same_stack(const dv_mask_stack& a, const dv_mask_stack& b) {
     return a.data == b.data && a.n_planes == b.n_planes && a.kind == b.kind && a.mem == b.mem && a.row_stride == b.row_stride && a.plane_stride == b.plane_stride;
 }
@@ -59,14 +43,14 @@ static int stage_host_stack(dv_ctx* ctx, const dv_mask_stack& st, int es, DevBuf
 void dv_stack_frame_done(dv_ctx* ctx) {
     InstStackFrame* V = ctx->istack;
     if (!V) return;
-    if (V->pending) V->set[V->cur ^ 1].has_staged = false;
+    if (V->slot.pending) V->set[V->cur ^ 1].has_staged = false;
     else V->set[0].has_staged = V->set[1].has_staged = false;
 }
 int dv_stack_resolve(dv_ctx* ctx, const dv_mask_stack& st, DevBuf& own_buf, hipStream_t s, DvStackSrc* out) {
     const int es = st.kind == DV_STACK_F32 ? 4 : 1, w = ctx->cfg.width, h = ctx->cfg.height;
     if (st.mem != DV_MEM_HOST) { *out = DvStackSrc{ (const uint8_t*)st.data, (long long)st.plane_stride, st.row_stride, st.n_planes, st.kind, st.threshold }; return 0; }
     const void* dev = nullptr;
-    if (ctx->istack && !ctx->istack->pending) {
+    if (ctx->istack && !ctx->istack->slot.pending) {
         const InstStackFrame::Set& Q = ctx->istack->set[ctx->istack->cur];
         if (Q.has_staged && same_stack(Q.from, st)) dev = Q.staged.p;
     }
@@ -88,21 +72,11 @@ int dv_viode_frame_enqueue(dv_ctx* ctx, const uint8_t* seg0_bgr, const uint8_t* 
     if (stride < 3 * w) DV_FAIL("dv_viode_frame_enqueue: stride below 3 * width");
     if (nkeys < 1 || nkeys > 64) DV_FAIL("dv_viode_frame_enqueue: 1..64 dynamic keys");
     if (!dv_mem_known(mem)) DV_FAIL("dv_viode_frame_enqueue: unknown memory kind");
-    if (ctx->viode && ctx->viode->pending) DV_FAIL("dv_viode_frame_enqueue: previous frame not collected");
-    DV_CHECK(hipSetDevice(ctx->cfg.device));
-    hipStream_t s = ctx->stream;
-    if (!ctx->viode) {
-        ViodeFrame* N = new ViodeFrame();
-        ctx->viode = N;          // (a half-built one is completed by the next call or released by dv_destroy)
-    }
+    if (!ctx->viode) ctx->viode = new ViodeFrame();          // (a half-built one is completed by the next call or deleted by dv_destroy)
     ViodeFrame& V = *ctx->viode;
-    if (!V.ev) DV_CHECK(hipEventCreateWithFlags(&V.ev, hipEventDisableTiming));
-    if (!V.pinned) {
-        void* p = nullptr;
-        DV_CHECK(hipHostMalloc(&p, 1024 + 256 + 1024, hipHostMallocDefault));
-        V.pinned = (uint8_t*)p;
-        dv_boxes_init((int32_t*)V.pinned);
-    }
+    if (V.slot.open(ctx, "dv_viode_frame_enqueue: previous frame not collected")) return -1;
+    hipStream_t s = ctx->stream;
+    if (!V.pinned.p) { DV_CHECK(V.pinned.ensure(1024 + 256 + 1024)); dv_boxes_init((int32_t*)V.pinned.p); }
     const int mp = w;          // the masks are tightly packed: the inverse mask goes to dv_track_stereo_enqueue as a DV_MEM_DEVICE mask beside gray frames of stride w
     const size_t plane = ((size_t)mp * h + 255) / 256 * 256;
     ViodeFrame::Set& Q = V.set[V.cur ^ 1];
@@ -113,13 +87,13 @@ int dv_viode_frame_enqueue(dv_ctx* ctx, const uint8_t* seg0_bgr, const uint8_t* 
     if (dv_inst_wait_before_next_frame(ctx, s, false)) DV_FAIL("dv_viode_frame_enqueue: hipStreamWaitEvent");
     uint32_t* d_keys = (uint32_t*)V.small.p; int32_t* d_box0 = (int32_t*)((uint8_t*)V.small.p + 256); int32_t* d_box1 = d_box0 + 256;
     if (V.keys_on_dev != nkeys || std::memcmp(V.keys, dyn_keys, 4 * (size_t)nkeys) != 0) {      // (no frame is in flight: the pinned copy of the table is not being read)
-        std::memcpy(V.keys, dyn_keys, 4 * (size_t)nkeys); std::memcpy(V.pinned + 1024, dyn_keys, 4 * (size_t)nkeys);
-        DV_CHECK(dv_copy_async(d_keys, V.pinned + 1024, 256, s));
+        std::memcpy(V.keys, dyn_keys, 4 * (size_t)nkeys); std::memcpy(V.pinned.p + 1024, dyn_keys, 4 * (size_t)nkeys);
+        DV_CHECK(dv_copy_async(d_keys, V.pinned.p + 1024, 256, s));
         V.keys_on_dev = nkeys;
     }
     V.nkeys = nkeys;
-    DV_CHECK(dv_copy_async(d_box0, V.pinned, 1024, s));          // the box buffers start every frame at (max, -1, max, -1)
-    if (seg1_bgr_or_null) DV_CHECK(dv_copy_async(d_box1, V.pinned, 1024, s));
+    DV_CHECK(dv_copy_async(d_box0, V.pinned.p, 1024, s));          // the box buffers start every frame at (max, -1, max, -1)
+    if (seg1_bgr_or_null) DV_CHECK(dv_copy_async(d_box1, V.pinned.p, 1024, s));
     const uint8_t* src[2] = { seg0_bgr, seg1_bgr_or_null }; int spitch = stride;
     for (int i = 0; i < 2; ++i) if (src[i]) {
         DvRows r;
@@ -132,21 +106,20 @@ int dv_viode_frame_enqueue(dv_ctx* ctx, const uint8_t* seg0_bgr, const uint8_t* 
         dv_launch_viode_mask(src[0], w, h, spitch, d_keys, nkeys, sc, (uint8_t*)Q.inv.p, mp, (uint32_t*)Q.keys0.p, d_box0, s);
         if (src[1]) dv_launch_viode_mask(src[1], w, h, spitch, d_keys, nkeys, sc + plane, sc + 2 * plane, mp, (uint32_t*)Q.keys1.p, d_box1, s);
     }
-    DV_CHECK(hipGetLastError());
-    DV_CHECK(dv_copy_async(V.pinned + 1280, d_box0, 1024, s));
-    DV_CHECK(hipEventRecord(V.ev, s));
-    V.cur ^= 1; V.pending = true; V.has_right = seg1_bgr_or_null != nullptr;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = dv_copy_async(V.pinned.p + 1280, d_box0, 1024, s);
+    if (V.slot.close(ctx, e, s)) return -1;
+    V.cur ^= 1; V.has_right = seg1_bgr_or_null != nullptr;
     return 0;
 }
 
 int dv_viode_frame_collect(dv_ctx* ctx, int min_inst_size, dv_inst_det* dets, int cap, int* n_dets, const uint8_t** inv_mask_dev, const uint32_t** keys0_dev, const uint32_t** keys1_dev) {
     if (!ctx) return -1;
-    if (!ctx->viode || !ctx->viode->pending) DV_FAIL("dv_viode_frame_collect: nothing enqueued");
+    if (!ctx->viode || !ctx->viode->slot.pending) DV_FAIL("dv_viode_frame_collect: nothing enqueued");
     if (!n_dets || cap < 0 || (cap > 0 && !dets)) DV_FAIL("dv_viode_frame_collect: bad argument");
     ViodeFrame& V = *ctx->viode;
-    DV_CHECK(hipEventSynchronize(V.ev));
-    V.pending = false;
-    const int n = dv_viode_build_dets((const int32_t*)(V.pinned + 1280), V.keys, V.nkeys, min_inst_size, dets, cap);
+    if (V.slot.wait(ctx)) return -1;
+    const int n = dv_viode_build_dets((const int32_t*)(V.pinned.p + 1280), V.keys, V.nkeys, min_inst_size, dets, cap);
     if (n < 0) DV_FAIL("dv_viode_frame_collect: more detections than `cap`");
     *n_dets = n;
     const ViodeFrame::Set& Q = V.set[V.cur];
@@ -167,18 +140,11 @@ int dv_inst_stack_frame_enqueue(dv_ctx* ctx, const dv_mask_stack* stack, int w, 
     if (flags & ~DV_STACK_REMAP_MERGED) DV_FAIL("dv_inst_stack_frame_enqueue: unknown flag");
     const bool remap = (flags & DV_STACK_REMAP_MERGED) != 0;
     if (remap && !ctx->undist[0]) DV_FAIL("dv_inst_stack_frame_enqueue: DV_STACK_REMAP_MERGED needs installed undistortion maps (dv_undistort_setup / dv_set_undistort_maps)");
-    if (ctx->istack && ctx->istack->pending) DV_FAIL("dv_inst_stack_frame_enqueue: previous frame not collected");
-    DV_CHECK(hipSetDevice(ctx->cfg.device));
-    hipStream_t s = ctx->stream;
-    if (!ctx->istack) ctx->istack = new InstStackFrame();          // (a half-built one is completed by the next call or released by dv_destroy)
+    if (!ctx->istack) ctx->istack = new InstStackFrame();          // (a half-built one is completed by the next call or deleted by dv_destroy)
     InstStackFrame& V = *ctx->istack;
-    if (!V.ev) DV_CHECK(hipEventCreateWithFlags(&V.ev, hipEventDisableTiming));
-    if (!V.pinned) {
-        void* p = nullptr;
-        DV_CHECK(hipHostMalloc(&p, 2048, hipHostMallocDefault));
-        V.pinned = (uint8_t*)p;
-        dv_boxes_init((int32_t*)V.pinned);
-    }
+    if (V.slot.open(ctx, "dv_inst_stack_frame_enqueue: previous frame not collected")) return -1;
+    hipStream_t s = ctx->stream;
+    if (!V.pinned.p) { DV_CHECK(V.pinned.ensure(2048)); dv_boxes_init((int32_t*)V.pinned.p); }
     const size_t plane = ((size_t)w * h + 255) / 256 * 256;          // the masks are tightly packed: the inverse goes to dv_track_stereo_enqueue as a DV_MEM_DEVICE mask beside frames of stride w
     const int rp = align_up(w, 16);
     InstStackFrame::Set& Q = V.set[V.cur ^ 1];
@@ -196,7 +162,7 @@ int dv_inst_stack_frame_enqueue(dv_ctx* ctx, const dv_mask_stack* stack, int w, 
         S.base = (const uint8_t*)Q.staged.p; S.row_stride = w * L.es; S.plane_stride = (long long)w * L.es * h;
     }
     int32_t* d_box = (int32_t*)V.small.p;
-    DV_CHECK(dv_copy_async(d_box, V.pinned, 1024, s));          // the boxes start every frame at (max, -1, max, -1)
+    DV_CHECK(dv_copy_async(d_box, V.pinned.p, 1024, s));          // the boxes start every frame at (max, -1, max, -1)
     {
         StageScope sc_t(ctx, "inst_stack_frame");
         if (!remap) dv_launch_inst_stack(S, w, h, (uint8_t*)Q.merge.p, (uint8_t*)Q.inv.p, d_box, s);
@@ -208,22 +174,21 @@ int dv_inst_stack_frame_enqueue(dv_ctx* ctx, const dv_mask_stack* stack, int w, 
             dv_launch_stack_finish_remap(mapped, rp, w, h, (uint8_t*)Q.merge.p, (uint8_t*)Q.inv.p, s);
         }
     }
-    DV_CHECK(hipGetLastError());
-    DV_CHECK(dv_copy_async(V.pinned + 1024, d_box, 1024, s));
-    DV_CHECK(hipEventRecord(V.ev, s));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = dv_copy_async(V.pinned.p + 1024, d_box, 1024, s);
+    if (V.slot.close(ctx, e, s)) return -1;
     if (st.mem == DV_MEM_HOST) { Q.from = st; Q.has_staged = true; }
-    V.cur ^= 1; V.pending = true; V.n_planes = st.n_planes;
+    V.cur ^= 1; V.n_planes = st.n_planes;
     return 0;
 }
 
 int dv_inst_stack_frame_collect(dv_ctx* ctx, int min_inst_size, dv_inst_det* dets, int32_t* planes, int cap, int* n_dets, const uint8_t** inv_mask_dev, const uint8_t** merge_mask_dev) {
     if (!ctx) return -1;
-    if (!ctx->istack || !ctx->istack->pending) DV_FAIL("dv_inst_stack_frame_collect: nothing enqueued");
+    if (!ctx->istack || !ctx->istack->slot.pending) DV_FAIL("dv_inst_stack_frame_collect: nothing enqueued");
     if (!n_dets || cap < 0 || (cap > 0 && !dets)) DV_FAIL("dv_inst_stack_frame_collect: bad argument");
     InstStackFrame& V = *ctx->istack;
-    DV_CHECK(hipEventSynchronize(V.ev));
-    V.pending = false;
-    const int n = dv_stack_build_dets((const int32_t*)(V.pinned + 1024), V.n_planes, min_inst_size, dets, planes, cap);
+    if (V.slot.wait(ctx)) return -1;
+    const int n = dv_stack_build_dets((const int32_t*)(V.pinned.p + 1024), V.n_planes, min_inst_size, dets, planes, cap);
     if (n < 0) DV_FAIL("dv_inst_stack_frame_collect: more detections than `cap`");
     *n_dets = n;
     const InstStackFrame::Set& Q = V.set[V.cur];

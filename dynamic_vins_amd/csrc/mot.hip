@@ -428,20 +428,13 @@ struct MotTracker {
     DvMotLayout L{};
     DevBuf table, gallery, featmin, out, staged, op;
     MotDev D{};
-    int32_t* pinned = nullptr;      // O_WORDS ints
-    hipEvent_t ev = nullptr;
-    bool configured = false, pending = false; int pend_n = 0;
+    PinBuf pinned;      // O_WORDS ints
+    StageSlot slot;
+    bool configured = false; int pend_n = 0;
     int n_tracks = 0, n_confirmed = 0;
 };
 
-void dv_mot_release(dv_ctx* ctx) {
-    MotTracker* T = ctx->mot;
-    if (!T) return;
-    T->table.release(); T->gallery.release(); T->featmin.release(); T->out.release(); T->staged.release(); T->op.release();
-    if (T->pinned) (void)hipHostFree(T->pinned);
-    if (T->ev) (void)hipEventDestroy(T->ev);
-    delete T; ctx->mot = nullptr;
-}
+void dv_stage_delete(MotTracker* p) { delete p; }
 
 static int mot_reset(dv_ctx* ctx, MotTracker& T) {
     hipLaunchKernelGGL(mot_reset_kernel, dim3(1), dim3(256), 0, ctx->stream, T.D);
@@ -461,13 +454,12 @@ int dv_mot_check(const dv_mot_params* par) {
 int dv_mot_config(dv_ctx* ctx, const dv_mot_params* par) {
     if (!ctx) return -1;
     if (const char* why = dv_mot_check_host(par)) DV_FAIL(std::string("dv_mot_config: ") + why);
-    if (ctx->mot && ctx->mot->pending) DV_FAIL("dv_mot_config: a frame is in flight");
+    if (ctx->mot && ctx->mot->slot.pending) DV_FAIL("dv_mot_config: a frame is in flight");
     DV_CHECK(hipSetDevice(ctx->cfg.device));
     DV_CHECK(hipStreamSynchronize(ctx->stream));
     if (!ctx->mot) ctx->mot = new MotTracker();
     MotTracker& T = *ctx->mot;
-    if (!T.ev) DV_CHECK(hipEventCreateWithFlags(&T.ev, hipEventDisableTiming));
-    if (!T.pinned) { void* p = nullptr; DV_CHECK(hipHostMalloc(&p, O_WORDS * 4, hipHostMallocDefault)); T.pinned = (int32_t*)p; }
+    DV_CHECK(T.pinned.ensure(O_WORDS * 4));
     T.par = *par; T.L = dv_mot_layout(par->max_tracks);
     const size_t gbytes = (size_t)par->max_tracks * par->budget * par->feat_dim * 4;
     DV_CHECK(T.table.ensure(T.L.bytes));
@@ -491,7 +483,7 @@ int dv_mot_config(dv_ctx* ctx, const dv_mot_params* par) {
 int dv_mot_reset(dv_ctx* ctx) {
     if (!ctx) return -1;
     if (!ctx->mot || !ctx->mot->configured) DV_FAIL("dv_mot_reset: dv_mot_config first");
-    if (ctx->mot->pending) DV_FAIL("dv_mot_reset: a frame is in flight");
+    if (ctx->mot->slot.pending) DV_FAIL("dv_mot_reset: a frame is in flight");
     DV_CHECK(hipSetDevice(ctx->cfg.device));
     return mot_reset(ctx, *ctx->mot);
 }
@@ -501,9 +493,8 @@ int dv_mot_update_enqueue(dv_ctx* ctx, const float* rects_xywh, const float* fea
     if (!ctx->mot || !ctx->mot->configured) DV_FAIL("dv_mot_update_enqueue: dv_mot_config first");
     MotTracker& T = *ctx->mot;
     if (const char* why = dv_mot_frame_check_host(rects_xywh, feats, n, mem)) DV_FAIL(std::string("dv_mot_update_enqueue: ") + why);
-    if (T.pending) DV_FAIL("dv_mot_update_enqueue: previous frame not collected");
-    if (n == 0) { T.pending = true; T.pend_n = 0; return 0; }      // the reference's tracker is not called: nothing predicts, nothing ages
-    DV_CHECK(hipSetDevice(ctx->cfg.device));
+    if (T.slot.open(ctx, "dv_mot_update_enqueue: previous frame not collected")) return -1;
+    if (n == 0) { T.slot.close_empty(); T.pend_n = 0; return 0; }      // the reference's tracker is not called: nothing predicts, nothing ages
     hipStream_t s = ctx->stream;
     MotDev D = T.D;
     D.n = n;
@@ -520,22 +511,22 @@ int dv_mot_update_enqueue(dv_ctx* ctx, const float* rects_xywh, const float* fea
         hipLaunchKernelGGL(mot_feat_kernel, dim3(T.par.max_tracks), dim3(256), 0, s, D);
         hipLaunchKernelGGL(mot_assoc_kernel, dim3(1), dim3(256), 0, s, D);
     }
-    DV_CHECK(hipGetLastError());
-    DV_CHECK(dv_copy_async(T.pinned, D.out, O_WORDS * 4, s));
-    DV_CHECK(hipEventRecord(T.ev, s));
-    T.pending = true; T.pend_n = n;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = dv_copy_async(T.pinned.p, D.out, O_WORDS * 4, s);
+    if (T.slot.close(ctx, e, s)) return -1;
+    T.pend_n = n;
     return 0;
 }
 
 int dv_mot_update_collect(dv_ctx* ctx, int32_t* track_id, int* n_tracks, int* n_confirmed) {
     if (!ctx) return -1;
-    if (!ctx->mot || !ctx->mot->pending) DV_FAIL("dv_mot_update_collect: nothing enqueued");
+    if (!ctx->mot || !ctx->mot->slot.pending) DV_FAIL("dv_mot_update_collect: nothing enqueued");
     MotTracker& T = *ctx->mot;
     if (T.pend_n > 0 && !track_id) DV_FAIL("dv_mot_update_collect: null track_id");
-    if (T.pend_n > 0) { DV_CHECK(hipEventSynchronize(T.ev)); if (ctx->timing) dv_harvest_timers(ctx, ctx->stream); }
-    T.pending = false;
+    if (T.slot.wait(ctx)) return -1;
     if (T.pend_n > 0) {
-        const int32_t* o = T.pinned;
+        if (ctx->timing) dv_harvest_timers(ctx, ctx->stream);
+        const int32_t* o = (const int32_t*)T.pinned.p;
         if (o[O_FAIL] == FAIL_CAPACITY)
             DV_FAIL("dv_mot_update_collect: the frame would leave " + std::to_string(o[O_WOULD]) + " tracks, more than max_tracks " + std::to_string(T.par.max_tracks) +
                     ": the frame is dropped and the tracker is as it was before it");
@@ -554,7 +545,7 @@ int dv_mot_get_tracks(dv_ctx* ctx, dv_mot_track* out, int cap, int* n) {
     if (!ctx->mot || !ctx->mot->configured) DV_FAIL("dv_mot_get_tracks: dv_mot_config first");
     MotTracker& T = *ctx->mot;
     if (!n || cap < 0 || (cap > 0 && !out)) DV_FAIL("dv_mot_get_tracks: bad argument");
-    if (T.pending) DV_FAIL("dv_mot_get_tracks: a frame is in flight");
+    if (T.slot.pending) DV_FAIL("dv_mot_get_tracks: a frame is in flight");
     DV_CHECK(hipSetDevice(ctx->cfg.device));
     DV_CHECK(hipStreamSynchronize(ctx->stream));
     std::vector<uint8_t> h(T.L.bytes);

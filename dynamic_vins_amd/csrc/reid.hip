@@ -188,22 +188,14 @@ static ConvArgs conv_args(const float* x, const float* w, const float* scale, co
 
 struct ReidNet {
     int in_w = 0, in_h = 0;
-    bool loaded = false, pending = false, failed = false; int pend_n = 0, last_n = 0;
+    bool loaded = false, failed = false; int pend_n = 0, last_n = 0;
     DevBuf weights /* conv1 [27][64], then the packed convolutions in file order */, bn /* scale, shift per layer */, lut, act[3], input, feats, flags, img, rects, op;
     size_t w_off[DV_REID_CONVS]{}, s_off[DV_REID_CONVS]{};      // floats into weights / bn; conv1: weights 0, bn 0
-    int32_t* pinned = nullptr;      // MC flags
-    hipEvent_t ev = nullptr;
+    PinBuf pinned;      // MC flags
+    StageSlot slot;
 };
 
-void dv_reid_release(dv_ctx* ctx) {
-    ReidNet* R = ctx->reid;
-    if (!R) return;
-    R->weights.release(); R->bn.release(); R->lut.release(); for (DevBuf& b : R->act) b.release();
-    R->input.release(); R->feats.release(); R->flags.release(); R->img.release(); R->rects.release(); R->op.release();
-    if (R->pinned) (void)hipHostFree(R->pinned);
-    if (R->ev) (void)hipEventDestroy(R->ev);
-    delete R; ctx->reid = nullptr;
-}
+void dv_stage_delete(ReidNet* p) { delete p; }
 
 extern "C" {
 
@@ -217,14 +209,13 @@ int dv_reid_load(dv_ctx* ctx, const float* weights, size_t n_floats, int in_w, i
     if (!ctx) return -1;
     if (const char* why = dv_reid_check_host(n_floats, in_w, in_h)) DV_FAIL(std::string("dv_reid_load: ") + why);
     if (!weights) DV_FAIL("dv_reid_load: null weights");
-    if (ctx->reid && ctx->reid->pending) DV_FAIL("dv_reid_load: a frame is in flight");
+    if (ctx->reid && ctx->reid->slot.pending) DV_FAIL("dv_reid_load: a frame is in flight");
     DV_CHECK(hipSetDevice(ctx->cfg.device));
     DV_CHECK(hipStreamSynchronize(ctx->stream));
     if (!ctx->reid) ctx->reid = new ReidNet();
     ReidNet& R = *ctx->reid;
     R.loaded = false;
-    if (!R.ev) DV_CHECK(hipEventCreateWithFlags(&R.ev, hipEventDisableTiming));
-    if (!R.pinned) { void* p = nullptr; DV_CHECK(hipHostMalloc(&p, MC * 4, hipHostMallocDefault)); R.pinned = (int32_t*)p; }
+    DV_CHECK(R.pinned.ensure(MC * 4));
     // the device layout: conv1's [27][64] then every convolution packed for the kernel's B operand (same float counts as the file's); scale / shift pairs per layer
     constexpr DvReidPlan P = dv_reid_plan();
     size_t wn = 27 * DV_REID_C1, sn = 2 * DV_REID_C1;
@@ -259,9 +250,8 @@ int dv_reid_extract_enqueue(dv_ctx* ctx, const uint8_t* bgr, int stride, const f
     ReidNet& R = *ctx->reid;
     const int W = ctx->cfg.width, H = ctx->cfg.height;
     if (const char* why = dv_reid_frame_check_host(bgr, W, stride, rects_xywh, n, mem)) DV_FAIL(std::string("dv_reid_extract_enqueue: ") + why);
-    if (R.pending) DV_FAIL("dv_reid_extract_enqueue: previous frame not collected");
-    if (n == 0) { R.pending = true; R.pend_n = 0; return 0; }
-    DV_CHECK(hipSetDevice(ctx->cfg.device));
+    if (R.slot.open(ctx, "dv_reid_extract_enqueue: previous frame not collected")) return -1;
+    if (n == 0) { R.slot.close_empty(); R.pend_n = 0; return 0; }
     hipStream_t s = ctx->stream;
     CropArgs ca{};
     DvRows im;          // the rectangles travel with the image: both in place, or both copied
@@ -298,22 +288,23 @@ int dv_reid_extract_enqueue(dv_ctx* ctx, const uint8_t* bgr, int stride, const f
         }
         hipLaunchKernelGGL(reid_tail_kernel, dim3(n), dim3(FD), 0, s, A, (float*)R.feats.p);
     }
-    DV_CHECK(hipGetLastError());
-    DV_CHECK(dv_copy_async(R.pinned, R.flags.p, MC * 4, s));
-    DV_CHECK(hipEventRecord(R.ev, s));
-    R.pending = true; R.pend_n = n;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = dv_copy_async(R.pinned.p, R.flags.p, MC * 4, s);
+    if (R.slot.close(ctx, e, s)) return -1;
+    R.pend_n = n;
     return 0;
 }
 
 int dv_reid_extract_collect(dv_ctx* ctx, const float** feats_dev) {
     if (!ctx) return -1;
-    if (!ctx->reid || !ctx->reid->pending) DV_FAIL("dv_reid_extract_collect: nothing enqueued");
+    if (!ctx->reid || !ctx->reid->slot.pending) DV_FAIL("dv_reid_extract_collect: nothing enqueued");
     ReidNet& R = *ctx->reid;
-    if (R.pend_n > 0) { DV_CHECK(hipEventSynchronize(R.ev)); if (ctx->timing) dv_harvest_timers(ctx, ctx->stream); }
-    R.pending = false; R.last_n = R.pend_n; R.failed = false;
+    if (R.slot.wait(ctx)) return -1;
+    if (R.pend_n > 0 && ctx->timing) dv_harvest_timers(ctx, ctx->stream);
+    R.last_n = R.pend_n; R.failed = false;
     if (feats_dev) *feats_dev = R.pend_n > 0 ? (const float*)R.feats.p : nullptr;
     for (int j = 0; j < R.pend_n; ++j)
-        if (R.pinned[j]) {
+        if (((const int32_t*)R.pinned.p)[j]) {
             R.failed = true;
             DV_FAIL("dv_reid_extract_collect: rectangle " + std::to_string(j) + " is empty or leaves the " + std::to_string(ctx->cfg.width) + " x " + std::to_string(ctx->cfg.height) +
                     " image after rounding (the reference's ori_img(rect) throws): the frame has no embeddings");
@@ -325,7 +316,7 @@ int dv_reid_get_feats(dv_ctx* ctx, float* out, int n) {
     if (!ctx) return -1;
     if (!ctx->reid || !ctx->reid->loaded) DV_FAIL("dv_reid_get_feats: dv_reid_load first");
     ReidNet& R = *ctx->reid;
-    if (R.pending) DV_FAIL("dv_reid_get_feats: a frame is in flight");
+    if (R.slot.pending) DV_FAIL("dv_reid_get_feats: a frame is in flight");
     if (R.failed) DV_FAIL("dv_reid_get_feats: the last frame failed");
     if (n < 0 || n > R.last_n || (n > 0 && !out)) DV_FAIL("dv_reid_get_feats: n exceeds the last frame's crops, or null output");
     if (n == 0) return 0;
@@ -339,7 +330,7 @@ int dv_reid_input(dv_ctx* ctx, float* out) {
     if (!ctx) return -1;
     if (!ctx->reid || !ctx->reid->loaded) DV_FAIL("dv_reid_input: dv_reid_load first");
     ReidNet& R = *ctx->reid;
-    if (R.pending) DV_FAIL("dv_reid_input: a frame is in flight");
+    if (R.slot.pending) DV_FAIL("dv_reid_input: a frame is in flight");
     if (R.last_n == 0) return 0;
     if (!out) DV_FAIL("dv_reid_input: null output");
     DV_CHECK(hipSetDevice(ctx->cfg.device));
@@ -353,7 +344,7 @@ int dv_reid_layer(dv_ctx* ctx, const float* x, int n, int c_in, int h, int w, co
     if (!ctx) return -1;
     if (const char* why = dv_reid_layer_check_host(n, c_in, h, w, c_out, k, stride)) DV_FAIL(std::string("dv_reid_layer: ") + why);
     if (!x || !weight || !scale || !shift || !out) DV_FAIL("dv_reid_layer: null argument");
-    if (ctx->reid && ctx->reid->pending) DV_FAIL("dv_reid_layer: a frame is in flight");
+    if (ctx->reid && ctx->reid->slot.pending) DV_FAIL("dv_reid_layer: a frame is in flight");
     if (!ctx->reid) ctx->reid = new ReidNet();
     ReidNet& R = *ctx->reid;
     DV_CHECK(hipSetDevice(ctx->cfg.device));

@@ -334,20 +334,13 @@ __global__ __launch_bounds__(256) void solo_resample_kernel(SoloDev D, SoloResam
 struct SoloHeadFrame {
     DevBuf planes[2], work, staged;
     int cur = 1;
-    uint8_t* pinned = nullptr;      // out_i (4 + 128 + 128 ints) | scores (128 floats)
-    hipEvent_t ev = nullptr; bool pending = false;
+    PinBuf pinned;      // out_i (4 + 128 + 128 ints) | scores (128 floats)
+    StageSlot slot;
     int ow = 0, oh = 0, pitch = 0;
 };
 constexpr size_t SOLO_OUT_INTS = 4 + 2 * DV_SOLO_MAX_PER_IMG, SOLO_OUT_BYTES = SOLO_OUT_INTS * 4 + DV_SOLO_MAX_PER_IMG * 4;
 
-void dv_solo_head_release(dv_ctx* ctx) {
-    SoloHeadFrame* V = ctx->solo;
-    if (!V) return;
-    V->planes[0].release(); V->planes[1].release(); V->work.release(); V->staged.release();
-    if (V->pinned) (void)hipHostFree(V->pinned);
-    if (V->ev) (void)hipEventDestroy(V->ev);
-    delete V; ctx->solo = nullptr;
-}
+void dv_stage_delete(SoloHeadFrame* p) { delete p; }
 
 extern "C" {
 
@@ -366,13 +359,11 @@ int dv_solo_check(const dv_solo_outputs* out, const dv_solo_params* par) {
 int dv_solo_head_enqueue(dv_ctx* ctx, const dv_solo_outputs* out, const dv_solo_params* par) {
     if (!ctx) return -1;
     if (const char* why = dv_solo_check_host(out, par)) DV_FAIL(std::string("dv_solo_head_enqueue: ") + why);
-    if (ctx->solo && ctx->solo->pending) DV_FAIL("dv_solo_head_enqueue: previous frame not collected");
-    DV_CHECK(hipSetDevice(ctx->cfg.device));
-    hipStream_t s = ctx->stream;
     if (!ctx->solo) ctx->solo = new SoloHeadFrame();
     SoloHeadFrame& V = *ctx->solo;
-    if (!V.ev) DV_CHECK(hipEventCreateWithFlags(&V.ev, hipEventDisableTiming));
-    if (!V.pinned) { void* p = nullptr; DV_CHECK(hipHostMalloc(&p, SOLO_OUT_BYTES, hipHostMallocDefault)); V.pinned = (uint8_t*)p; }
+    if (V.slot.open(ctx, "dv_solo_head_enqueue: previous frame not collected")) return -1;
+    hipStream_t s = ctx->stream;
+    DV_CHECK(V.pinned.ensure(SOLO_OUT_BYTES));
 
     DvSoloTables T;
     dv_solo_tables(out, par, &T);
@@ -439,22 +430,21 @@ int dv_solo_head_enqueue(dv_ctx* ctx, const dv_solo_outputs* out, const dv_solo_
         hipLaunchKernelGGL((solo_product_kernel<true>), dim3(col_blocks, (D.max_per_img + 31) / 32), dim3(256), 0, s, D);
         hipLaunchKernelGGL(solo_resample_kernel, dim3((R.pitch / 4 + 63) / 64, (R.oh + 3) / 4, D.max_per_img), dim3(64, 4), 0, s, D, R);
     }
-    DV_CHECK(hipGetLastError());
-    DV_CHECK(dv_copy_async(V.pinned, D.out_i, SOLO_OUT_BYTES, s));
-    DV_CHECK(hipEventRecord(V.ev, s));
-    V.cur ^= 1; V.pending = true; V.ow = R.ow; V.oh = R.oh; V.pitch = R.pitch;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = dv_copy_async(V.pinned.p, D.out_i, SOLO_OUT_BYTES, s);
+    if (V.slot.close(ctx, e, s)) return -1;
+    V.cur ^= 1; V.ow = R.ow; V.oh = R.oh; V.pitch = R.pitch;
     return 0;
 }
 
 int dv_solo_head_collect(dv_ctx* ctx, int32_t* labels, float* scores, int cap, int* n, int* n_candidates, dv_mask_stack* stack) {
     if (!ctx) return -1;
-    if (!ctx->solo || !ctx->solo->pending) DV_FAIL("dv_solo_head_collect: nothing enqueued");
+    if (!ctx->solo || !ctx->solo->slot.pending) DV_FAIL("dv_solo_head_collect: nothing enqueued");
     if (!n || cap < 0 || (cap > 0 && (!labels || !scores))) DV_FAIL("dv_solo_head_collect: bad argument");
     SoloHeadFrame& V = *ctx->solo;
-    DV_CHECK(hipEventSynchronize(V.ev));
-    V.pending = false;
-    const int32_t* oi = (const int32_t*)V.pinned;
-    const float* os = (const float*)(V.pinned + SOLO_OUT_INTS * 4);
+    if (V.slot.wait(ctx)) return -1;
+    const int32_t* oi = (const int32_t*)V.pinned.p;
+    const float* os = (const float*)(V.pinned.p + SOLO_OUT_INTS * 4);
     if (n_candidates) *n_candidates = oi[1];
     *n = 0;
     if (stack) *stack = dv_mask_stack{};

@@ -71,17 +71,11 @@ __global__ __launch_bounds__(256) void solo_input_kernel(SoloInputArgs a) {
 struct SoloInputFrame {
     DevBuf out[2], staged;
     int cur = 1;
-    hipEvent_t ev = nullptr; bool pending = false;
+    StageSlot slot;
     const float* last = nullptr; int rect[4] = {0, 0, 0, 0};
 };
 
-void dv_solo_input_release(dv_ctx* ctx) {
-    SoloInputFrame* V = ctx->solo_in;
-    if (!V) return;
-    V->out[0].release(); V->out[1].release(); V->staged.release();
-    if (V->ev) (void)hipEventDestroy(V->ev);
-    delete V; ctx->solo_in = nullptr;
-}
+void dv_stage_delete(SoloInputFrame* p) { delete p; }
 
 extern "C" {
 
@@ -99,12 +93,10 @@ int dv_solo_input_enqueue(dv_ctx* ctx, const uint8_t* bgr, int stride, int mem, 
     if (!bgr) DV_FAIL("dv_solo_input_enqueue: null image");
     if (!dv_mem_known(mem)) DV_FAIL("dv_solo_input_enqueue: unknown memory kind");
     if ((uintptr_t)dst_dev & 3) DV_FAIL("dv_solo_input_enqueue: dst_dev must be 4-byte aligned");
-    if (ctx->solo_in && ctx->solo_in->pending) DV_FAIL("dv_solo_input_enqueue: previous frame not collected");
-    DV_CHECK(hipSetDevice(ctx->cfg.device));
-    hipStream_t s = ctx->stream;
     if (!ctx->solo_in) ctx->solo_in = new SoloInputFrame();
     SoloInputFrame& V = *ctx->solo_in;
-    if (!V.ev) DV_CHECK(hipEventCreateWithFlags(&V.ev, hipEventDisableTiming));
+    if (V.slot.open(ctx, "dv_solo_input_enqueue: previous frame not collected")) return -1;
+    hipStream_t s = ctx->stream;
 
     DvRows im;
     if (dv_stage_rows(ctx, V.staged, bgr, (size_t)3 * W, H, stride, dv_in_place_device_or_pinned(mem), s, &im)) return -1;
@@ -122,19 +114,17 @@ int dv_solo_input_enqueue(dv_ctx* ctx, const uint8_t* bgr, int stride, int mem, 
         StageScope sc_t(ctx, "solo_input");
         hipLaunchKernelGGL(solo_input_kernel, dim3((a.mw + 255) / 256, (a.mh + 3) / 4), dim3(256), 0, s, a);
     }
-    DV_CHECK(hipGetLastError());
-    DV_CHECK(hipEventRecord(V.ev, s));
+    if (V.slot.close(ctx, hipGetLastError(), s)) return -1;
     if (!dst_dev) V.cur ^= 1;
-    V.pending = true; V.last = a.out; V.rect[0] = a.rx; V.rect[1] = a.ry; V.rect[2] = a.rw; V.rect[3] = a.rh;
+    V.last = a.out; V.rect[0] = a.rx; V.rect[1] = a.ry; V.rect[2] = a.rw; V.rect[3] = a.rh;
     return 0;
 }
 
 int dv_solo_input_collect(dv_ctx* ctx, const float** input_dev, int* rect_x, int* rect_y, int* rect_w, int* rect_h) {
     if (!ctx) return -1;
-    if (!ctx->solo_in || !ctx->solo_in->pending) DV_FAIL("dv_solo_input_collect: nothing enqueued");
+    if (!ctx->solo_in || !ctx->solo_in->slot.pending) DV_FAIL("dv_solo_input_collect: nothing enqueued");
     SoloInputFrame& V = *ctx->solo_in;
-    DV_CHECK(hipEventSynchronize(V.ev));
-    V.pending = false;
+    if (V.slot.wait(ctx)) return -1;
     if (input_dev) *input_dev = V.last;
     if (rect_x) *rect_x = V.rect[0];
     if (rect_y) *rect_y = V.rect[1];
