@@ -131,6 +131,10 @@ SIGNATURES = {
     "dv_solo_input_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "dv_solo_input_enqueue": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dv_solo_input_collect": (C.c_int, [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dv_stereo_sgm_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dv_stereo_sgm_enqueue": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dv_stereo_sgm_collect": (C.c_int, [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    "dv_stereo_sgm_debug": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_longlong]),
     "dv_mot_check": (C.c_int, [C.c_void_p]),
     "dv_mot_config": (C.c_int, [_ctx, C.c_void_p]),
     "dv_mot_reset": (C.c_int, [_ctx]),

@@ -162,9 +162,9 @@ void dv_destroy(dv_ctx* ctx) {
     if (ctx->out_pinned) (void)hipHostFree(ctx->out_pinned);
     if (ctx->unmask_pinned) (void)hipHostFree(ctx->unmask_pinned);
     ctx->unmask_src_buf.release();
-    // the eight per-frame stages own their buffers, pinned blocks and events (StageSlot, dv_ctx.h)
+    // the nine per-frame stages own their buffers, pinned blocks and events (StageSlot, dv_ctx.h)
     dv_stage_delete(ctx->viode); dv_stage_delete(ctx->istack); dv_stage_delete(ctx->solo); dv_stage_delete(ctx->solo_in);
-    dv_stage_delete(ctx->mot); dv_stage_delete(ctx->reid); dv_stage_delete(ctx->line_track); dv_stage_delete(ctx->lbd);
+    dv_stage_delete(ctx->mot); dv_stage_delete(ctx->reid); dv_stage_delete(ctx->line_track); dv_stage_delete(ctx->lbd); dv_stage_delete(ctx->sgm);
     if (ctx->done) (void)hipEventDestroy(ctx->done);
     if (ctx->ev_pyr) (void)hipEventDestroy(ctx->ev_pyr);
     if (ctx->ev_bg_select) (void)hipEventDestroy(ctx->ev_bg_select);

@@ -258,6 +258,8 @@ struct dv_ctx {
     struct SoloHeadFrame* solo = nullptr;
     // dv_solo_input_enqueue / _collect: the detector's input in front of the network (colour frame -> [3, model_h, model_w]; solo_input.hip)
     struct SoloInputFrame* solo_in = nullptr;
+    // dv_stereo_sgm_enqueue / _collect: the stereo matcher (gray pair -> SemanticImage::disp on the device; stereo_sgm.hip)
+    struct StereoSgmStage* sgm = nullptr;
     // dv_mot_*: the multi-object tracker behind that stage (detections + embeddings -> track ids; mot.hip)
     struct MotTracker* mot = nullptr;
     // dv_reid_*: the ReID extractor in front of it (colour image + rectangles -> embeddings; reid.hip)
@@ -336,9 +338,9 @@ struct StageSlot {
     StageSlot& operator=(const StageSlot&) = delete;
     ~StageSlot() { if (ev) (void)hipEventDestroy(ev); }
 };
-// The stages are defined in their own files, each beside its one-line deleter; dv_destroy deletes all eight once the streams are idle
+// The stages are defined in their own files, each beside its one-line deleter; dv_destroy deletes all nine once the streams are idle
 void dv_stage_delete(ViodeFrame* p); void dv_stage_delete(InstStackFrame* p); void dv_stage_delete(SoloHeadFrame* p); void dv_stage_delete(SoloInputFrame* p);
-void dv_stage_delete(MotTracker* p); void dv_stage_delete(ReidNet* p); void dv_stage_delete(LineTracker* p); void dv_stage_delete(LbdStage* p);
+void dv_stage_delete(MotTracker* p); void dv_stage_delete(ReidNet* p); void dv_stage_delete(LineTracker* p); void dv_stage_delete(LbdStage* p); void dv_stage_delete(StereoSgmStage* p);
 
 // ---- The staging rule: a caller's 2-D array as the kernels read it, and a pitched result on its way back.  Every entry that takes an image goes through these two. ----
 // h rows of row_bytes bytes at src, stride_bytes apart.  in_place: the caller's pointer and stride — the site says which memory kinds it reads where they lie with

@@ -113,6 +113,31 @@ def solo_input_check(img_w, img_h, model_w, model_h, mean=SOLO_IMG_MEAN, std=SOL
         raise DvinsError(lib.dv_last_error(None).decode())
 
 
+class dv_sgm_params(C.Structure):
+    _fields_ = [("n_disp", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32), ("uniqueness", C.c_int32), ("lr_max_diff", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+DV_SGM_DEBUG_CENSUS_L, DV_SGM_DEBUG_CENSUS_R, DV_SGM_DEBUG_S, DV_SGM_DEBUG_DSTAR, DV_SGM_DEBUG_DR = 0, 1, 2, 3, 4
+
+
+def sgm_params(n_disp=128, p1=10, p2=120, uniqueness=5, lr_max_diff=1, reserved=(0, 0, 0)):
+    """dv_sgm_params of the stereo matcher (MyStereoMatcher's place, stereo/stereo.cpp): n_disp 64 / 128 / 256, the two path penalties, OpenCV's uniqueness margin in
+    per cent, the left-right tolerance (< 0: no test)"""
+    p = dv_sgm_params()
+    p.n_disp, p.p1, p.p2, p.uniqueness, p.lr_max_diff = int(n_disp), int(p1), int(p2), int(uniqueness), int(lr_max_diff)
+    for i in range(3):
+        p.reserved[i] = int(reserved[i])
+    return p
+
+
+def sgm_check(w, h, params=None, stride=None, **kw):
+    """the refusals of Context.stereo_sgm_enqueue for a w x h pair (stride: bytes per row, default w), without a device: raises DvinsError with the reason"""
+    lib = _abi.load()
+    p = params if params is not None else sgm_params(**kw)
+    if lib.dv_stereo_sgm_check(int(w), int(h), int(w if stride is None else stride), C.addressof(p)) != 0:
+        raise DvinsError(lib.dv_last_error(None).decode())
+
+
 class _DeviceArray:
     """a device pointer and a shape behind __cuda_array_interface__: what torch.as_tensor wraps without a copy"""
 
@@ -488,6 +513,54 @@ class Context:
         ptr, shape, rect = self.solo_input_collect()
         return device_tensor(ptr, shape, device=self.cfg.device), rect
 
+    # ---- the stereo matcher (MyStereoMatcher::Launch / WaitResult, stereo/stereo.cpp): rectified gray pair -> SemanticImage::disp on the device ----
+    def stereo_sgm_enqueue(self, gray0, gray1, params=None, mem=DV_MEM_HOST, stride=None, **kw):
+        """one frame on the ctx's stream; params = sgm_params(...) or its keywords.  mem = DV_MEM_HOST: two (height, width) uint8 arrays of the ctx's size with ONE row
+        stride, staged.  DV_MEM_DEVICE / DV_MEM_PINNED: pointers (int) read in place until the collect, with the row stride in bytes"""
+        par = params if params is not None else sgm_params(**kw)
+        if mem == DV_MEM_HOST:
+            for g in (gray0, gray1):
+                if not (isinstance(g, np.ndarray) and g.dtype == np.uint8 and g.ndim == 2 and g.strides[1] == 1 and g.shape == (self.cfg.height, self.cfg.width)):
+                    raise ValueError("stereo_sgm_enqueue: images must be (height, width) uint8 arrays of the ctx's size")
+            if gray0.strides[0] != gray1.strides[0]:
+                raise ValueError("stereo_sgm_enqueue: the two images must share one row stride")
+            stride = gray0.strides[0]
+        else:
+            if stride is None:
+                raise ValueError("stereo_sgm_enqueue: stride is required with device or pinned pointers")
+            if not (isinstance(gray0, (int, np.integer)) and isinstance(gray1, (int, np.integer))):
+                raise ValueError("stereo_sgm_enqueue: images must be pointers (int) with device or pinned memory")
+        self._sgm_keep, self._sgm_par = ((gray0, gray1) if mem == DV_MEM_HOST else None), par
+        self._check(self.lib.dv_stereo_sgm_enqueue(self.h, _ptr(gray0), _ptr(gray1), int(stride), int(mem), C.addressof(par)))
+
+    def stereo_sgm_collect(self):
+        """waits for the stage -> (device pointer of the float32 [height, width] disparity map, its row stride in bytes).  The map is the library's and stays valid until
+        the second enqueue after this collect; it goes straight into inst_set_disparity(ptr, baseline, DV_MEM_DEVICE, stride)"""
+        p, st = C.c_void_p(0), C.c_int(0)
+        self._sgm_keep = None
+        self._check(self.lib.dv_stereo_sgm_collect(self.h, C.byref(p), C.byref(st)))
+        return p.value, st.value
+
+    def stereo_sgm(self, gray0, gray1, params=None, mem=DV_MEM_HOST, stride=None, host=True, **kw):
+        """stereo_sgm_enqueue + stereo_sgm_collect -> the disparity map as a float32 [height, width] host array (host=True) or (device pointer, stride in bytes)"""
+        self.stereo_sgm_enqueue(gray0, gray1, params, mem, stride, **kw)
+        ptr, st = self.stereo_sgm_collect()
+        if not host:
+            return ptr, st
+        return device_tensor(ptr, (self.cfg.height, self.cfg.width), device=self.cfg.device).cpu().numpy()
+
+    def stereo_sgm_debug(self, what):
+        """the last collected frame, for tests: what = DV_SGM_DEBUG_CENSUS_L / _R -> uint64 [h, w]; _S -> uint16 [h, w, n_disp]; _DSTAR / _DR -> int16 [h, w]"""
+        h, w = self.cfg.height, self.cfg.width
+        if what in (DV_SGM_DEBUG_CENSUS_L, DV_SGM_DEBUG_CENSUS_R):
+            out = np.zeros((h, w), np.uint64)
+        elif what == DV_SGM_DEBUG_S:
+            out = np.zeros((h, w, int(self._sgm_par.n_disp)), np.uint16)
+        else:
+            out = np.zeros((h, w), np.int16)
+        self._check(self.lib.dv_stereo_sgm_debug(self.h, int(what), out.ctypes.data, out.nbytes))
+        return out
+
     # ---- the multi-object tracker (DeepSORT::update, mot/deep_sort.cpp:72-139): detections + embeddings -> track ids, table and galleries resident ----
     def mot_config(self, params=None, **kw):
         """allocates and resets the tracker; params = mot_params(...) or its keywords"""
@@ -795,13 +868,19 @@ class Context:
         else:
             self._check(self.lib.dv_inst_set_right_keys(self.h, int(key_img), 0, int(mem)))
 
-    def extra_points(self, mask, box_xy, disp, baseline, stage=0):
-        """operator form: one object through InstFeat::DetectExtraPoints (stage 1) or the whole extra-point pipeline (stage 0) -> float64 [n, 3]"""
-        mask = np.ascontiguousarray(mask, np.uint8); disp = np.ascontiguousarray(disp, np.float32)
+    def extra_points(self, mask, box_xy, disp, baseline, stage=0, mem=DV_MEM_HOST, stride_bytes=0):
+        """operator form: one object through InstFeat::DetectExtraPoints (stage 1) or the whole extra-point pipeline (stage 0) -> float64 [n, 3].  disp: a float32 [h, w]
+        host array, or a device pointer (int) with mem=DV_MEM_DEVICE (stereo_sgm_collect's map), read in place"""
+        mask = np.ascontiguousarray(mask, np.uint8)
+        if isinstance(disp, (int, np.integer)):
+            dptr, dstride, dmem = int(disp), int(stride_bytes), int(mem)
+        else:
+            disp = np.ascontiguousarray(disp, np.float32)
+            dptr, dstride, dmem = disp.ctypes.data, disp.strides[0], DV_MEM_HOST
         h, w = mask.shape
         out = np.zeros((4096, 3), np.float64)
         n = C.c_int(0)
-        self._check(self.lib.dv_extra_points(self.h, mask.ctypes.data, int(box_xy[0]), int(box_xy[1]), w, h, disp.ctypes.data, disp.strides[0], DV_MEM_HOST, float(baseline), int(stage),
+        self._check(self.lib.dv_extra_points(self.h, mask.ctypes.data, int(box_xy[0]), int(box_xy[1]), w, h, dptr, dstride, dmem, float(baseline), int(stage),
                                              out.ctypes.data, len(out), C.byref(n)))
         return out[: n.value].copy()
 

@@ -299,6 +299,10 @@ struct ImageView {                      // a CV_8UC1 cv::Mat: gray0 / gray1 / in
     bool bgr = false;                   // true: 8-bit BGR (SemanticImage::color0 / color1): converted — and undistorted, if maps are installed — on the device
     bool empty() const { return data == nullptr; }
 };
+struct DisparityMap {                   // SemanticImage::disp (CV_32F) as MyStereoMatcher::WaitResult hands it over: rows of stride_bytes in device memory
+    const float* data = nullptr; int width = 0, height = 0, stride_bytes = 0;
+    bool empty() const { return data == nullptr; }
+};
 struct SemanticImage {                  // basic/semantic_image.h:30-65 (the fields the path reads)
     ImageView gray0, gray1, inv_merge_mask;
     double time0 = 0; unsigned int seq = 0;
@@ -763,6 +767,8 @@ public:
     void SetDisparity(const float* disp, int stride_bytes, double baseline, bool device = false) {
         detail::check(ctx_, dv_inst_set_disparity(ctx_, disp, stride_bytes, device ? DV_MEM_DEVICE : DV_MEM_HOST, baseline), "SetDisparity");
     }
+    // the same from MyStereoMatcher::WaitResult's map, which stays on the device
+    void SetDisparity(const DisparityMap& disp, double baseline) { SetDisparity(disp.data, disp.stride_bytes, baseline, true); }
     // cfg::dataset == kViode: the keys of SemanticImage::seg1 (VIODE::PixelToKey per pixel, dv_viode_mask's key image) of the frame the next InstsTrack processes —
     // TrackRightByPad keeps a right-image point only where seg1 carries the object's key (front_end/instance_feature.cpp:263-268)
     void SetRightKeys(const uint32_t* key_image, int stride_bytes = 0, bool device = false) {
@@ -907,6 +913,34 @@ public:
     int model_w() const { return par_.model_w; } int model_h() const { return par_.model_h; }
 private:
     dv_ctx* ctx_; dv_solo_input_params par_{}; int origin_w_ = 0, origin_h_ = 0;
+};
+// The stereo matcher (stereo/stereo.h) on the device.  The reference's MyStereoMatcher::Launch starts an empty StereoMatch() and WaitResult reads a disparity PNG an
+// offline network wrote (stereo/stereo.cpp); here Launch enqueues the census + semi-global matcher of include/dvins.h (dv_stereo_sgm_*) on the frame's rectified gray
+// pair (host memory, or device memory with gray0.device; both of one stride and kind) and WaitResult returns SemanticImage::disp as a device map, one of two used
+// alternately: it stays valid until the second Launch after it and goes into InstsFeatManager::SetDisparity without a host round trip.
+class MyStereoMatcher {
+public:
+    using Ptr = std::shared_ptr<MyStereoMatcher>;
+    explicit MyStereoMatcher(dv_ctx* ctx, int n_disp = 128, int p1 = 10, int p2 = 120, int uniqueness = 5, int lr_max_diff = 1) : ctx_(ctx) {
+        if (!ctx) throw std::runtime_error("MyStereoMatcher: a ctx is required (dv_create failed? " + std::string(dv_last_error(nullptr)) + ")");
+        par_.n_disp = n_disp; par_.p1 = p1; par_.p2 = p2; par_.uniqueness = uniqueness; par_.lr_max_diff = lr_max_diff;
+    }
+    void Launch(const ImageView& gray0, const ImageView& gray1) {
+        if (gray0.empty() || gray1.empty() || gray0.bgr || gray1.bgr) throw std::runtime_error("MyStereoMatcher::Launch: two 8-bit gray images are required");
+        if (gray0.width != gray1.width || gray0.height != gray1.height || gray0.stride != gray1.stride || gray0.device != gray1.device)
+            throw std::runtime_error("MyStereoMatcher::Launch: the two images must share size, stride and memory kind");
+        if (dv_stereo_sgm_check(gray0.width, gray0.height, gray0.stride, &par_) != 0) throw std::runtime_error(std::string("MyStereoMatcher::Launch: ") + dv_last_error(nullptr));
+        detail::check(ctx_, dv_stereo_sgm_enqueue(ctx_, gray0.data, gray1.data, gray0.stride, gray0.device ? DV_MEM_DEVICE : DV_MEM_HOST, &par_), "MyStereoMatcher::Launch");
+        w_ = gray0.width; h_ = gray0.height;
+    }
+    DisparityMap WaitResult() {
+        DisparityMap m; m.width = w_; m.height = h_;
+        detail::check(ctx_, dv_stereo_sgm_collect(ctx_, &m.data, &m.stride_bytes), "MyStereoMatcher::WaitResult");
+        return m;
+    }
+    const dv_sgm_params& params() const { return par_; }
+private:
+    dv_ctx* ctx_; dv_sgm_params par_{}; int w_ = 0, h_ = 0;
 };
 class Detector2D {
 public:

@@ -215,7 +215,7 @@ class DynamicPipeline(Pipeline):
 
     def __init__(self, seq: DynamicSequence, max_cnt=250, min_dist=25, max_iters=10, device=0, use_imu=1, max_dynamic_cnt=50, min_dynamic_dist=5, use_det3d=1,
                  static_inst_threshold=1.0, mask_morphology_size=0, segments=None, est_kw=None, extra_from_disparity=True, ba_stride=1,
-                 static_as_background=False, live_masks=False, mask_stack=False, solo_head=None, mot=None, solo_input=None):
+                 static_as_background=False, live_masks=False, mask_stack=False, solo_head=None, mot=None, solo_input=None, stereo_sgm=None):
         from .frontend import DV_MODE_SEMANTIC
         # live_masks: `seq` carries label images (a viode.ViodeSequence: seg0, seg1, dyn_keys) and thread T1's stage runs per frame on the device (viode_frame_enqueue /
         # _collect + the key-image entries) instead of reading the sequence's pre-computed masks, detections and key images; same results, bit for bit
@@ -267,6 +267,20 @@ class DynamicPipeline(Pipeline):
                     raise ValueError("DynamicPipeline: mot must be (\"device\", params) with feat_dim 512, the extractor's width")
                 mot = ("device", par)
         self.mot, self._mot_keep, self._reid_img = mot, None, (None, None)
+        # stereo_sgm: the stereo matcher on the device in MyStereoMatcher's place (stereo/stereo.cpp) — a frontend.sgm_params(...) or a dict of its keywords.  Per frame
+        # Context.stereo_sgm_enqueue / _collect turn the frame's gray pair into SemanticImage::disp in the library's memory, and that map goes to inst_set_disparity in
+        # place of seq.disp_dev[k] — also for a sequence that carries none (a ViodeSequence).  The matcher of frame k + 1 is enqueued where that frame's other T1 stages
+        # are, behind the tracking of frame k.  The images are rectified as they are (no undistortion in front of it)
+        if stereo_sgm is not None:
+            from .frontend import dv_sgm_params, sgm_params, sgm_check
+            if isinstance(stereo_sgm, dict):
+                stereo_sgm = sgm_params(**stereo_sgm)
+            if not isinstance(stereo_sgm, dv_sgm_params):
+                raise ValueError("DynamicPipeline: stereo_sgm must be frontend.sgm_params(...) or a dict of its keywords")
+            if not extra_from_disparity:
+                raise ValueError("DynamicPipeline: stereo_sgm needs extra_from_disparity: its map is the extra points' source")
+            sgm_check(seq.w, seq.h, stereo_sgm)
+        self.stereo_sgm, self._sgm_enq = stereo_sgm, None
         self.extra_from_disparity = extra_from_disparity      # False: the detections' own `points` are handed through (the caller ran the extra-point pipeline)
         self.seq, self.host = seq, None
         c = make_cam(*sim.cam_tuple(seq.cam))
@@ -353,6 +367,29 @@ class DynamicPipeline(Pipeline):
             self._reid_img = (k, img)
         return self._reid_img[1]
 
+    def _sgm_enqueue(self, k):
+        l, r = self.seq.frames[k]
+        self.ctx.stereo_sgm_enqueue(l.data_ptr(), r.data_ptr(), self.stereo_sgm, mem=DV_MEM_DEVICE, stride=l.stride(0))
+        self._sgm_enq = k
+
+    def _set_disparity(self, k):
+        """SemanticImage::disp of frame k for the object tracker: the matcher's map (stereo_sgm), else the sequence's own where it has one"""
+        if not self.extra_from_disparity:
+            return
+        if self.stereo_sgm is not None:
+            if self._sgm_enq != k:
+                self._sgm_enqueue(k)
+            self._sgm_enq = None
+            ptr, stride = self.ctx.stereo_sgm_collect()
+            self.ctx.inst_set_disparity(ptr, self.seq.baseline, DV_MEM_DEVICE, stride)
+        elif len(getattr(self.seq, "disp_dev", [])):
+            self.ctx.inst_set_disparity(self.seq.disp_dev[k].data_ptr(), self.seq.baseline, DV_MEM_DEVICE)
+
+    def _sgm_next(self, k):
+        """the matcher of frame k + 1 behind the tracking of frame k, beside that frame's other T1 stages"""
+        if self.stereo_sgm is not None and k + 1 < len(self.seq.frames):
+            self._sgm_enqueue(k + 1)
+
     def _enqueue_stack(self, k):
         from .frontend import DV_MEM_DEVICE as DEV
         s, ctx, q = self.seq, self.ctx, self.stack_input()
@@ -369,13 +406,13 @@ class DynamicPipeline(Pipeline):
         if self.static_as_background and len(dets):
             ctx.track_unmask_static_planes(dets, self.static_ids_for(k), q["stacks"][k].data_ptr(), **kw(k))
         ctx.track_stereo_enqueue(l.data_ptr(), r.data_ptr(), s.times[k], inv, self.mode, DEV)
-        if self.extra_from_disparity and len(getattr(s, "disp_dev", [])):
-            ctx.inst_set_disparity(s.disp_dev[k].data_ptr(), s.baseline, DEV)
+        self._set_disparity(k)
         ctx.inst_track_enqueue_planes(s.times[k], dets, q["stacks"][k].data_ptr(), **kw(k))
         self.enqueued = True
         if k + 1 < len(s.frames):          # T1's stage of the next frame behind this frame's tracking
             ctx.inst_stack_frame_enqueue(q["stacks"][k + 1].data_ptr(), **kw(k + 1))
             self._live_enq = k + 1
+        self._sgm_next(k)
 
     def _solo_enqueue_head(self, k):
         if self.solo_input is not None:          # the network's input of frame k from the resident colour frame, then the caller's network on it
@@ -421,8 +458,7 @@ class DynamicPipeline(Pipeline):
                 torch.cuda.synchronize()
             inv = self._solo_blank.data_ptr()
         ctx.track_stereo_enqueue(l.data_ptr(), r.data_ptr(), s.times[k], inv, self.mode, DEV)
-        if self.extra_from_disparity and len(getattr(s, "disp_dev", [])):
-            ctx.inst_set_disparity(s.disp_dev[k].data_ptr(), s.baseline, DEV)
+        self._set_disparity(k)
         if st.n_planes:
             ctx.inst_track_enqueue_planes(s.times[k], dets, st)
         else:
@@ -430,6 +466,7 @@ class DynamicPipeline(Pipeline):
         self.enqueued = True
         if k + 1 < len(s.frames):          # the head of the next frame behind this frame's tracking: its planes go to the other of the two sets
             self._solo_enqueue_head(k + 1)
+        self._sgm_next(k)
 
     def _enqueue_live(self, k):
         from . import viode
@@ -442,8 +479,7 @@ class DynamicPipeline(Pipeline):
         if self.static_as_background and len(dets):
             ctx.track_unmask_static_keys(dets, self.static_ids_for(k), k0, DV_MEM_DEVICE)
         ctx.track_stereo_enqueue(l.data_ptr(), r.data_ptr(), s.times[k], inv, self.mode, DV_MEM_DEVICE)
-        if self.extra_from_disparity and len(getattr(s, "disp_dev", [])):
-            ctx.inst_set_disparity(s.disp_dev[k].data_ptr(), s.baseline, DV_MEM_DEVICE)
+        self._set_disparity(k)
         if k1:
             ctx.inst_set_right_keys(k1, DV_MEM_DEVICE)
         ctx.inst_track_enqueue_keys(s.times[k], dets, k0, DV_MEM_DEVICE)
@@ -451,6 +487,7 @@ class DynamicPipeline(Pipeline):
         if k + 1 < len(s.frames):          # T1's stage of the next frame behind this frame's tracking: its boxes are there when the host turns to it
             ctx.viode_frame_enqueue(s.seg0[k + 1], s.seg1[k + 1], s.dyn_keys)
             self._live_enq = k + 1
+        self._sgm_next(k)
 
     def _enqueue(self, k):
         if self.mask_stack:
@@ -463,12 +500,15 @@ class DynamicPipeline(Pipeline):
         if self.static_as_background and len(self.seq.dets[k]):
             self.ctx.track_unmask_static(self.seq.dets[k], self.static_ids_for(k))
         self.ctx.track_stereo_enqueue(l.data_ptr(), r.data_ptr(), self.seq.times[k], self.seq.inv_mask_dev[k].data_ptr(), self.mode, DV_MEM_DEVICE)
-        if self.extra_from_disparity:      # the extra points of the objects: DetectExtraPoints + ProcessExtraPoints on the device from the frame's disparity map
+        if self.stereo_sgm is not None:
+            self._set_disparity(k)
+        elif self.extra_from_disparity:      # the extra points of the objects: DetectExtraPoints + ProcessExtraPoints on the device from the frame's disparity map
             self.ctx.inst_set_disparity(self.seq.disp_dev[k].data_ptr(), self.seq.baseline, DV_MEM_DEVICE)
         if getattr(self.seq, "right_keys", None) is not None:      # VIODE: seg1's key image -> TrackRightByPad's segmentation-key test
             self.ctx.inst_set_right_keys(self.seq.right_keys[k])
         self.ctx.inst_track_enqueue(self.seq.times[k], self.seq.dets[k], self.seq.boxes3d[k] if self.use_det3d else None)
         self.enqueued = True
+        self._sgm_next(k)
 
     def _collect(self):
         return (self.ctx.track_stereo_collect(),) + tuple(self.ctx.inst_track_collect())

@@ -292,6 +292,38 @@ typedef struct dv_solo_input_params { int32_t model_w, model_h; float mean[3], s
 int dv_solo_input_check(int img_w, int img_h, int stride, const dv_solo_input_params* par);
 int dv_solo_input_enqueue(dv_ctx* ctx, const uint8_t* bgr, int stride, int mem, const dv_solo_input_params* par, float* dst_dev);
 int dv_solo_input_collect(dv_ctx* ctx, const float** input_dev, int* rect_x, int* rect_y, int* rect_w, int* rect_h);
+/* The STEREO MATCHER for ONE frame: the rectified gray pair -> the float disparity map of the left image, on the device: what MyStereoMatcher::Launch (stereo/stereo.cpp,
+ * an empty StereoMatch()) leaves to an offline network and MyStereoMatcher::WaitResult reads back from a PNG into SemanticImage::disp.  The reference has no matcher to
+ * restate; this one is a semi-global matcher specified in integers, so a numpy restatement matches it bit for bit.  w x h are the ctx's; a left
+ * pixel (x, y) with disparity d matches the right pixel (x - d, y), d in [0, n_disp).
+ *   census       9 wide x 7 high, source coordinates clamped to the image; one bit per non-centre position, set where neighbour < centre: 62 bits in a uint64.
+ *   cost         C(x, y, d) = popcount(cL(x, y) ^ cR(x - d, y)) for x - d >= 0, and 64 for x - d < 0.
+ *   paths        eight directions r; L_r(p, d) = C(p, d) + min(L_r(p-r, d), L_r(p-r, d-1) + p1, L_r(p-r, d+1) + p1, m + p2) - m with m = min_k L_r(p-r, k); terms with
+ *                d +- 1 outside [0, n_disp) are left out; L_r(p, d) = C(p, d) where p - r lies outside the image.  S = the sum over the eight directions (16 bits).
+ *   winner       d* = argmin_d S(p, d), ties to the lowest d.
+ *   uniqueness   OpenCV's integer rule: invalid if some d with |d - d*| > 1 has S(p, d) (100 - uniqueness) < S(p, d*) 100.
+ *   left-right   dR(x, y) = argmin_d S((x + d, y), d) over x + d < w, ties to the lowest d; invalid if |dR(x - d*, y) - d*| > lr_max_diff (lr_max_diff < 0: no test);
+ *                d* > x is invalid.
+ *   subpixel     for 0 < d* < n_disp - 1: den = max(S(d*-1) + S(d*+1) - 2 S(d*), 1), d16 = 16 d* + floor((16 (S(d*-1) - S(d*+1)) + den) / (2 den)), a mathematical
+ *                floor; d16 = 16 d* at the two ends.
+ *   output       float(d16) / 16, +0.0f where invalid (DetectExtraPoints reads disparity > 0 as "has a disparity").  Every element is written every frame.
+ * Refused, each with its own dv_last_error text: n_disp other than 64, 128, 256; p1 < 0; p2 < p1; p2 > 255; uniqueness outside [0, 100); a non-zero reserved word;
+ * stride < w; non-positive sizes; an unknown memory kind.  dv_stereo_sgm_check: those refusals without a device (0, or < 0 with dv_last_error(NULL)).
+ * _enqueue: on the ctx's stream.  mem = DV_MEM_HOST (both images staged) or DV_MEM_DEVICE / DV_MEM_PINNED (read in place, any base alignment, valid until the collect).
+ * One frame may be in flight.  _collect waits and returns one of two library-owned maps used alternately (rows of *stride_bytes = 4 w): the pointer stays valid until
+ * the SECOND enqueue after it and goes straight into dv_inst_set_disparity(ctx, p, stride, DV_MEM_DEVICE, baseline) — SemanticImage::disp without a host round trip.
+ * dv_stereo_sgm_debug: for tests — of the last COLLECTED frame, what = DV_SGM_DEBUG_CENSUS_L / _R (w x h uint64), _S (h x w x n_disp uint16), _DSTAR / _DR (w x h int16:
+ * the winner and the right image's winner, before any validity test); cap_bytes must cover it. */
+typedef struct dv_sgm_params { int32_t n_disp /* 64, 128, 256 */, p1 /* 10 */, p2 /* 120 */, uniqueness /* 5 */, lr_max_diff /* 1 */, reserved[3] /* zero */; } dv_sgm_params;
+#define DV_SGM_DEBUG_CENSUS_L 0
+#define DV_SGM_DEBUG_CENSUS_R 1
+#define DV_SGM_DEBUG_S        2
+#define DV_SGM_DEBUG_DSTAR    3
+#define DV_SGM_DEBUG_DR       4
+int dv_stereo_sgm_check(int w, int h, int stride, const dv_sgm_params* par);
+int dv_stereo_sgm_enqueue(dv_ctx* ctx, const uint8_t* gray0, const uint8_t* gray1, int stride, int mem, const dv_sgm_params* par);
+int dv_stereo_sgm_collect(dv_ctx* ctx, const float** disp_dev, int* stride_bytes);
+int dv_stereo_sgm_debug(dv_ctx* ctx, int what, void* host, long long cap_bytes);
 /* The MULTI-OBJECT TRACKER between the detector and the object tracker: a frame's detection rectangles and appearance embeddings -> a track id per detection, as
  * InstsFeatManager::AddInstancesByTracking (front_end/dynamic_tracker.cpp:791-828) gets them from DeepSORT::update (mot/deep_sort.cpp:72-139).  Track table and appearance
  * galleries stay in HBM between frames.  The ReID network (mot/reid_net.cpp, mot/extractor.cpp) stays with the caller: feats is its output, [n, feat_dim] float32 rows
