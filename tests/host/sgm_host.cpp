@@ -1,5 +1,5 @@
 // The stereo matcher's host rules (csrc/stereo_sgm_host.h) as a stand-alone program for the sanitizers: the census at clamped borders, the cost rule, the path step,
-// the uniqueness test, the floored subpixel division and every refusal.  Prints "sgm_host ok"; any failed check aborts.
+// the uniqueness test, the floored subpixel division and every refusal, the census and the cost also on the smallest frames (narrower than n_disp, 1 x 1).  Prints "sgm_host ok"; any failed check aborts.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -39,6 +39,47 @@ int main() {
         CHECK(dv_sgm_popcount(dv_sgm_census(img.data(), stride, w, h, w - 1, h - 1)) > 0);
         std::vector<uint8_t> one(1, 200);                                                            // a 1 x 1 image: every neighbour is the centre
         CHECK(dv_sgm_census(one.data(), 1, 1, 1, 0, 0) == 0);
+    }
+    // the matcher's smallest frames (tests/sgm_hostile.py: narrower than n_disp, one row, one column, 1 x 1), tight rows and rows of w + 5 bytes, on exactly sized heap
+    // blocks: the census against the clamp written out; the cost of every (x, d) with the right code fetched only where x - d >= 0, as the path kernel fetches it; the
+    // right winner's range x + d < w; the frame accepted for every n_disp
+    {
+        const int shapes[][2] = {{37, 6}, {5, 3}, {63, 2}, {70, 1}, {130, 1}, {1, 9}, {1, 1}, {2, 2}};
+        for (const auto& sh : shapes) for (int extra : {0, 5}) {
+            const int w = sh[0], h = sh[1], stride = w + extra;
+            std::vector<uint8_t> img((size_t)(h - 1) * stride + w);
+            for (int y = 0; y < h; ++y) for (int x = 0; x < w; ++x) img[(size_t)y * stride + x] = (uint8_t)((37 * x + 101 * y + (x * y) % 7) & 255);
+            std::vector<uint64_t> code((size_t)w * h);
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x) {
+                    uint64_t want = 0;
+                    const int c = img[(size_t)y * stride + x];
+                    for (int dy = -3; dy <= 3; ++dy)
+                        for (int dx = -4; dx <= 4; ++dx) {
+                            if (!dx && !dy) continue;
+                            const int yy = y + dy < 0 ? 0 : (y + dy > h - 1 ? h - 1 : y + dy), xx = x + dx < 0 ? 0 : (x + dx > w - 1 ? w - 1 : x + dx);
+                            want = (want << 1) | (uint64_t)(img[(size_t)yy * stride + xx] < c);
+                        }
+                    CHECK((code[(size_t)y * w + x] = dv_sgm_census(img.data(), stride, w, h, x, y)) == want);
+                }
+            if (w == 1 && h == 1) CHECK(code[0] == 0);
+            for (int D : {64, 128, 256}) {
+                const dv_sgm_params p = params(D);
+                CHECK(!dv_sgm_check_host(w, h, stride, &p) && (extra == 0 || refused(w, h, w - 1, p, "row stride below width")));
+                for (int y = 0; y < h; ++y)
+                    for (int x = 0; x < w; ++x) {
+                        int outside = 0, reach = 0;
+                        for (int d = 0; d < D; ++d) {
+                            const int xr = x - d;
+                            const int c = dv_sgm_cost(code[(size_t)y * w + x], xr >= 0 ? code[(size_t)y * w + xr] : 0, x, d);
+                            CHECK(xr >= 0 ? (c >= 0 && c <= 62) : c == DV_SGM_OOB_COST);
+                            outside += xr < 0; reach += x + d < w;
+                        }
+                        CHECK(outside == (D - 1 - x > 0 ? D - 1 - x : 0) && reach == (w - x < D ? w - x : D) && reach >= 1);      // d = 0 always has a pixel on both sides
+                    }
+            }
+        }
+        for (int D : {64, 128, 256}) CHECK(dv_sgm_subpixel(D - 1, D, 7, 1, 0) == 16 * (D - 1) && dv_sgm_subpixel(D - 2, D, 9, 1, 9) == 16 * (D - 2) && dv_sgm_subpixel(0, D, 0, 1, 7) == 0);
     }
     // cost
     CHECK(dv_sgm_cost(0, ~0ull, 5, 6) == 64 && dv_sgm_cost(0x3ull, 0x1ull, 5, 5) == 1 && dv_sgm_cost(~0ull >> 2, 0, 9, 0) == 62 && dv_sgm_cost(7, 7, 0, 0) == 0);

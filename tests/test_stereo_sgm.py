@@ -48,9 +48,10 @@ def reference(shape, kind, seed=11, **par):
 
 
 def run(ctx, shape, l, r, mem="host", keep=None, **par):
+    """shape: a name of SHAPES, or its tuple (tests/test_stereo_sgm_hostile.py brings its own)"""
     import torch
     from dynamic_vins_amd.frontend import DV_MEM_DEVICE, DV_MEM_PINNED, sgm_params
-    w, h, D, extra, lead = SHAPES[shape]
+    w, h, D, extra, lead = SHAPES[shape] if isinstance(shape, str) else shape
     p = sgm_params(n_disp=D, **par)
     (fl, vl), (fr, vr) = laid_out(l, extra, lead), laid_out(r, extra, lead)
     if mem == "host":
