@@ -343,7 +343,10 @@ int dv_track_stereo_collect(dv_ctx* ctx, dv_feat* out, int* n_out) {
     if (ctx->timing) dv_harvest_timers(ctx, ctx->stream);
     if (*ctx->err_pinned) {
         int f = *ctx->err_pinned;
+        // cleared before this call returns: the next frame may run on another stream than this memset (a group member's frames run on the group's stream, and front_plan
+        // orders a frame behind last_done only), where the word could be wiped under that frame's selection, or still be set when its finalize copies it
         DV_CHECK(hipMemsetAsync(ctx->err_flag, 0, 4, ctx->stream));
+        DV_CHECK(hipStreamSynchronize(ctx->stream));
         DV_FAIL(std::string("front end device error flags=") + std::to_string(f) +
                 " (1: candidate buffer overflow, 2: min-distance grid too large, 4: value bin overflow)");
     }

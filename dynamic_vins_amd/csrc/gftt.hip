@@ -242,7 +242,7 @@ __device__ __forceinline__ void gftt_select_body(const GfttSelectArgs& a) {
     short* acc_y = acc_x + SEL_MAX_ACC;
     short* acc_next = acc_y + SEL_MAX_ACC;
     short* head = acc_next + SEL_MAX_ACC;                                                       // cells
-    int& s_m = ctl[0]; int& s_acc = ctl[1]; int& s_lo = ctl[2]; int& s_hi = ctl[3]; int& s_done = ctl[4];
+    int& s_m = ctl[0]; int& s_acc = ctl[1]; int& s_lo = ctl[2]; int& s_hi = ctl[3]; int& s_done = ctl[4]; int& s_over = ctl[5];
     const int tid = threadIdx.x;
     const int w = a.w, h = a.h;
 
@@ -265,7 +265,7 @@ __device__ __forceinline__ void gftt_select_body(const GfttSelectArgs& a) {
 
     for (int i = tid; i <= SEL_BINS; i += SEL_THREADS) hist[i] = 0;
     if (use_grid && gw * gh <= SEL_MAX_CELLS) for (int i = tid; i < gw * gh; i += SEL_THREADS) head[i] = -1;      // (a refused grid is not initialised: head holds SEL_MAX_CELLS entries)
-    if (tid == 0) { s_acc = 0; s_hi = SEL_BINS - 1; s_done = 0; }
+    if (tid == 0) { s_acc = 0; s_hi = SEL_BINS - 1; s_done = 0; s_over = 0; }
     __syncthreads();
     // a candidate survives THRESH_TOZERO iff v > thr (v < 0 can never survive: thr >= 0 whenever maxVal >= 0)
     auto valid_bin = [&](const DvCand& c) -> int {
@@ -313,9 +313,12 @@ __device__ __forceinline__ void gftt_select_body(const GfttSelectArgs& a) {
             const int target = min(SEL_CAP, max(512, 16 * (max_n - s_acc)));
             for (int b = tid; b <= hi; b += SEL_THREADS)
                 if (hist[b] - above <= target) atomicMin(&s_lo, b);
-            if (tid == 0 && hist[hi] - above > SEL_CAP && a.err_flag) atomicOr(a.err_flag, 4);   // one bin overflows a chunk
+            // one bin overflows a chunk: WHICH 8192 of its candidates a chunk would hold follows the order the tiles emitted them in, which no two runs share — the
+            // selection ends with what the bins above gave (s_over is read behind the barrier below, by every thread alike)
+            if (tid == 0 && hist[hi] - above > SEL_CAP) { if (a.err_flag) atomicOr(a.err_flag, 4); s_over = 1; }
         }
         __syncthreads();
+        if (s_over) break;
         const int lo = s_lo;
         for (int i0 = tid; i0 < n_cand; i0 += 8 * SEL_THREADS) {
             DvCand cb[8];

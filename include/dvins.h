@@ -138,7 +138,8 @@ int dv_pyr_down_cuda(dv_ctx* ctx, const uint8_t* src, int w, int h, int stride, 
  *           min_dist < 1 uses no grid and has no such limit;
  *   flag 4  the selection, taking the 2048 equal bins between the quality threshold and the maximum from the top, reaches a bin with more than 8192
  *           candidates before max_n corners are accepted (many exactly equal responses: a 4 px checkerboard over 320 x 240); a request that is
- *           met from the bins above such a bin is served.
+ *           met from the bins above such a bin is served.  Inside dv_track_stereo* the refused frame keeps the corners the bins above gave and takes none from
+ *           that bin on: the tracker's state behind a refused frame is the same in every run.
  * At most 1024 corners are returned (max_n <= 0: 1024). */
 int dv_gftt(dv_ctx* ctx, const uint8_t* img, const uint8_t* mask_or_null, int w, int h, int stride,
             int max_n, double quality, double min_dist, float* out_xy, int* n_out, int mem);
