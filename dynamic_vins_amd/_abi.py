@@ -159,6 +159,7 @@ SIGNATURES = {
     "dv_reid_get_feats": (C.c_int, [_ctx, C.c_void_p, C.c_int]),
     "dv_reid_input": (C.c_int, [_ctx, C.c_void_p]),
     "dv_reid_layer": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "dv_reid_stem": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dv_inst_track_enqueue_planes": (C.c_int, [_ctx, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "dv_track_unmask_static_planes": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dv_inst_set_disparity": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int, C.c_double]),

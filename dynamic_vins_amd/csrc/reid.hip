@@ -370,4 +370,33 @@ int dv_reid_layer(dv_ctx* ctx, const float* x, int n, int c_in, int h, int w, co
     return 0;
 }
 
+int dv_reid_stem(dv_ctx* ctx, const float* x, int n, int h, int w, const float* weight, const float* scale, const float* shift, float* out) {
+    if (!ctx) return -1;
+    if (const char* why = dv_reid_stem_check_host(n, h, w)) DV_FAIL(std::string("dv_reid_stem: ") + why);
+    if (!x || !weight || !scale || !shift || !out) DV_FAIL("dv_reid_stem: null argument");
+    if (ctx->reid && ctx->reid->slot.pending) DV_FAIL("dv_reid_stem: a frame is in flight");
+    if (!ctx->reid) ctx->reid = new ReidNet();
+    ReidNet& R = *ctx->reid;
+    DV_CHECK(hipSetDevice(ctx->cfg.device));
+    const int hp = dv_reid_half(h), wp = dv_reid_half(w);
+    const size_t nx = (size_t)n * 3 * h * w, nw = 27 * (size_t)DV_REID_C1, ny = (size_t)n * hp * wp * DV_REID_C1;
+    // host side: the input as it is (the kernel reads NCHW), conv1's weight into the kernel's layout; one device buffer x | w | scale | shift | y
+    std::vector<float> hb(nx + nw + 2 * (size_t)DV_REID_C1 + ny);
+    float* hx = hb.data(); float* hw = hx + nx; float* hs = hw + nw; float* hy = hs + 2 * DV_REID_C1;
+    std::memcpy(hx, x, nx * 4);
+    dv_reid_pack_c1(weight, hw);
+    std::memcpy(hs, scale, (size_t)DV_REID_C1 * 4); std::memcpy(hs + DV_REID_C1, shift, (size_t)DV_REID_C1 * 4);
+    DV_CHECK(R.op.ensure(hb.size() * 4));
+    float* d = (float*)R.op.p;
+    DV_CHECK(hipMemcpy(d, hb.data(), (hb.size() - ny) * 4, hipMemcpyHostToDevice));      // blocking both ways, as in dv_reid_layer
+    float* dw = d + nx; float* ds = dw + nw; float* dy = ds + 2 * DV_REID_C1;
+    StemArgs sa{d, dw, ds, ds + DV_REID_C1, dy, h, w, hp, wp};
+    hipLaunchKernelGGL(reid_stem_kernel, dim3((hp * wp + 3) / 4, n), dim3(256), 0, ctx->stream, sa);
+    DV_CHECK(hipGetLastError());
+    DV_CHECK(hipStreamSynchronize(ctx->stream));
+    DV_CHECK(hipMemcpy(hy, dy, ny * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < n; ++b) for (int c = 0; c < DV_REID_C1; ++c) for (int p = 0; p < hp * wp; ++p) out[((size_t)b * DV_REID_C1 + c) * hp * wp + p] = hy[((size_t)b * hp * wp + p) * DV_REID_C1 + c];
+    return 0;
+}
+
 }  // extern "C"

@@ -81,6 +81,12 @@ static inline const char* dv_reid_layer_check_host(int n, int c_in, int h, int w
     if ((long long)n * h * w * (c_in > c_out ? c_in : c_out) > (1LL << 24)) return "n * h * w * channels beyond 2^24 elements";
     return nullptr;
 }
+// the reason dv_reid_stem refuses its shapes, or nullptr: at most 64 x 3 x 128 x 128 in and 64 x 64 x 64 x 64 out, the 2^24 elements of the layer operator
+static inline const char* dv_reid_stem_check_host(int n, int h, int w) {
+    if (n < 1 || n > DV_REID_MAX_CROPS) return "1..64 images";
+    if (h < 1 || h > 128 || w < 1 || w > 128) return "height and width 1..128";
+    return nullptr;
+}
 constexpr int dv_reid_out_size(int n, int k, int stride) { return (n + (k == 3 ? 2 : 0) - k) / stride + 1; }
 
 // Eval-mode batch-norm as y = x * scale + shift, in float64, rounded once: scale = w / sqrt(var + eps), shift = b - mean * scale (+ conv_bias * scale).  A declared

@@ -826,6 +826,18 @@ class Context:
                                            residual.ctypes.data if residual is not None else None, int(bool(relu)), out.ctypes.data))
         return out
 
+    def reid_stem(self, x, weight, scale, shift):
+        """the extractor's fused stem kernel alone: max_pool2d(relu(conv2d(x, weight, padding 1) * scale + shift), 3, 2, 1), x [n, 3, h, w] -> [n, 64, ceil(h / 2),
+        ceil(w / 2)], NCHW float32"""
+        x, weight = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(weight, np.float32)
+        scale, shift = np.ascontiguousarray(scale, np.float32), np.ascontiguousarray(shift, np.float32)
+        if x.ndim != 4 or x.shape[1] != 3 or weight.shape != (64, 3, 3, 3) or scale.shape != (64,) or shift.shape != (64,):
+            raise ValueError("reid_stem: x [n, 3, h, w], weight [64, 3, 3, 3], scale and shift [64]")
+        n, _, h, w = x.shape
+        out = np.zeros((n, 64, max((h + 1) // 2, 1), max((w + 1) // 2, 1)), np.float32)
+        self._check(self.lib.dv_reid_stem(self.h, x.ctypes.data, n, h, w, weight.ctypes.data, scale.ctypes.data, shift.ctypes.data, out.ctypes.data))
+        return out
+
     def solo_head(self, outputs, params):
         """solo_head_enqueue + solo_head_collect"""
         self.solo_head_enqueue(outputs, params)

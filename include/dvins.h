@@ -410,7 +410,9 @@ int dv_mot_assign(dv_ctx* ctx, const float* cost, int rows, int cols, int32_t* a
  * dv_reid_get_feats: the first n rows of the last collected frame, downloaded (tests, the shim).  dv_reid_input: the prepared [n, 3, in_h, in_w] tensor of the last frame.
  * dv_reid_layer: the operator form of the convolution kernel alone on host tensors: x [n, c_in, h, w], weight [c_out, c_in, k, k], scale and shift [c_out], residual
  * [n, c_out, h_out, w_out] or null -> out [n, c_out, h_out, w_out] = relu?(conv(x) * scale + shift + residual), h_out = (h + 2 pad - k) / stride + 1 with pad 1 for
- * k = 3 and 0 for k = 1.  (k, stride) in {(3, 1), (3, 2), (1, 2)}, c_in a multiple of 32, c_out of 64, both <= 512, h and w <= 128, n <= 64, n h w max(c_in, c_out) <= 2^24. */
+ * k = 3 and 0 for k = 1.  (k, stride) in {(3, 1), (3, 2), (1, 2)}, c_in a multiple of 32, c_out of 64, both <= 512, h and w <= 128, n <= 64, n h w max(c_in, c_out) <= 2^24.
+ * dv_reid_stem: the operator form of the fused stem kernel alone on host tensors: x [n, 3, h, w], weight [64, 3, 3, 3], scale and shift [64] -> out [n, 64, ceil(h / 2),
+ * ceil(w / 2)] = max_pool2d(relu(conv(x, padding 1) * scale + shift), 3, 2, 1).  n in 1..64, h and w in 1..128.  Both operators are refused while a frame is in flight. */
 #define DV_REID_N_FLOATS 11178496
 #define DV_REID_FEAT_DIM 512
 #define DV_REID_MAX_CROPS 64
@@ -422,6 +424,7 @@ int dv_reid_get_feats(dv_ctx* ctx, float* out, int n);
 int dv_reid_input(dv_ctx* ctx, float* out);
 int dv_reid_layer(dv_ctx* ctx, const float* x, int n, int c_in, int h, int w, const float* weight, int c_out, int k, int stride, const float* scale, const float* shift,
                   const float* residual_or_null, int relu, float* out);
+int dv_reid_stem(dv_ctx* ctx, const float* x, int n, int h, int w, const float* weight, const float* scale, const float* shift, float* out);
 /* cv::cvtColor(BGR2GRAY) on 8-bit images: (B 1868 + G 9617 + R 4899 + 8192) >> 14; gray is w x h, tightly packed */
 int dv_bgr2gray(dv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, uint8_t* gray, int mem);
 /* cv::remap(src, dst, map1, map2, INTER_LINEAR) — BORDER_CONSTANT 0 — with the fixed-point maps cv::initUndistortRectifyMap(..., CV_16SC2, ...)

@@ -1,6 +1,7 @@
 // The ReID extractor's host rules (csrc/reid_host.h) as a stand-alone program for the sanitizers: the layer list and its offsets into the weight file, the accepted
 // sizes, the refusals, the fold, the weight layouts, cvRound of rectangles, and the resize rule on small crops whose every read must stay inside the crop.
-// Prints "reid_host ok"; tests/test_reid_ref.py builds it through reid.mk and runs it.
+// Then the rectangles of tests/reid_hostile.py on frames of a camera's size, each printed as it is walked.
+// Prints "reid_host ok"; tests/test_reid_ref.py and tests/test_reid_hostile_ref.py build it through reid.mk and run it.
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -88,6 +89,47 @@ int main() {
       dv_reid_coef(1, 32, 64, false, &i0, &i1, &c0, &c1); EXPECT(i0 == 0 && i1 == 1 && c0 == 1536 && c1 == 512);
       dv_reid_coef(63, 32, 64, false, &i0, &i1, &c0, &c1); EXPECT(i0 == 31 && i1 == 31 && c0 == 2048 && c1 == 0); }
     EXPECT(dv_reid_area2(128, 256, 64, 128) && !dv_reid_area2(128, 255, 64, 128));
+
+    // the stem operator's refusals, and the limit shapes of tests/reid_hostile.py within the layer operator's 2^24 elements
+    EXPECT(!dv_reid_stem_check_host(1, 1, 1) && !dv_reid_stem_check_host(64, 128, 128) && !dv_reid_stem_check_host(3, 121, 57));
+    EXPECT(dv_reid_stem_check_host(0, 8, 8) && dv_reid_stem_check_host(65, 8, 8) && dv_reid_stem_check_host(1, 0, 8) && dv_reid_stem_check_host(1, 8, 0) && dv_reid_stem_check_host(1, 129, 8) &&
+           dv_reid_stem_check_host(1, 8, 129) && dv_reid_stem_check_host(-1, 8, 8));
+    { static const int PAIRS[4][2] = {{32, 64}, {96, 192}, {160, 320}, {512, 192}}, KS[3][2] = {{3, 1}, {3, 2}, {1, 2}}, MAPS[2][2] = {{9, 7}, {17, 13}};
+      for (const auto& p : PAIRS) for (const auto& ks : KS) for (const auto& m : MAPS) EXPECT(!dv_reid_layer_check_host(3, p[0], m[0], m[1], p[1], ks[0], ks[1]));
+      static const int NET[7][7] = {{1, 64, 128, 128, 64, 3, 1}, {2, 64, 61, 29, 64, 3, 1}, {2, 64, 61, 29, 128, 3, 2}, {2, 64, 64, 32, 128, 3, 2}, {2, 128, 31, 15, 256, 3, 2}, {2, 256, 16, 8, 512, 3, 2}, {64, 512, 8, 4, 512, 3, 1}};
+      for (const auto& c : NET) { EXPECT(!dv_reid_layer_check_host(c[0], c[1], c[2], c[3], c[4], c[5], c[6])); EXPECT((long long)c[0] * c[2] * c[3] * (c[1] > c[4] ? c[1] : c[4]) <= (1LL << 24)); }
+      EXPECT(!dv_reid_layer_check_host(24, 64, 17, 13, 64, 3, 1)); }      // the impulse cases' batch
+
+    // crops at camera geometry: the rectangles of tests/reid_hostile.py (camera_rects; tests/test_reid_hostile_ref.py compares the lines printed here with its list) on
+    // images of exactly H rows of 3 W + 5 bytes.  Every prepared byte is computed twice: from the frame, and from a copy of the crop in an allocation of exactly its size
+    // with packed rows, where a read past the crop's edge is either a different byte or the sanitizer's business
+    static const int CTX[3][2] = {{752, 480}, {1242, 375}, {480, 752}}, INSZ[2][2] = {{64, 128}, {57, 121}};
+    for (const auto& cx : CTX) {
+        const int W = cx[0], H = cx[1], stride = 3 * W + 5;
+        std::vector<uint8_t> frame((size_t)stride * H);
+        for (size_t i = 0; i < frame.size(); ++i) frame[i] = (uint8_t)((i * 2654435761u) >> 13);
+        for (const auto& is : INSZ) {
+            const int iw = is[0], ih = is[1];
+            const float gx = 37, gy = 11;
+            const float R[24][4] = {{gx, gy, 3.f * iw, 3.f * ih}, {gx, gy, 4.f * iw, 4.f * ih}, {gx, gy, 4.f * iw, 3.f * ih}, {gx, gy, 2.f * iw, 1.f * ih}, {gx, gy, 1.f * iw, 2.f * ih},
+                                    {gx, gy, 2.f * iw, 2.f * ih}, {gx, gy, 2.f * iw - 1, 2.f * ih}, {gx, gy, 2.f * iw + 1, 2.f * ih}, {gx, gy, 2.f * iw, 2.f * ih - 1}, {gx, gy, 2.f * iw, 2.f * ih + 1},
+                                    {gx, gy, (float)((3 * iw + 1) / 2), (float)((3 * ih + 1) / 2)}, {gx, gy, 200, 333}, {gx, gy, (float)iw, (float)ih}, {0, 0, (float)W, (float)H},
+                                    {0, 0, 150, 290}, {W - 150.f, 0, 150, 290}, {0, H - 290.f, 150, 290}, {W - 150.f, H - 290.f, 150, 290},
+                                    {W - 1.f, 0, 1, (float)H}, {0, H - 1.f, (float)W, 1}, {W - 1.f, H - 1.f, 1, 1},
+                                    {W - 100.5f, H - 200.5f, 100.5f, H % 2 == 0 ? 200.5f : 201.f}, {0.5f, 0.5f, 2.5f, 3.5f}, {0.5f, 0.5f, W - 0.5f, H - 0.5f}};
+            for (const auto& r : R) {
+                if (!dv_reid_rect(r, W, H, q)) continue;
+                std::printf("rect %d %d %d %d %d %d %d %d\n", W, H, iw, ih, q[0], q[1], q[2], q[3]);
+                std::vector<uint8_t> crop((size_t)q[2] * q[3] * 3);
+                for (int y = 0; y < q[3]; ++y) std::memcpy(crop.data() + (size_t)y * q[2] * 3, frame.data() + (size_t)(q[1] + y) * stride + (size_t)q[0] * 3, (size_t)q[2] * 3);
+                const int rq[4] = {0, 0, q[2], q[3]};
+                int differ = 0;
+                for (int dy = 0; dy < ih; ++dy) for (int dx = 0; dx < iw; ++dx) for (int c = 0; c < 3; ++c)
+                    differ += dv_reid_pixel(frame.data(), stride, q, iw, ih, dx, dy, c) != dv_reid_pixel(crop.data(), 3 * q[2], rq, iw, ih, dx, dy, c);
+                EXPECT(differ == 0);
+            }
+        }
+    }
 
     std::printf(fails ? "reid_host: %d FAILED\n" : "reid_host ok\n", fails);
     return fails ? 1 : 0;
