@@ -3,6 +3,7 @@
 // between iterations: every kernel is predicated on the device-resident BeCtl) and downloads the solved states.
 #include <algorithm>
 #include "be_host.h"
+#include "est_window.h"
 
 static_assert(sizeof(dv_ba_factor) == sizeof(BeFactor), "public/private factor layouts must match");
 static_assert(sizeof(dv_ba_lm) == sizeof(BeLm), "public/private landmark layouts must match");
@@ -78,31 +79,6 @@ int be_prepare(dv_ctx* ctx, bool dynamic) {
     return 0;
 }
 
-// 15x15: U upper-triangular with U^T U = cov^-1   (LLT(cov^-1).matrixL().transpose(), imu_factor.h:74-75; cached, Q8)
-static bool imu_sqrt_info(const double* cov, double* U) {
-    double a[15][30];
-    for (int i = 0; i < 15; ++i) for (int j = 0; j < 15; ++j) { a[i][j] = cov[i * 15 + j]; a[i][15 + j] = i == j ? 1.0 : 0.0; }
-    for (int c = 0; c < 15; ++c) {
-        int p = c; for (int i = c + 1; i < 15; ++i) if (std::fabs(a[i][c]) > std::fabs(a[p][c])) p = i;
-        if (a[p][c] == 0.0) return false;
-        if (p != c) for (int j = 0; j < 30; ++j) std::swap(a[c][j], a[p][j]);
-        const double piv = a[c][c];
-        for (int j = 0; j < 30; ++j) a[c][j] /= piv;
-        for (int i = 0; i < 15; ++i) if (i != c) { const double f = a[i][c]; if (f != 0.0) for (int j = 0; j < 30; ++j) a[i][j] -= f * a[c][j]; }
-    }
-    double inv[15][15], L[15][15] = { { 0 } };
-    for (int i = 0; i < 15; ++i) for (int j = 0; j < 15; ++j) inv[i][j] = 0.5 * (a[i][15 + j] + a[j][15 + i]);
-    for (int j = 0; j < 15; ++j) {
-        double s = inv[j][j];
-        for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
-        if (!(s > 0)) return false;
-        const double d = std::sqrt(s); L[j][j] = d;
-        for (int i = j + 1; i < 15; ++i) { double t = inv[i][j]; for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k]; L[i][j] = t / d; }
-    }
-    for (int i = 0; i < 15; ++i) for (int j = 0; j < 15; ++j) U[i * 15 + j] = L[j][i];
-    return true;
-}
-
 int be_fill_imu(const dv_ba_imu& in, BeImu& o, const double* sqrt_hint) {
     o.sum_dt = in.sum_dt;
     for (int k = 0; k < 3; ++k) { o.dp[k] = in.dp[k]; o.dv[k] = in.dv[k]; o.lin_ba[k] = in.lin_ba[k]; o.lin_bg[k] = in.lin_bg[k]; }
@@ -111,9 +87,9 @@ int be_fill_imu(const dv_ba_imu& in, BeImu& o, const double* sqrt_hint) {
     blk(0, 9, o.dp_dba); blk(0, 12, o.dp_dbg); blk(3, 12, o.dq_dbg); blk(6, 9, o.dv_dba); blk(6, 12, o.dv_dbg);
     o.fi = in.fi; o.fj = in.fj; o.pad0 = o.pad1 = 0;
     if (sqrt_hint) { std::memcpy(o.sqrt_info, sqrt_hint, sizeof(o.sqrt_info)); return 0; }
-    return imu_sqrt_info(in.covariance, o.sqrt_info) ? 0 : -1;
+    return estw::imu_sqrt_info(in.covariance, o.sqrt_info) ? 0 : -1;
 }
-bool be_imu_sqrt_info(const double* cov, double* U) { return imu_sqrt_info(cov, U); }
+bool be_imu_sqrt_info(const double* cov, double* U) { return estw::imu_sqrt_info(cov, U); }      // (est_window.h, beside the pre-integration that owns the covariance)
 
 // The stages of one window's slots for be_run_slots (be_host.h): the member's arguments by value, the _ext launches of the free extrinsic / td blocks behind
 // evaluation and reduce, and per-launch events when kernel_timing is on.
